@@ -20,6 +20,16 @@ Extra objects: `roofline` for the dominant blend kernel (algorithmic bytes of SU
 intersections the launch actually processed, over its HIP-event duration on the launch stream),
 `roofline_compute` (the same kernel against the VALU issue rate, the limiter it actually has) and
 `cpu_baseline` (the C/OpenMP oracle timed on the host cores on a bounded sample; rank 0, N=1 only).
+
+A plain run sets up, warms up, times the K steps and prints the headline line (`metric`, `value`, `unit`,
+`ms_per_step`, `step_ms`, `config`, ...).  Everything else -- static view, hand-back and host-fed loops, forward fps,
+per-stage times, rooflines, extras, captured-step configs, `cpu_baseline`, `per_rank` -- runs with `--full` only
+(`--no-extras`, `--no-configs`, `--no-cpu-baseline` trim a `--full` run).
+
+`--dump-outputs DIR`: after the timed steps, what the last timed step handed its caller -- the rendered image,
+the three loss terms, and the Gaussians' parameters after the optimizer step plus the step's radii and
+absolute 2-D mean gradients on a fixed seeded sample of 65536 Gaussians -- as float32 / float64 DIR/<name>.npy.
+The workload, the targets and the view schedule are seeded: the same arguments give the same inputs.
 """
 from __future__ import annotations
 
@@ -58,6 +68,11 @@ def parse_args(argv=None):
     ap.add_argument("--no-configs", action="store_true", help="skip the captured-step figures on the long-list / S3 / S5 workloads")
     ap.add_argument("--torch-adam", action="store_true", help="torch.optim.Adam(fused=True) instead of the HIP Adam")
     ap.add_argument("--no-graph", action="store_true", help="enqueue every step from Python instead of replaying the captured hipGraph")
+    ap.add_argument("--full", action="store_true",
+                    help="also run every secondary measurement (static view, host-fed, forward fps, stage times, rooflines, extras, "
+                         "configs, CPU baseline); off: the headline alone")
+    ap.add_argument("--dump-outputs", metavar="DIR", default=None,
+                    help="write what the last timed step computed to DIR/<name>.npy (float32 / float64, <= 64 MB)")
     return ap.parse_args(argv)
 
 
@@ -142,6 +157,33 @@ def sq_counters(kernel_prefix: str):
         if k.startswith(kernel_prefix):
             return v, src
     return None, src
+
+
+DUMP_SAMPLE = 65536            # Gaussians in the seeded sample of --dump-outputs
+DUMP_LIMIT_BYTES = 64 << 20
+
+
+def dump_outputs(out_dir: str, model, render_img, loss3, radii, absgrad) -> int:
+    """--dump-outputs: the last timed step's image and loss terms in full, the parameters after its optimizer step and its
+    radii / absolute 2-D mean gradients on a fixed sample of Gaussians (seed 0, sorted indices, the same for the same
+    model size).  Returns the bytes written."""
+    import numpy as np
+    import torch
+    n = int(model.means.shape[0])
+    idx = np.sort(np.random.default_rng(0).choice(n, size=min(n, DUMP_SAMPLE), replace=False))
+    sel = torch.from_numpy(idx).to(model.means.device)
+    rows = lambda t: t.detach().reshape((n,) + tuple(t.shape[2:])).index_select(0, sel)   # [1, N, ...] -> [sample, ...]
+    arrays = {"render_img": render_img.detach(), "loss3": loss3.detach().reshape(-1), "gaussian_sample_index": idx.astype(np.float64),
+              "radii": rows(radii), "absgrad": rows(absgrad)}
+    for name in ("means", "quats", "log_scales", "logit_opacities", "sh_0", "sh_rest"):
+        arrays[name] = getattr(model, name).detach().index_select(0, sel)
+    arrays = {k: np.ascontiguousarray(v.float().cpu().numpy() if torch.is_tensor(v) else v) for k, v in arrays.items()}
+    total = sum(a.nbytes for a in arrays.values())
+    assert total <= DUMP_LIMIT_BYTES, f"--dump-outputs would write {total} bytes"
+    os.makedirs(out_dir, exist_ok=True)
+    for k, a in arrays.items():
+        np.save(os.path.join(out_dir, f"{k}.npy"), a)
+    return total
 
 
 def cpu_model() -> str:
@@ -522,6 +564,7 @@ def run_rank(args) -> int:
         exchange = "allreduce"
 
     one = torch.ones((), device=device)   # root gradient, allocated once (backward() would fill a new one per step)
+    last = {}   # what the latest step of the timed path handed back (--dump-outputs)
 
     def train_step(data=data, gt_img=gt_img):
         if vp is not None:
@@ -529,7 +572,9 @@ def run_rank(args) -> int:
         out = model(data, clamp=False)
         if vp is not None:
             vp.after_forward(data, out)
-        loss = loss_computer.get_loss_dict(out["render_img"], gt_img, mask)["total"]
+        ld = loss_computer.get_loss_dict(out["render_img"], gt_img, mask)
+        last["loss3"] = (ld["l1"], ld["ssim"], ld["total"])
+        loss = ld["total"]
         loss.backward(gradient=one)
         if vp is not None:
             vp.step(data, out)
@@ -572,7 +617,7 @@ def run_rank(args) -> int:
         if graph_step is not None:
             graph_step.step(datas[v], targets[v], mask)
         else:
-            train_step(datas[v], targets[v])
+            last["out"] = train_step(datas[v], targets[v])
         model.update_learning_rate(sched.step)
 
     step_fn = loop_step
@@ -643,6 +688,65 @@ def run_rank(args) -> int:
     if os.environ.get("GS_BENCH_TRACE") == "1":
         print("[bench] step ms: " + " ".join(f"{x:.3f}" for x in step_ms[:64]), file=sys.stderr, flush=True)
     graph_report = None if graph_step is None else graph_step.report()   # (of the headline run: the extras re-capture the runner)
+    if args.dump_outputs and rank == 0:
+        if graph_step is not None:   # (finish() ran inside the bracket: the runner's buffers hold the last step's results)
+            b = graph_step.buf
+            res = (b["render_colors"][0], b["loss3"], b["radii"], b["v_abs"])
+        else:
+            o = last["out"]
+            res = (o["render_img"], torch.stack(last["loss3"]), o["batch_radii"], o["batch_xys"].absgrad)
+        dump_outputs(args.dump_outputs, model, *res)
+
+    def headline_line(elapsed):
+        """The result line's headline part: what a plain run prints (a --full run adds its figures to it)."""
+        line = {
+            "metric": "train iters/sec + forward render fps, 1M Gaussians @ 1080p",
+            "value": round(world * args.steps / elapsed, 3), "unit": "iters/s",
+            "n_gpus": world, "steps": args.steps, "warmup": args.warmup,
+            "ms_per_step": round(1e3 * elapsed / args.steps, 4),
+            "spin_up_ms": spin_ms,
+            "higher_is_better": True, "scaling": "weak", "vs_baseline": None,
+            "dtype": "f32", "data": "synthetic",
+            "step_ms": _percentiles(step_ms),
+            "config": {"workload": f"{args.gaussians} Gaussians, {W}x{H}, SH degree {sc['sh_degree']}, "
+                                   "1 view per GPU per step, full train step (fwd + L1/SSIM + bwd + stats + Adam)",
+                       "view_schedule": f"{n_views} views (camera + target image), a fresh seeded permutation per epoch "
+                                        "(DataLoader shuffle=True, the reference's train.py:36-43), a different view every "
+                                        "step, means-LR schedule updated every step (train.py:140); TrainStepGraph at its class defaults "
+                                        "(handback='eager', inputs_ready off)",
+                       "list_mode": "tight (model default; image, radii, means2d bitwise identical to the gsplat-list mode, gradients equal to rounding: "
+                                    "<= 1e-4 of the tensor's largest entry)",
+                       "parallelism": f"view-dp{world}", "exchange": exchange,
+                       "dist_backend": dist.get_backend() if (world > 1 or force_dist) else None,
+                       "dist_world_size": dist.get_world_size() if (world > 1 or force_dist) else 1,
+                       "step_launch": ("hipGraph replay" if (world == 1 and not force_dist) else "hipGraph replay up to the first collective + 4 launches") if graph_step is not None else "eager",
+                       "exchange_bytes_per_rank": None if (world == 1 and not force_dist) else (
+                           {"all_gather_view_record": 16 * args.gaussians + 64, "all_reduce_geometry_stats": 4 * 13 * args.gaussians,
+                            "collectives_per_step": 2} if vp is not None else
+                           {"all_reduce_grads": 4 * 59 * args.gaussians, "all_reduce_stats": 12 * args.gaussians})},
+            # host diagnostics: ms/step the host spent enqueueing, and blocked on the list-size read-back (0 when
+            # the captured step is replayed: no read-back exists on that path)
+            "host": {"enqueue_ms_per_step": round(1e3 * t_enqueued / args.steps, 4),
+                     "blocked_on_readback_ms_per_step": round(host_wait_ms, 4)},
+        }
+        if graph_report is not None:
+            line["host"]["graph"] = graph_report
+            if graph_report["overflows"]:
+                line["host"]["graph"]["note"] = "overflowed steps were replayed inside the timed bracket"
+        return line
+
+    if not args.full:   # the headline alone
+        if world > 1:
+            tt = torch.tensor([elapsed], device=device, dtype=torch.float64)
+            dist.all_reduce(tt, op=dist.ReduceOp.MAX)
+            elapsed = float(tt.item())
+        if rank == 0:
+            print(json.dumps(headline_line(elapsed)), flush=True)
+        if world > 1 or force_dist:
+            dist.barrier()
+            dist.destroy_process_group()
+        return 0
+
     lazy_handback = None
     if graph_step is not None and graph_step.handback == "eager" and not args.no_extras and world == 1 and not force_dist:
         graph_step.handback = "lazy"   # (read per step: no re-build)
@@ -1156,45 +1260,16 @@ def run_rank(args) -> int:
                     "note": "class costs at 4 waves per SIMD (the kernel runs 3: plain fma measured 5.5 / 2.8 / 2.55 / 2.3 cycles at 1 / 2 / 4 / 8 "
                             "waves per SIMD -- a wave cannot issue VALU back to back, the guide's 2 cycles need >= 8 waves); a fraction above 1 "
                             "means hipcc's schedule hides part of the v_cmp -> v_cndmask dependency the micro-kernel exposes"}
-        result = {
-            "metric": "train iters/sec + forward render fps, 1M Gaussians @ 1080p",
-            "value": round(world * args.steps / elapsed, 3), "unit": "iters/s",
-            "n_gpus": world, "steps": args.steps, "warmup": args.warmup,
-            "ms_per_step": round(1e3 * elapsed / args.steps, 4),
-            "spin_up_ms": spin_ms,
-            "higher_is_better": True, "scaling": "weak", "vs_baseline": None,
-            "dtype": "f32", "data": "synthetic",
-            "step_ms": _percentiles(step_ms),
-            "forward_fps": round(args.steps / fwd_elapsed, 2),
-            "forward_ms": round(1e3 * fwd_elapsed / args.steps, 4),
-            "forward_step_ms": _percentiles(fwd_ms),
-            "config": {"workload": f"{args.gaussians} Gaussians, {W}x{H}, SH degree {sc['sh_degree']}, "
-                                   "1 view per GPU per step, full train step (fwd + L1/SSIM + bwd + stats + Adam)",
-                       "view_schedule": f"{n_views} views (camera + target image), a fresh seeded permutation per epoch "
-                                        "(DataLoader shuffle=True, /root/reference/train.py:36-43), a different view every "
-                                        "step, means-LR schedule updated every step (train.py:140); TrainStepGraph at its class defaults "
-                                        "(handback='eager', inputs_ready off)",
-                       "n_visible": n_vis, "n_isects": n_isects, "n_isects_gsplat_lists": n_isects_ref,
-                       "list_mode": "tight (model default; image, radii, means2d bitwise identical to the gsplat-list mode, gradients equal to rounding: "
-                                    "<= 1e-4 of the tensor's largest entry)",
-                       "parallelism": f"view-dp{world}", "exchange": exchange,
-                       "dist_backend": dist.get_backend() if (world > 1 or force_dist) else None,
-                       "dist_world_size": dist.get_world_size() if (world > 1 or force_dist) else 1,
-                       "step_launch": ("hipGraph replay" if (world == 1 and not force_dist) else "hipGraph replay up to the first collective + 4 launches") if graph_step is not None else "eager",
-                       "exchange_bytes_per_rank": None if (world == 1 and not force_dist) else (
-                           {"all_gather_view_record": 16 * args.gaussians + 64, "all_reduce_geometry_stats": 4 * 13 * args.gaussians,
-                            "collectives_per_step": 2} if vp is not None else
-                           {"all_reduce_grads": 4 * 59 * args.gaussians, "all_reduce_stats": 12 * args.gaussians})},
-            "stage_ms": {k: round(v, 4) for k, v in sorted(stage_ms.items())},
-            "blend_kernel_ms": {k: round(v, 4) for k, v in sorted(kernel_ms.items())},
-            # host diagnostics: ms/step the host spent enqueueing, and blocked on the list-size read-back (0 when
-            # the captured step is replayed: no read-back exists on that path)
-            "host": {"enqueue_ms_per_step": round(1e3 * t_enqueued / args.steps, 4),
-                     "blocked_on_readback_ms_per_step": round(host_wait_ms, 4)},
-            "roofline": roofline,
-            "roofline_compute": rc_obj,
-            "roofline_step": roofline_step,
-        }
+        result = headline_line(elapsed)
+        result.update({"forward_fps": round(args.steps / fwd_elapsed, 2),
+                       "forward_ms": round(1e3 * fwd_elapsed / args.steps, 4),
+                       "forward_step_ms": _percentiles(fwd_ms),
+                       "stage_ms": {k: round(v, 4) for k, v in sorted(stage_ms.items())},
+                       "blend_kernel_ms": {k: round(v, 4) for k, v in sorted(kernel_ms.items())},
+                       "roofline": roofline,
+                       "roofline_compute": rc_obj,
+                       "roofline_step": roofline_step})
+        result["config"].update(n_visible=n_vis, n_isects=n_isects, n_isects_gsplat_lists=n_isects_ref)
         if static_view is not None:
             result["static_view"] = static_view
         if lazy_handback is not None:
@@ -1203,10 +1278,6 @@ def run_rank(args) -> int:
             result["host_fed"] = host_fed
         if per_rank is not None:
             result["per_rank"] = per_rank
-        if graph_report is not None:
-            result["host"]["graph"] = graph_report
-            if graph_report["overflows"]:
-                result["host"]["graph"]["note"] = "overflowed steps were replayed inside the timed bracket"
         result.update(extras)
         if world == 1 and not args.no_cpu_baseline:
             result["cpu_baseline"] = cpu_baseline(sc, args.cpu_sample, args.cpu_reps)

@@ -6,6 +6,7 @@ import os
 import subprocess
 import sys
 
+import numpy as np
 import pytest
 
 pytestmark = pytest.mark.gpu
@@ -22,8 +23,28 @@ def _bench(args, env_extra=None, timeout=900):
     return lines[0]
 
 
+def test_bench_plain_line_and_dump_outputs(tmp_path):
+    """A plain run: the headline alone (no secondary figure), and --dump-outputs writes the last timed step's results."""
+    out = tmp_path / "outputs"
+    r = _bench(["--gpus", "1", "--steps", "5", "--warmup", "2", "--gaussians", "200000", "--dump-outputs", str(out)])
+    for k in ("metric", "value", "unit", "n_gpus", "steps", "warmup", "ms_per_step", "higher_is_better", "dtype", "step_ms", "config"):
+        assert k in r, k
+    assert r["steps"] == 5 and r["warmup"] == 2 and r["step_ms"]["n"] == 5 and r["unit"] == "iters/s" and r["dtype"] == "f32"
+    assert abs(r["value"] - 1e3 / r["ms_per_step"]) <= 1e-3 * r["value"]
+    for k in ("forward_fps", "stage_ms", "roofline", "cpu_baseline", "static_view", "real_loop", "summary"):
+        assert k not in r, k
+    files = {p.stem: np.load(p) for p in out.glob("*.npy")}
+    assert {"render_img", "loss3", "means", "quats", "log_scales", "logit_opacities", "sh_0", "sh_rest", "radii", "absgrad"} <= set(files)
+    assert sum(a.nbytes for a in files.values()) <= 64 << 20
+    for name, a in files.items():
+        assert a.dtype in (np.float32, np.float64) and np.isfinite(a).all(), name
+    assert files["render_img"].shape == (1080, 1920, 3) and files["loss3"].shape == (3,)
+    assert files["means"].shape == (65536, 3) and (files["radii"] > 0).any()
+
+
 def test_bench_line_contract_single_gpu():
-    r = _bench(["--gpus", "1", "--steps", "6", "--warmup", "3", "--gaussians", "200000", "--cpu-sample", "20000", "--cpu-reps", "1"])
+    r = _bench(["--gpus", "1", "--steps", "6", "--warmup", "3", "--gaussians", "200000", "--cpu-sample", "20000", "--cpu-reps", "1",
+                "--full"])
     for k in ("metric", "value", "unit", "n_gpus", "steps", "warmup", "ms_per_step", "higher_is_better", "scaling", "vs_baseline",
               "dtype", "data", "config", "roofline", "roofline_compute", "cpu_baseline", "step_ms"):
         assert k in r, k

@@ -7,6 +7,9 @@
 tag=${1:-r06}
 cd $GRAFT_REPO_ROOT
 mkdir -p gpurun_out
+root=$(cd "$(dirname "$0")/.." && pwd)
+out=${GS_PROF_OUT:-$(mktemp -d)}   # the bench lines of this script (bench.py --full) and their logs; set GS_PROF_OUT to keep them
+mkdir -p "$out"
 # the diagnostic variants, re-made on the box unless GS_SKIP_VARIANT_BUILD=1 (a variant older than the sources lacks the symbols newer
 # sources export, and the package refuses to bind such a library: the tools that load one would fail silently)
 if [ "$GS_SKIP_VARIANT_BUILD" != 1 ]; then
@@ -27,16 +30,16 @@ for part in ("fwd", "bwd"):
     json.dump({k: v for k, v in d.items() if f"blend_{part}" in k}, open(f"gpurun_out/{tag}_sq_blend_{part}.json", "w"), indent=1)
 PY
 timeout 300 bash tools/prof_bench.sh ${tag}_bench > gpurun_out/${tag}_prof_bench.log 2>&1
-timeout 600 python bench.py > gpurun_out/${tag}_bench_line.json 2> gpurun_out/${tag}_bench.err
+timeout 600 python bench.py --full > "$out/${tag}_bench_line.json" 2> "$out/${tag}_bench.err"
 for m in tight gsplat_eager; do
   timeout 200 bash tools/prof_cmd.sh ${tag}_longlists_$m tools/long_lists_run.py $m 10 > /dev/null 2>&1
   grep -v "amdgpu.ids\|^W2026\|^E2026" /tmp/${tag}_longlists_$m.log > gpurun_out/${tag}_longlists_$m.txt
 done
 GS_BINNING=bins timeout 300 bash tools/prof_pmc.sh ${tag}_longlists tools/long_lists_run.py tight 3 > /dev/null 2>&1
 timeout 300 bash tools/micro/traffic_cal.sh $tag > gpurun_out/${tag}_traffic_cal.log 2>&1
-(GS_BENCH_FORCE_DIST=1 timeout 300 python bench.py --steps 50 --warmup 10 > gpurun_out/${tag}_bench_forcedist_rccl.json 2> gpurun_out/${tag}_bench_forcedist.err)
+(GS_BENCH_FORCE_DIST=1 timeout 300 python bench.py --full --steps 50 --warmup 10 > "$out/${tag}_bench_forcedist_rccl.json" 2> "$out/${tag}_bench_forcedist.err")
 # ... and its kernel trace (row_sums_kernel, project_bwd_kernel<3, false, true>, sh_grad_views_kernel<3, true>, RCCL's own kernels)
-(cd /tmp && export TMPDIR=/tmp GS_BENCH_FORCE_DIST=1 && timeout 400 rocprofv3 --kernel-trace --stats --output-format csv -d /tmp/${tag}_fd -o fd -- python3 $GRAFT_REPO_ROOT/bench.py --steps 50 --warmup 10 > /tmp/${tag}_fd.log 2>&1; f=$(find /tmp/${tag}_fd -name "*kernel_stats.csv" | head -1); cp "$f" $GRAFT_REPO_ROOT/gpurun_out/${tag}_forcedist_kernel_stats.csv)
+(work=$(mktemp -d) && cd "$work" && export TMPDIR="$work" GS_BENCH_FORCE_DIST=1 && timeout 400 rocprofv3 --kernel-trace --stats --output-format csv -d "$work/fd" -o fd -- python3 "$root/bench.py" --full --steps 50 --warmup 10 > "$work/fd.log" 2>&1; f=$(find "$work/fd" -name "*kernel_stats.csv" | head -1); cp "$f" "$out/${tag}_forcedist_kernel_stats.csv")
 timeout 900 python tools/config_table.py > gpurun_out/${tag}_configs.md 2> gpurun_out/${tag}_configs.err
 timeout 200 python tools/binning_sweep.py 2>/dev/null > gpurun_out/${tag}_binning_sweep.txt
 timeout 200 python tools/blend_time.py 2>/dev/null > gpurun_out/${tag}_blend_time.txt
@@ -68,4 +71,4 @@ timeout 300 bash tools/prof_cmd.sh ${tag}_rounds_heavy2m tools/rounds_time.py he
 timeout 300 bash tools/prof_cmd.sh ${tag}_oneround_heavy2m tools/rounds_time.py heavy2M tight off,off 40 > /dev/null 2>&1
 # per-Gaussian criterion: fp32 sums / fp64 sums / fp64 sums + exact exp2 and division / fp32 oracle
 timeout 900 python tools/acc64_ab.py gpurun_out/${tag}_acc64_ab.json > gpurun_out/${tag}_acc64_ab.log 2>&1
-head -c 600 gpurun_out/${tag}_bench_line.json; echo; tail -3 gpurun_out/${tag}_bench.err
+echo "bench lines: $out"; head -c 600 "$out/${tag}_bench_line.json"; echo; tail -3 "$out/${tag}_bench.err"

@@ -3,7 +3,7 @@
 #   tools/prof_sq.sh <tag> [tool.py args...]  -> gpurun_out/<tag>_sq_counters.json  (per kernel: per-launch averages; default
 #   program: the bench; GS_SQ_EXTRA="C1 C2 C3 C4": one more counter set, GS_SQ_SHOW: substring of the kernels to print)
 tag=${1:-sq}; shift
-prog="bench.py --no-cpu-baseline --no-extras --no-graph --steps 3 --warmup 2"
+prog="bench.py --full --no-cpu-baseline --no-extras --no-graph --steps 3 --warmup 2"
 [ $# -gt 0 ] && prog="$*"
 cd /tmp && export TMPDIR=/tmp
 dirs=""

@@ -17,7 +17,7 @@ if [ "$mode" = build ]; then
 else
   for name in base "$@"; do
     lib=$root/build/variants/libgsraster_$name.so; [ $name = base ] && lib=$root/easy_gaussian_splatting_amd/libgsraster.so
-    GS_ALLOW_VARIANT=1 GS_LIB_PATH=$lib timeout 200 python $root/bench.py --no-cpu-baseline --no-extras --steps 100 --warmup 20 2>/dev/null | python3 -c "
+    GS_ALLOW_VARIANT=1 GS_LIB_PATH=$lib timeout 200 python $root/bench.py --full --no-cpu-baseline --no-extras --steps 100 --warmup 20 2>/dev/null | python3 -c "
 import json,sys
 d=json.loads(sys.stdin.readline()); print('$name', d['value'], d['step_ms']['median'], d['forward_fps'], {k[3:]:round(v,3) for k,v in d['stage_ms'].items()})"
   done
