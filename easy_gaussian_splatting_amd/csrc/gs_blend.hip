@@ -165,6 +165,20 @@ __device__ __forceinline__ void blend_pair(const float alpha, const bool ok, con
     cr = fmaf(r, w, cr); cg = fmaf(g, w, cg); cb = fmaf(b, w, cb);
     T = Tn;
 }
+// The same pair with a fourth colour channel (gs_blend_fwd_ch, channels = 4): channels 0..2 round exactly as above.
+__device__ __forceinline__ void blend_pair4(const float alpha, const bool ok, const float r, const float g, const float b,
+                                            const float c3, float& T, float& cr, float& cg, float& cb, float& ca) {
+    const float am = ok ? alpha : 0.f;
+    float w = am * T;
+    float Tn = fmaf(-am, T, T);
+    const bool stop = Tn <= kTMin;
+    if (__builtin_expect(__builtin_amdgcn_ballot_w64(stop) != 0ull, 0)) {
+        w = stop ? 0.f : w;
+        Tn = stop ? T * kDoneScale : Tn;
+    }
+    cr = fmaf(r, w, cr); cg = fmaf(g, w, cg); cb = fmaf(b, w, cb); ca = fmaf(c3, w, ca);
+    T = Tn;
+}
 
 // The training instantiation is held to 5 waves / SIMD (the 8160 tile-waves of a 1080p frame then run in 1.6 rounds); held
 // to 80 VGPRs (5 spilled to scratch) it keeps 6 resident and is 2-3 % faster back to back -- but a kernel
@@ -213,8 +227,12 @@ __global__ __launch_bounds__(256) void qmask_clear_kernel(uint8_t* __restrict__ 
 // ROUND (depth rounds, include/gs_raster.h): 0 = the frame's one list per tile; 1 = front round: a tile that still has live pixels
 // behind its list leaves them (and, training, where its quadrant sublists stand) for the back round; 2 = back round: only such
 // tiles, from those states -- the same walk as over one list, cut in two.
-template <bool CKPT, int WAVES, int ROUND>
-__global__ __launch_bounds__(64 * WAVES) GS_FWD_ATTR void blend_fwd_kernel(const BlendFwdArgs a) {
+// NC: colour channels (gs_blend_fwd_ch).  The record's colour quad holds channels 0..3 (zero above NC); NC <= 3 blends the three
+// record channels like the RGB kernel and stores NC of them; NC = 4 adds a fourth accumulator, whose checkpoint plane is
+// ckpt_ext[cap_units][64].  Depth rounds are RGB only (tile_state holds (T, r, g, b)).
+template <bool CKPT, int WAVES, int ROUND, int NC>
+__device__ __forceinline__ void blend_fwd_body(const BlendFwdArgs& a, float* __restrict__ ckpt_ext) {
+    static_assert(NC >= 1 && NC <= 4 && (NC == 3 || ROUND == 0), "channels 1..4; depth rounds with 3 channels only");
     __shared__ float4 srec_all[WAVES][GS_BUCKET * 3];
     __shared__ int2 ulog_all[CKPT ? WAVES : 1][CKPT ? kUnitLog : 1];
     float4* srec = srec_all[threadIdx.x >> 6];
@@ -239,6 +257,7 @@ __global__ __launch_bounds__(64 * WAVES) GS_FWD_ATTR void blend_fwd_kernel(const
     if (ROUND == 2 && (len == 0 || a.live[t] == 0)) return;   // wave-uniform
 
     float T[4], cr[4], cg[4], cb[4];   // T <= 1: live; T > 2^32: finished, T * 2^-64 final (blend_pair)
+    float ca[4];                       // (NC = 4: the fourth channel)
     int cnt[4] = {0, 0, 0, 0};   // wave-uniform sublist lengths
     // storage of the work units a bucket's sublist entries can fall into (wave-uniform): [k][0] the unit that holds position
     // cnt[k] at the start of the bucket (carried over when it is part-filled), [k][1..2] the units opened behind it
@@ -252,6 +271,7 @@ __global__ __launch_bounds__(64 * WAVES) GS_FWD_ATTR void blend_fwd_kernel(const
 #pragma unroll
     for (int k = 0; k < 4; ++k) {
         cr[k] = cg[k] = cb[k] = 0.f;
+        ca[k] = 0.f;
         T[k] = ((px0 + 8 * (k & 1)) < a.W && (py0 + 8 * (k >> 1)) < a.H) ? 1.f : kDoneScale;
     }
     if (ROUND == 2) {   // the states the front round left, in its lanes' own layout
@@ -378,6 +398,7 @@ __global__ __launch_bounds__(64 * WAVES) GS_FWD_ATTR void blend_fwd_kernel(const
                             const int su = pool_next++;
                             --pool_left;
                             a.ckpt[(size_t)su * 64 + lane] = make_float4(px_live(T[k]) ? T[k] : -1.f, cr[k], cg[k], cb[k]);   // (the backward's "finished" is T < 0)
+                            if constexpr (NC == 4) ckpt_ext[(size_t)su * 64 + lane] = ca[k];
                             if (lane == 0) ulog[log_n] = make_int2(su, (pos / kUnit) * 4 + k);
                             ++log_n;
                             const int w = pos / kUnit - cnt[k] / kUnit;
@@ -386,7 +407,8 @@ __global__ __launch_bounds__(64 * WAVES) GS_FWD_ATTR void blend_fwd_kernel(const
                         cq[k] |= 1ull << j;
                     }
                     GS_IF_CHECK(const float T_before = T[k];)
-                    blend_pair(alpha, ok, r, g, bl, T[k], cr[k], cg[k], cb[k]);
+                    if constexpr (NC == 4) blend_pair4(alpha, ok, r, g, bl, q2.w, T[k], cr[k], cg[k], cb[k], ca[k]);
+                    else blend_pair(alpha, ok, r, g, bl, T[k], cr[k], cg[k], cb[k]);
                     GS_IF_CHECK(taken[k] += T[k] < T_before ? 1 : 0;)   // (blended: T shrinks and stays live; stop rule: T jumps beyond 2^32; not taken: unchanged)
                 }
             }
@@ -436,21 +458,38 @@ __global__ __launch_bounds__(64 * WAVES) GS_FWD_ATTR void blend_fwd_kernel(const
             }
         }
     }
-    float bgr = 0.f, bgg = 0.f, bgb = 0.f;
-    if (a.bg) { bgr = a.bg[3 * cam]; bgg = a.bg[3 * cam + 1]; bgb = a.bg[3 * cam + 2]; }
+    float bgr = 0.f, bgg = 0.f, bgb = 0.f, bga = 0.f;
+    if (a.bg) {
+        bgr = a.bg[NC * cam];
+        if (NC > 1) bgg = a.bg[NC * cam + 1];
+        if (NC > 2) bgb = a.bg[NC * cam + 2];
+        if (NC > 3) bga = a.bg[NC * cam + 3];
+    }
 #pragma unroll
     for (int k = 0; k < 4; ++k) {
         const int px = px0 + 8 * (k & 1), py = py0 + 8 * (k >> 1);
         if (px < a.W && py < a.H) {
             const size_t o = ((size_t)cam * a.H + py) * a.W + px;
             const float Tf = px_final_T(T[k]);
-            a.out_colors[3 * o] = cr[k] + Tf * bgr;
-            a.out_colors[3 * o + 1] = cg[k] + Tf * bgg;
-            a.out_colors[3 * o + 2] = cb[k] + Tf * bgb;
+            a.out_colors[NC * o] = cr[k] + Tf * bgr;
+            if (NC > 1) a.out_colors[NC * o + 1] = cg[k] + Tf * bgg;
+            if (NC > 2) a.out_colors[NC * o + 2] = cb[k] + Tf * bgb;
+            if (NC > 3) a.out_colors[NC * o + 3] = ca[k] + Tf * bga;
             a.out_alphas[o] = 1.f - Tf;
             GS_IF_CHECK(if (CKPT && a.chk.fwd_T) { a.chk.fwd_T[o] = Tf; a.chk.fwd_cnt[o] = taken[k]; })
         }
     }
+}
+
+template <bool CKPT, int WAVES, int ROUND>
+__global__ __launch_bounds__(64 * WAVES) GS_FWD_ATTR void blend_fwd_kernel(const BlendFwdArgs a) {
+    blend_fwd_body<CKPT, WAVES, ROUND, 3>(a, nullptr);
+}
+// channels != 3 (gs_blend_fwd_ch; one list per tile).  The four-channel training form needs more than the 102 VGPRs of five waves
+// per SIMD: it is held to four (no scratch, see above).
+template <bool CKPT, int WAVES, int NC>
+__global__ __launch_bounds__(64 * WAVES) __attribute__((amdgpu_waves_per_eu(CKPT ? (NC == 4 ? 4 : 5) : 1, 8))) void chan_fwd_kernel(const BlendFwdArgs a, float* ckpt_ext) {
+    blend_fwd_body<CKPT, WAVES, 0, NC>(a, ckpt_ext);
 }
 
 // ------------------------------------------------------------------------------------------------
@@ -614,6 +653,7 @@ struct EntryState {
     float mx, my, hA, Bc, hC, op, colr, colg, colb, At, Bt, Ct;
     acc_t s_mx, s_my, s_ax, s_ay, s_A, s_B, s_C, s_vs, s_r, s_g, s_b;
     bool has;
+    float col3; acc_t s_3;   // (NC = 4 only: the fourth channel)
 };
 
 // Round 5 tried the forward's own state encoding here (T alone: 0 = finished; alpha masked once; the stop rule behind a
@@ -622,7 +662,9 @@ struct EntryState {
 // than eleven selects cost them, and four instructions fewer are within the noise.  Not kept.
 // (pixels outside the pipeline window arrive with T < 0; slots past the end of the sublist have
 // opacity 0, hence alpha 0: neither needs a flag of its own)
-__device__ __forceinline__ void bwd_pair(EntryState& e, const float4 d0, const float2 d1, float& T, float& P) {
+// NC = 4: v3 = the pixel's upstream gradient of the fourth channel (its E term already holds that channel's share)
+template <int NC>
+__device__ __forceinline__ void bwd_pair(EntryState& e, const float4 d0, const float v3, const float2 d1, float& T, float& P) {
     const float dx = e.mx - d1.x, dy = e.my - d1.y;
     const float sigma = fmaf(dy, fmaf(e.hC, dy, e.Bc * dx), e.hA * dx * dx);   // same op sequence as the forward
     const float vis = fast_exp2(-sigma);
@@ -633,12 +675,14 @@ __device__ __forceinline__ void bwd_pair(EntryState& e, const float4 d0, const f
     const float Tn = fmaf(-alpha, T, T);   // identical to the forward's update
     const bool stop = ok && Tn <= kTMin;
     const bool contrib = ok && !stop;
-    const float cv = e.colr * d0.x + e.colg * d0.y + e.colb * d0.z;
+    float cv = e.colr * d0.x + e.colg * d0.y + e.colb * d0.z;
+    if constexpr (NC == 4) cv = fmaf(e.col3, v3, cv);
     const float wm = contrib ? w : 0.f;
     const float Pn = fmaf(wm, cv, P);   // == P exactly when the entry does not contribute: no select for P below
     const float ra = fast_rcp(1.f - alpha);
     const float v_alpha = fmaf(T, cv, ra * (d0.w + Pn));
     e.s_r = GS_ACC_FMA(wm, d0.x, e.s_r); e.s_g = GS_ACC_FMA(wm, d0.y, e.s_g); e.s_b = GS_ACC_FMA(wm, d0.z, e.s_b);
+    if constexpr (NC == 4) e.s_3 = GS_ACC_FMA(wm, v3, e.s_3);
     const float vs = (contrib && ov <= kAlphaMax) ? -ov * v_alpha : 0.f;   // d loss / d sigma
     const float hx = vs * dx, hy = vs * dy;
     e.s_A = GS_ACC_FMA(hx, dx, e.s_A); e.s_B = GS_ACC_FMA(hx, dy, e.s_B); e.s_C = GS_ACC_FMA(hy, dy, e.s_C);
@@ -653,8 +697,12 @@ __device__ __forceinline__ void bwd_pair(EntryState& e, const float4 d0, const f
 // entries -- full units and tails (the last, part-filled unit of a quadrant sublist) of 25-32 entries are class 4, tails of 1-8 /
 // 9-16 / 17-24 entries classes 1 / 2 / 3 -- and the systolic loop passes over 8 E entry slots per unit instead of all 32 (the
 // bench workload: 9 % of the slots of its 169 k units are empty, heavy-tailed footprints 16 %; tools/tail_stats.py).
-template <int E>
-__device__ __forceinline__ void bwd_wave(const BlendBwdArgs& a, const int4 ud, const bool valid, const int unit, float4* sd0, float2* sck, const int r) {
+// NC: colour channels of v_colors / out_colors (gs_blend_bwd_ch).  Channels the record does not have are zero in sd0 and in the
+// record, so NC <= 3 runs the RGB arithmetic; NC = 4 stages the fourth channel's upstream gradient in sd1 and reads the fourth
+// channel's checkpoint plane ckpt_ext.
+template <int E, int NC>
+__device__ __forceinline__ void bwd_wave(const BlendBwdArgs& a, const int4 ud, const bool valid, const int unit, float4* sd0, float* sd1,
+                                         float2* sck, const int r, const float* __restrict__ ckpt_ext) {
     const int tq = ud.x, su = ud.z;
     const bool first_unit = ud.y == 0;   // the sublist starts here: every pixel inside the image has T = 1, no colour yet
     const int t = tq >> 2, q = tq & 3;
@@ -690,6 +738,7 @@ __device__ __forceinline__ void bwd_wave(const BlendBwdArgs& a, const int4 ud, c
     }
     constexpr int kPix = kUnitPixels / kPipeLanes;
     float l_vr[kPix], l_vg[kPix], l_vb[kPix], l_oa[kPix], l_cr[kPix], l_cg[kPix], l_cb[kPix], l_va[kPix];
+    float l_v3[kPix], l_c3[kPix], l_k3[kPix];   // (NC = 4)
     float4 l_ck[kPix];
     const float* vap = a.v_alphas ? a.v_alphas : a.out_alphas;   // (one load either way; masked below)
 #pragma unroll
@@ -697,11 +746,16 @@ __device__ __forceinline__ void bwd_wave(const BlendBwdArgs& a, const int4 ud, c
         const int p = r + kPipeLanes * i;
         const int px = min(qx0 + (p & 7), a.W - 1), py = min(qy0 + (p >> 3), a.H - 1);
         const size_t o = ((size_t)cam * a.H + py) * a.W + px;
-        l_vr[i] = a.v_colors[3 * o]; l_vg[i] = a.v_colors[3 * o + 1]; l_vb[i] = a.v_colors[3 * o + 2];
+        l_vr[i] = a.v_colors[NC * o];
+        l_vg[i] = NC > 1 ? a.v_colors[NC * o + 1] : 0.f;
+        l_vb[i] = NC > 2 ? a.v_colors[NC * o + 2] : 0.f;
         l_oa[i] = a.out_alphas[o];
-        l_cr[i] = a.out_colors[3 * o]; l_cg[i] = a.out_colors[3 * o + 1]; l_cb[i] = a.out_colors[3 * o + 2];
+        l_cr[i] = a.out_colors[NC * o];
+        l_cg[i] = NC > 1 ? a.out_colors[NC * o + 1] : 0.f;
+        l_cb[i] = NC > 2 ? a.out_colors[NC * o + 2] : 0.f;
         l_va[i] = vap[o];
         l_ck[i] = ckp[p];
+        if constexpr (NC == 4) { l_v3[i] = a.v_colors[NC * o + 3]; l_c3[i] = a.out_colors[NC * o + 3]; l_k3[i] = ckpt_ext[(size_t)su * 64 + p]; }
     }
     // batch 2: the entries' packed records (addresses from batch 1), in flight while the pixels are staged
     const int n_in = min(kPipeLanes * E, n_sub - ud.y * kUnit);   // entries of the sublist that fall into this unit (a unit of class E: <= 8 E)
@@ -720,12 +774,19 @@ __device__ __forceinline__ void bwd_wave(const BlendBwdArgs& a, const int4 ud, c
         const float Tf = 1.f - l_oa[i];
         const float va = a.v_alphas ? l_va[i] : 0.f;
         // E = T_final * v_alpha - render_colour . v_colour  (background terms cancel)
-        const float Ev = Tf * va - (l_cr[i] * vr + l_cg[i] * vg + l_cb[i] * vb);
+        float Ev = Tf * va - (l_cr[i] * vr + l_cg[i] * vg + l_cb[i] * vb);
         // the unit's checkpoint: the pixel's state in front of its first entry (T < 0: finished or outside the image); the
         // first unit of a sublist starts from T = 1, nothing accumulated
         const float4 ck = first_unit ? make_float4(1.f, 0.f, 0.f, 0.f) : l_ck[i];
+        float Pk = ck.y * vr + ck.z * vg + ck.w * vb;
+        if constexpr (NC == 4) {
+            const float v3 = l_v3[i];
+            Ev = Tf * va - fmaf(l_c3[i], v3, l_cr[i] * vr + l_cg[i] * vg + l_cb[i] * vb);
+            Pk = fmaf(first_unit ? 0.f : l_k3[i], v3, Pk);
+            sd1[p] = inside ? v3 : 0.f;
+        }
         sd0[p] = inside ? make_float4(vr, vg, vb, Ev) : make_float4(0.f, 0.f, 0.f, 0.f);
-        sck[p] = inside ? make_float2(ck.x, ck.y * vr + ck.z * vg + ck.w * vb) : make_float2(-1.f, 0.f);
+        sck[p] = inside ? make_float2(ck.x, Pk) : make_float2(-1.f, 0.f);
     }
 
     EntryState e[E];
@@ -739,6 +800,7 @@ __device__ __forceinline__ void bwd_wave(const BlendBwdArgs& a, const int4 ud, c
         const float4 q0 = e[i].has ? rq[i][0] : z4, q1 = e[i].has ? rq[i][1] : z4, q2 = e[i].has ? rq[i][2] : z4;
         e[i].mx = q0.x; e[i].my = q0.y; e[i].hA = q0.z; e[i].Bc = q0.w; e[i].hC = q1.x; e[i].op = q1.y;
         e[i].colr = q2.x; e[i].colg = q2.y; e[i].colb = q2.z;
+        e[i].col3 = q2.w; e[i].s_3 = (acc_t)0;
         // true conic entries for the mean gradient (the record stores them scaled by log2(e))
         e[i].At = 2.f * kLn2 * q0.z; e[i].Bt = kLn2 * q0.w; e[i].Ct = 2.f * kLn2 * q1.x;
         e[i].s_mx = e[i].s_my = e[i].s_ax = e[i].s_ay = e[i].s_A = e[i].s_B = e[i].s_C = e[i].s_vs = (acc_t)0;
@@ -755,6 +817,7 @@ __device__ __forceinline__ void bwd_wave(const BlendBwdArgs& a, const int4 ud, c
         const bool act = (unsigned)p < (unsigned)kUnitPixels;
         const int pc = min(max(p, 0), kUnitPixels - 1);
         const float4 d0 = sd0[pc];
+        const float v3 = NC == 4 ? sd1[pc] : 0.f;
         const float2 ck = sck[pc];
         const float2 d1 = make_float2(fx0 + (float)(pc & 7), fy0 + (float)(pc >> 3));   // pixel centre
         if (r == 0) { T = ck.x; P = ck.y; }   // head of the pipeline: fed from the checkpoint, not from the lane below
@@ -763,7 +826,7 @@ __device__ __forceinline__ void bwd_wave(const BlendBwdArgs& a, const int4 ud, c
 #pragma unroll
         for (int i = 0; i < E; ++i) {
             GS_IF_CHECK(const float T_before = T;)
-            bwd_pair(e[i], d0, d1, T, P);
+            bwd_pair<NC>(e[i], d0, v3, d1, T, P);
             GS_IF_CHECK(if (T > 0.f && T < T_before) { D = T; Cn += 1.f; })   // (contributed; the stop rule leaves T = -1 and D at the final value)
         }
         GS_IF_CHECK(D_out = D; C_out = Cn;
@@ -789,7 +852,7 @@ __device__ __forceinline__ void bwd_wave(const BlendBwdArgs& a, const int4 ud, c
             const float v_op = e[i].op > 0.f ? (float)(-e[i].s_vs / (acc_t)e[i].op) : 0.f;
             rp[0] = make_float4((float)e[i].s_mx, (float)e[i].s_my, (float)e[i].s_ax, (float)e[i].s_ay);
             rp[1] = make_float4((float)((acc_t)0.5f * e[i].s_A), (float)e[i].s_B, (float)((acc_t)0.5f * e[i].s_C), v_op);
-            rp[2] = make_float4((float)e[i].s_r, (float)e[i].s_g, (float)e[i].s_b, 0.f);
+            rp[2] = make_float4((float)e[i].s_r, (float)e[i].s_g, (float)e[i].s_b, NC == 4 ? (float)e[i].s_3 : 0.f);
         }
     }
 }
@@ -839,7 +902,8 @@ __global__ __launch_bounds__(kClsThreads) void unit_classes_kernel(const int32_t
     }
 }
 
-__global__ __launch_bounds__(kBwdWaves * 64) void blend_bwd_kernel(const BlendBwdArgs a) {
+template <int NC>
+__device__ __forceinline__ void blend_bwd_body(const BlendBwdArgs& a, const float* __restrict__ ckpt_ext) {
     __shared__ float4 sd0_all[kBwdWaves][kUnitsPerWave][64];   // 8 KB per wave: v_r, v_g, v_b, E of the unit's 64 pixels
     __shared__ float2 sck_all[kBwdWaves][kUnitsPerWave][64];   // 4 KB per wave: checkpoint T, P = checkpoint colour . v
     const int wave = threadIdx.x >> 6, lane = threadIdx.x & 63;
@@ -864,14 +928,28 @@ __global__ __launch_bounds__(kBwdWaves * 64) void blend_bwd_kernel(const BlendBw
     const bool valid = in_class < n_units;
     float4* sd0 = sd0_all[wave][pipe];
     float2* sck = sck_all[wave][pipe];
+    float* sd1 = nullptr;
+    if constexpr (NC == 4) {
+        __shared__ float sd1_all[kBwdWaves][kUnitsPerWave][64];   // 2 KB per wave: the fourth channel's v
+        sd1 = sd1_all[wave][pipe];
+    }
 
     int4 ud = make_int4(0, 0, 0, 0);
     if (valid) ud = a.cls_hdr ? a.cls_desc[first + in_class] : a.unit_desc[in_class];
     const int unit = a.cls_hdr ? ud.w : in_class;   // the unit's published index (the check build's arrays are indexed by it)
-    if (cls == 4) bwd_wave<4>(a, ud, valid, unit, sd0, sck, r);
-    else if (cls == 3) bwd_wave<3>(a, ud, valid, unit, sd0, sck, r);
-    else if (cls == 2) bwd_wave<2>(a, ud, valid, unit, sd0, sck, r);
-    else bwd_wave<1>(a, ud, valid, unit, sd0, sck, r);
+    if (cls == 4) bwd_wave<4, NC>(a, ud, valid, unit, sd0, sd1, sck, r, ckpt_ext);
+    else if (cls == 3) bwd_wave<3, NC>(a, ud, valid, unit, sd0, sd1, sck, r, ckpt_ext);
+    else if (cls == 2) bwd_wave<2, NC>(a, ud, valid, unit, sd0, sd1, sck, r, ckpt_ext);
+    else bwd_wave<1, NC>(a, ud, valid, unit, sd0, sd1, sck, r, ckpt_ext);
+}
+
+__global__ __launch_bounds__(kBwdWaves * 64) void blend_bwd_kernel(const BlendBwdArgs a) {
+    blend_bwd_body<3>(a, nullptr);
+}
+// channels != 3 (gs_blend_bwd_ch)
+template <int NC>
+__global__ __launch_bounds__(kBwdWaves * 64) void chan_bwd_kernel(const BlendBwdArgs a, const float* ckpt_ext) {
+    blend_bwd_body<NC>(a, ckpt_ext);
 }
 
 }  // namespace gs
@@ -900,11 +978,13 @@ extern "C" size_t gs_walk_state_ints(int64_t n_isects) {
     return (size_t)GS_WALK_WORDS + (size_t)(n_isects / kScanChunk + 1);
 }
 
-extern "C" int gs_blend_fwd(void* stream, int C, int width, int height, const float* rec,
+template <int NC>
+static int blend_fwd_launch(void* stream, int C, int width, int height, const float* rec,
                             const float* backgrounds, const int32_t* isect_offsets, const int32_t* tile_order,
                             const int32_t* flatten_ids, const int32_t* slots, int64_t n_isects, float* render_colors,
                             float* render_alphas, float* ckpt, int32_t* qlist, int32_t* qcnt, uint8_t* qmask,
-                            int32_t* unit_desc, int64_t cap_units, int32_t* row_base, int64_t cap_rows, int32_t* walk_state) {
+                            int32_t* unit_desc, int64_t cap_units, int32_t* row_base, int64_t cap_rows, int32_t* walk_state,
+                            float* ckpt_ext) {
     GS_REQUIRE(C >= 1 && width > 0 && height > 0 && n_isects >= 0, "C>=1, positive image size, n_isects>=0");
     GS_REQUIRE(isect_offsets && render_colors && render_alphas, "null pointer");
     const bool train = ckpt != nullptr;
@@ -933,6 +1013,8 @@ extern "C" int gs_blend_fwd(void* stream, int C, int width, int height, const fl
     GS_REQUIRE(R.phase != 4 || a.flags != nullptr, "depth rounds, front round alone: needs a step guard (gs_guard_set)");
     GS_REQUIRE(phase == 0 || C == 1, "depth rounds: one camera per call");
     GS_REQUIRE(phase == 0 || !train || R.tile_rec, "depth rounds, training mode: gs_rounds_set needs tile_rec");
+    GS_REQUIRE(NC == 3 || phase == 0, "depth rounds render 3 channels only (tile_state holds T, r, g, b): clear gs_rounds_set");
+    GS_REQUIRE(NC != 4 || !train || ckpt_ext, "channels = 4, training mode: ckpt_ext (cap_units * 64 floats) is required");
     a.rblk = R.blk; a.live = R.live; a.tstate = R.state; a.trec = reinterpret_cast<int4*>(R.tile_rec);
     GS_IF_CHECK(a.chk = g_bwd_check;)
     const unsigned n_tiles = (unsigned)(C * a.tiles);
@@ -950,7 +1032,8 @@ extern "C" int gs_blend_fwd(void* stream, int C, int width, int height, const fl
         hipLaunchKernelGGL(qmask_clear_kernel, dim3(cg), dim3(256), 0, st, qmask, n_isects, walk_state, walk_ints, a.guard,
                            (const int64_t*)R.blk, phase);
         GS_LAUNCH_CHECK("qmask_clear_kernel");
-        if (phase == 1) hipLaunchKernelGGL((blend_fwd_kernel<true, kFwdWaves, 1>), grid, block, 0, st, a);
+        if constexpr (NC != 3) hipLaunchKernelGGL((chan_fwd_kernel<true, kFwdWaves, NC>), grid, block, 0, st, a, ckpt_ext);
+        else if (phase == 1) hipLaunchKernelGGL((blend_fwd_kernel<true, kFwdWaves, 1>), grid, block, 0, st, a);
         else if (phase == 2) hipLaunchKernelGGL((blend_fwd_kernel<true, kFwdWaves, 2>), grid, block, 0, st, a);
         else hipLaunchKernelGGL((blend_fwd_kernel<true, kFwdWaves, 0>), grid, block, 0, st, a);
         GS_LAUNCH_CHECK("blend_fwd_kernel");
@@ -964,12 +1047,42 @@ extern "C" int gs_blend_fwd(void* stream, int C, int width, int height, const fl
         hipLaunchKernelGGL(row_base_kernel, dim3(chunks), dim3(kScanThreads), 0, st, s);
         GS_LAUNCH_CHECK("row_base_kernel");
     } else {
-        if (phase == 1) hipLaunchKernelGGL((blend_fwd_kernel<false, kFwdWaves, 1>), grid, block, 0, st, a);
+        if constexpr (NC != 3) hipLaunchKernelGGL((chan_fwd_kernel<false, kFwdWaves, NC>), grid, block, 0, st, a, nullptr);
+        else if (phase == 1) hipLaunchKernelGGL((blend_fwd_kernel<false, kFwdWaves, 1>), grid, block, 0, st, a);
         else if (phase == 2) hipLaunchKernelGGL((blend_fwd_kernel<false, kFwdWaves, 2>), grid, block, 0, st, a);
         else hipLaunchKernelGGL((blend_fwd_kernel<false, kFwdWaves, 0>), grid, block, 0, st, a);
         GS_LAUNCH_CHECK("blend_fwd_kernel");
     }
     return GS_OK;
+}
+
+extern "C" int gs_blend_fwd(void* stream, int C, int width, int height, const float* rec,
+                            const float* backgrounds, const int32_t* isect_offsets, const int32_t* tile_order,
+                            const int32_t* flatten_ids, const int32_t* slots, int64_t n_isects, float* render_colors,
+                            float* render_alphas, float* ckpt, int32_t* qlist, int32_t* qcnt, uint8_t* qmask,
+                            int32_t* unit_desc, int64_t cap_units, int32_t* row_base, int64_t cap_rows, int32_t* walk_state) {
+    return blend_fwd_launch<3>(stream, C, width, height, rec, backgrounds, isect_offsets, tile_order, flatten_ids, slots, n_isects,
+                               render_colors, render_alphas, ckpt, qlist, qcnt, qmask, unit_desc, cap_units, row_base, cap_rows,
+                               walk_state, nullptr);
+}
+
+extern "C" int gs_blend_fwd_ch(void* stream, int C, int width, int height, int channels, const float* rec,
+                               const float* backgrounds, const int32_t* isect_offsets, const int32_t* tile_order,
+                               const int32_t* flatten_ids, const int32_t* slots, int64_t n_isects, float* render_colors,
+                               float* render_alphas, float* ckpt, int32_t* qlist, int32_t* qcnt, uint8_t* qmask,
+                               int32_t* unit_desc, int64_t cap_units, int32_t* row_base, int64_t cap_rows, int32_t* walk_state,
+                               float* ckpt_ext) {
+    GS_REQUIRE(channels >= 1 && channels <= 4, "channels must be 1, 2, 3 or 4");
+#define GS_FWD_CH(NC) blend_fwd_launch<NC>(stream, C, width, height, rec, backgrounds, isect_offsets, tile_order, flatten_ids, slots, \
+                                           n_isects, render_colors, render_alphas, ckpt, qlist, qcnt, qmask, unit_desc, cap_units,   \
+                                           row_base, cap_rows, walk_state, ckpt_ext)
+    switch (channels) {
+        case 1: return GS_FWD_CH(1);
+        case 2: return GS_FWD_CH(2);
+        case 3: return GS_FWD_CH(3);
+        default: return GS_FWD_CH(4);
+    }
+#undef GS_FWD_CH
 }
 
 // descriptors a tail region holds: one tail per quadrant sublist at most, rounded up to whole blocks of the backward
@@ -984,15 +1097,17 @@ extern "C" size_t gs_unit_classes_ints(int64_t cap_units, int C, int width, int 
     return (size_t)kClsHdrInts + 4 * ((size_t)cap_units + 3 * (size_t)cls_region(C, width, height));
 }
 
-extern "C" int gs_blend_bwd(void* stream, int C, int width, int height, const float* rec,
+template <int NC>
+static int blend_bwd_launch(void* stream, int C, int width, int height, const float* rec,
                             const int32_t* qlist, const int32_t* qcnt, const int32_t* unit_desc, int64_t cap_units,
                             const float* ckpt, const uint8_t* qmask, const int32_t* row_base, const int32_t* walk_state,
                             const float* render_colors, const float* render_alphas, const float* v_render_colors,
-                            const float* v_render_alphas, float* rows, int32_t* unit_classes) {
+                            const float* v_render_alphas, float* rows, int32_t* unit_classes, const float* ckpt_ext) {
     GS_REQUIRE(C >= 1 && width > 0 && height > 0 && cap_units >= 0 && cap_units < (1ll << 26), "C>=1, positive image size, 0 <= cap_units < 2^26");
     if (cap_units == 0) return GS_OK;
     GS_REQUIRE(rec && qlist && qcnt && unit_desc && ckpt && qmask && row_base && walk_state, "null list pointer");
     GS_REQUIRE(render_colors && render_alphas && v_render_colors && rows, "null image pointer");
+    GS_REQUIRE(NC != 4 || ckpt_ext, "channels = 4: ckpt_ext (gs_blend_fwd_ch's fourth-channel checkpoints) is required");
     BlendBwdArgs a;
     a.C = C; a.W = width; a.H = height;
     a.tw = (width + GS_TILE - 1) / GS_TILE;
@@ -1023,7 +1138,35 @@ extern "C" int gs_blend_bwd(void* stream, int C, int width, int height, const fl
         GS_LAUNCH_CHECK("unit_classes_kernel");
         grid += 3u * (unsigned)(a.cls_cap / (kUnitsPerWave * kBwdWaves));
     }
-    hipLaunchKernelGGL(blend_bwd_kernel, dim3(grid), dim3(kBwdWaves * 64), 0, (hipStream_t)stream, a);
+    if constexpr (NC == 3) hipLaunchKernelGGL(blend_bwd_kernel, dim3(grid), dim3(kBwdWaves * 64), 0, (hipStream_t)stream, a);
+    else hipLaunchKernelGGL((chan_bwd_kernel<NC>), dim3(grid), dim3(kBwdWaves * 64), 0, (hipStream_t)stream, a, ckpt_ext);
     GS_LAUNCH_CHECK("blend_bwd_kernel");
     return GS_OK;
+}
+
+extern "C" int gs_blend_bwd(void* stream, int C, int width, int height, const float* rec,
+                            const int32_t* qlist, const int32_t* qcnt, const int32_t* unit_desc, int64_t cap_units,
+                            const float* ckpt, const uint8_t* qmask, const int32_t* row_base, const int32_t* walk_state,
+                            const float* render_colors, const float* render_alphas, const float* v_render_colors,
+                            const float* v_render_alphas, float* rows, int32_t* unit_classes) {
+    return blend_bwd_launch<3>(stream, C, width, height, rec, qlist, qcnt, unit_desc, cap_units, ckpt, qmask, row_base, walk_state,
+                               render_colors, render_alphas, v_render_colors, v_render_alphas, rows, unit_classes, nullptr);
+}
+
+extern "C" int gs_blend_bwd_ch(void* stream, int C, int width, int height, int channels, const float* rec,
+                               const int32_t* qlist, const int32_t* qcnt, const int32_t* unit_desc, int64_t cap_units,
+                               const float* ckpt, const uint8_t* qmask, const int32_t* row_base, const int32_t* walk_state,
+                               const float* render_colors, const float* render_alphas, const float* v_render_colors,
+                               const float* v_render_alphas, float* rows, int32_t* unit_classes, const float* ckpt_ext) {
+    GS_REQUIRE(channels >= 1 && channels <= 4, "channels must be 1, 2, 3 or 4");
+#define GS_BWD_CH(NC) blend_bwd_launch<NC>(stream, C, width, height, rec, qlist, qcnt, unit_desc, cap_units, ckpt, qmask, row_base, \
+                                           walk_state, render_colors, render_alphas, v_render_colors, v_render_alphas, rows,         \
+                                           unit_classes, ckpt_ext)
+    switch (channels) {
+        case 1: return GS_BWD_CH(1);
+        case 2: return GS_BWD_CH(2);
+        case 3: return GS_BWD_CH(3);
+        default: return GS_BWD_CH(4);
+    }
+#undef GS_BWD_CH
 }

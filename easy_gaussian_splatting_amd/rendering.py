@@ -506,13 +506,16 @@ def _forward_stages(means, quats, scales, opacities, colors, colors_rest, viewma
     else:
         deg, per_cam = int(sh_degree), 0
         K = colors.shape[1] + (0 if colors_rest is None else colors_rest.shape[1])
+    # colour channels: 3 (SH colours, and RGB features) is the RGB path as it stands; 1, 2 or 4 feature channels go through the
+    # channel entry points (gs_rec_colors, gs_blend_fwd_ch / gs_blend_bwd_ch, gs_channel_grads), always in one depth round
+    ch = 3 if sh_degree is not None else int(colors.shape[-1])
 
     # what escapes to the caller through `meta` is allocated per call; everything else is workspace
     radii = torch.empty((C, N), **i32)
     means2d = torch.empty((C, N, 2), **f32)
     depths = torch.empty((C, N), **f32)
     conics = torch.empty((C, N, 3), **f32)
-    render_colors = torch.empty((C, H, W, 3), **f32)
+    render_colors = torch.empty((C, H, W, ch), **f32)
     render_alphas = torch.empty((C, H, W, 1), **f32)
 
     # "gsplat" lists, lazily: render from the short ("tight") lists -- image, alphas, radii, means2d bitwise the same, gradients
@@ -528,7 +531,7 @@ def _forward_stages(means, quats, scales, opacities, colors, colors_rest, viewma
     # depth rounds: inference, one camera, long lists (see ROUNDS_MIN_LISTED above); the decision of a call shape is taken from
     # what its one-round calls listed and kept (a two-round call reports the short total of its two rounds)
     rmode = cfg.get("rounds") or rounds_mode()
-    rounds = (not need_grad) and C == 1 and N > 0 and rmode != "off" and (rmode == "on" or (
+    rounds = (not need_grad) and C == 1 and N > 0 and ch == 3 and rmode != "off" and (rmode == "on" or (
         two_level and int(hint.get("n", -1)) == N and int(hint.get("listed_one_round", 0)) >= ROUNDS_MIN_LISTED and not hint.get("rounds_off")))
     rb = _round_buffers(dev, st, N, tiles) if rounds else None
     eager_ids = os.environ.get("GS_EAGER_ISECT_IDS") == "1"   # (default: meta builds isect_ids on first access, _LazyMeta)
@@ -595,11 +598,18 @@ def _forward_stages(means, quats, scales, opacities, colors, colors_rest, viewma
         if walk is not None:
             nat.check(L.gs_walk_mirror_set(walk.host.data_ptr()), "gs_walk_mirror_set")
         try:
-            _stage("gs_blend_fwd", dev, lambda: nat.check(L.gs_blend_fwd(
-                st, C, W, H, P(WS.REC), _ptr(backgrounds), P(WS.ISECT_OFFSETS), P(WS.TILE_ORDER),
-                P(WS.FLATTEN_IDS), P(WS.SLOTS), cap, _ptr(render_colors), _ptr(render_alphas), P(WS.CKPT), P(WS.QLIST), P(WS.QCNT),
-                P(WS.QMASK), P(WS.UNIT_DESC), lease.layout.cap_units, P(WS.ROW_BASE), lease.layout.cap_rows, P(WS.WALK_STATE)),
-                "gs_blend_fwd"))
+            if ch == 3:
+                _stage("gs_blend_fwd", dev, lambda: nat.check(L.gs_blend_fwd(
+                    st, C, W, H, P(WS.REC), _ptr(backgrounds), P(WS.ISECT_OFFSETS), P(WS.TILE_ORDER),
+                    P(WS.FLATTEN_IDS), P(WS.SLOTS), cap, _ptr(render_colors), _ptr(render_alphas), P(WS.CKPT), P(WS.QLIST), P(WS.QCNT),
+                    P(WS.QMASK), P(WS.UNIT_DESC), lease.layout.cap_units, P(WS.ROW_BASE), lease.layout.cap_rows, P(WS.WALK_STATE)),
+                    "gs_blend_fwd"))
+            else:
+                _stage("gs_blend_fwd", dev, lambda: nat.check(L.gs_blend_fwd_ch(
+                    st, C, W, H, ch, P(WS.REC), _ptr(backgrounds), P(WS.ISECT_OFFSETS), P(WS.TILE_ORDER),
+                    P(WS.FLATTEN_IDS), P(WS.SLOTS), cap, _ptr(render_colors), _ptr(render_alphas), P(WS.CKPT), P(WS.QLIST), P(WS.QCNT),
+                    P(WS.QMASK), P(WS.UNIT_DESC), lease.layout.cap_units, P(WS.ROW_BASE), lease.layout.cap_rows, P(WS.WALK_STATE),
+                    lease.ckpt_ext() if (need_grad and ch == 4) else None), "gs_blend_fwd_ch"))
         finally:
             if walk is not None:
                 L.gs_walk_mirror_set(None)
@@ -610,7 +620,12 @@ def _forward_stages(means, quats, scales, opacities, colors, colors_rest, viewma
     # 3. SH colours; 4. lists + blend, speculatively; 5. only now the host looks at the sizes.
     # (one launch for geometry + colour: since the list stages no longer wait for the host, a colour pass of its own behind
     #  the tile count hides nothing, and the fused launch is 25 us shorter than the two -- GS_FWD_SPLIT=1 keeps the split)
-    project(1 if _SPLIT_PROJECT else 0, "gs_project_fwd")
+    if ch == 3:
+        project(1 if _SPLIT_PROJECT else 0, "gs_project_fwd")
+    else:   # geometry, then the colour quad of the records from the D-channel features
+        project(1, "gs_project_fwd")
+        _stage("gs_rec_colors", dev, lambda: nat.check(L.gs_rec_colors(st, C, N, ch, _ptr(colors), per_cam, _ptr(radii), P(WS.REC)),
+                                                       "gs_rec_colors"))
     sizes = {"attempt": 0, "waited": 0, "info": None}   # (mutable: the deferred check finishes this call after it returned)
     tstream = torch.cuda.current_stream(dev)            # (the stream `st` belongs to: a late repair runs on it, whoever calls)
 
@@ -657,7 +672,7 @@ def _forward_stages(means, quats, scales, opacities, colors, colors_rest, viewma
             nat.check(L.gs_info_mirror_set(None), "gs_info_mirror_set")
             ev = torch.cuda.Event()
             ev.record(tstream)
-            if sizes["attempt"] == 0 and _SPLIT_PROJECT:
+            if sizes["attempt"] == 0 and _SPLIT_PROJECT and ch == 3:
                 project(2, "gs_project_fwd_color")
             lists_and_blend()
         finally:
@@ -808,7 +823,7 @@ def _forward_stages(means, quats, scales, opacities, colors, colors_rest, viewma
     })
     if not lazy_ref:
         meta._lease = ref   # (the list lazies above read the arenas; in the "gsplat" mode nothing in meta does)
-    state = dict(C=C, N=N, K=K, deg=deg, per_cam=per_cam, sh_jac=use_jac, n_isects=n_isects, n_buckets=n_buckets, radii=radii, lease=lease,
+    state = dict(C=C, N=N, K=K, deg=deg, per_cam=per_cam, ch=ch, sh_jac=use_jac, n_isects=n_isects, n_buckets=n_buckets, radii=radii, lease=lease,
                  lease_ref=WS.LeaseRef(lease) if need_grad else None, factorised=factorised, pending=pending, late=state_late,
                  walk=walk, hint_key=hint_key, backgrounds=backgrounds)
     if pending is not None:
@@ -850,9 +865,15 @@ def _settle_walk(s: dict, cfg: dict, render_colors: Tensor, render_alphas: Tenso
             sc, sa = torch.empty_like(render_colors), torch.empty_like(render_alphas)
             nat.check(L.gs_walk_mirror_set(walk.host.data_ptr()), "gs_walk_mirror_set")
             try:
-                nat.check(L.gs_blend_fwd(st, C, W, H, P(WS.REC), _ptr(s["backgrounds"]), P(WS.ISECT_OFFSETS), P(WS.TILE_ORDER),
-                                         P(WS.FLATTEN_IDS), P(WS.SLOTS), s["n_isects"], _ptr(sc), _ptr(sa), P(WS.CKPT), P(WS.QLIST),
-                                         P(WS.QCNT), P(WS.QMASK), P(WS.UNIT_DESC), cu, P(WS.ROW_BASE), cr, P(WS.WALK_STATE)), "gs_blend_fwd")
+                if s["ch"] == 3:
+                    nat.check(L.gs_blend_fwd(st, C, W, H, P(WS.REC), _ptr(s["backgrounds"]), P(WS.ISECT_OFFSETS), P(WS.TILE_ORDER),
+                                             P(WS.FLATTEN_IDS), P(WS.SLOTS), s["n_isects"], _ptr(sc), _ptr(sa), P(WS.CKPT), P(WS.QLIST),
+                                             P(WS.QCNT), P(WS.QMASK), P(WS.UNIT_DESC), cu, P(WS.ROW_BASE), cr, P(WS.WALK_STATE)), "gs_blend_fwd")
+                else:   # (the fourth channel's checkpoint plane follows the new cap_units)
+                    nat.check(L.gs_blend_fwd_ch(st, C, W, H, s["ch"], P(WS.REC), _ptr(s["backgrounds"]), P(WS.ISECT_OFFSETS),
+                                                P(WS.TILE_ORDER), P(WS.FLATTEN_IDS), P(WS.SLOTS), s["n_isects"], _ptr(sc), _ptr(sa), P(WS.CKPT),
+                                                P(WS.QLIST), P(WS.QCNT), P(WS.QMASK), P(WS.UNIT_DESC), cu, P(WS.ROW_BASE), cr, P(WS.WALK_STATE),
+                                                lease.ckpt_ext() if s["ch"] == 4 else None), "gs_blend_fwd_ch")
             finally:
                 L.gs_walk_mirror_set(None)
             torch.cuda.current_stream(dev).synchronize()   # (rare: the capacities follow the largest recent frame)
@@ -922,9 +943,16 @@ class _Rasterize(torch.autograd.Function):
         n_rows = _settle_walk(s, cfg, render_colors, render_alphas)
         # scratch for the backward's fill classes (gs_raster.h; a caching-allocator block, re-used stream-ordered)
         ucls = torch.empty((int(L.gs_unit_classes_ints(lease.layout.cap_units, C, W, H)),), dtype=torch.int32, device=dev) if _BWD_CLASSES else None
-        _stage("gs_blend_bwd", dev, lambda: nat.check(L.gs_blend_bwd(st, C, W, H, P(WS.REC), P(WS.QLIST), P(WS.QCNT),
-                                 P(WS.UNIT_DESC), lease.layout.cap_units, P(WS.CKPT), P(WS.QMASK), P(WS.ROW_BASE), P(WS.WALK_STATE),
-                                 _ptr(render_colors), _ptr(render_alphas), _ptr(v_rc), _ptr(v_ra), P(WS.ROWS), _ptr(ucls)), "gs_blend_bwd"))
+        ch = s["ch"]
+        if ch == 3:
+            _stage("gs_blend_bwd", dev, lambda: nat.check(L.gs_blend_bwd(st, C, W, H, P(WS.REC), P(WS.QLIST), P(WS.QCNT),
+                                     P(WS.UNIT_DESC), lease.layout.cap_units, P(WS.CKPT), P(WS.QMASK), P(WS.ROW_BASE), P(WS.WALK_STATE),
+                                     _ptr(render_colors), _ptr(render_alphas), _ptr(v_rc), _ptr(v_ra), P(WS.ROWS), _ptr(ucls)), "gs_blend_bwd"))
+        else:
+            _stage("gs_blend_bwd", dev, lambda: nat.check(L.gs_blend_bwd_ch(st, C, W, H, ch, P(WS.REC), P(WS.QLIST), P(WS.QCNT),
+                                     P(WS.UNIT_DESC), lease.layout.cap_units, P(WS.CKPT), P(WS.QMASK), P(WS.ROW_BASE), P(WS.WALK_STATE),
+                                     _ptr(render_colors), _ptr(render_alphas), _ptr(v_rc), _ptr(v_ra), P(WS.ROWS), _ptr(ucls),
+                                     lease.ckpt_ext() if ch == 4 else None), "gs_blend_bwd_ch"))
         go = holder.grad_out or {}   # (`_grad_out`: caller-owned gradient tensors; autograd then receives None for those inputs)
         for k_, shp in (("means", (N, 3)), ("quats", (N, 4)), ("scales", (N, 3)), ("opacities", (N,)), ("grad_norm", (N,)), ("count", (N,))):
             if k_ in go and not (go[k_].shape == shp and go[k_].is_contiguous() and go[k_].dtype == torch.float32 and go[k_].device == dev):
@@ -936,6 +964,9 @@ class _Rasterize(torch.autograd.Function):
         v_scales = go["scales"] if "scales" in go else torch.empty((N, 3), **f32)
         v_opac = go["opacities"] if "opacities" in go else torch.empty((N,), **f32)
         v_colors = None if factorised else torch.empty(colors.shape, **f32)
+        # D != 3 feature channels: gs_project_bwd gives the geometry gradients (its colour output, [C,N,3] scratch, is not used) and
+        # gs_channel_grads the channel gradients from the rows' colour quads
+        v_pc, pc_cam = (v_colors, s["per_cam"]) if ch == 3 else (torch.empty((C, N, 3), **f32), 1)
         v_rest = torch.empty(colors_rest.shape, **f32) if (ctx.split and not factorised) else None
         v_pre = row_sums = None
         if factorised:
@@ -969,13 +1000,17 @@ class _Rasterize(torch.autograd.Function):
             v_cn = torch.empty((C, N, 3), **f32)
             v_cp = torch.empty((C, N, 3), **f32)
         _stage("gs_project_bwd", dev, lambda: nat.check(L.gs_project_bwd(st, C, N, K, s["deg"], _ptr(means), _ptr(quats), _ptr(scales), _ptr(colors),
-                                   _ptr(colors_rest), s["per_cam"], _ptr(viewmats), _ptr(Ks), W, H, cfg["eps2d"],
+                                   _ptr(colors_rest), pc_cam, _ptr(viewmats), _ptr(Ks), W, H, cfg["eps2d"],
                                    cfg["near_plane"], cfg["far_plane"], _ptr(s["radii"]),
                                    P(WS.COLORS_POST), P(WS.TILES_PER_GAUSS), P(WS.CUM_TILES),
                                    P(WS.ROWS), P(WS.ROW_BASE), P(WS.QMASK), _ptr(v_means), _ptr(v_quats), _ptr(v_scales), _ptr(v_opac),
-                                   _ptr(v_colors), _ptr(v_rest), _ptr(v_abs), _ptr(v_m2), _ptr(v_cn), _ptr(v_cp), None,
+                                   _ptr(v_pc), _ptr(v_rest), _ptr(v_abs), _ptr(v_m2), _ptr(v_cn), _ptr(v_cp), None,
                                    _ptr(opacities), cfg.get("activations", 0), P(WS.SH_JAC) if s.get("sh_jac") else None,
                                    _ptr(row_sums), _ptr(go.get("grad_norm")), _ptr(go.get("count"))), "gs_project_bwd"))
+        if ch != 3:
+            _stage("gs_channel_grads", dev, lambda: nat.check(L.gs_channel_grads(
+                st, C, N, ch, s["per_cam"], _ptr(s["radii"]), P(WS.TILES_PER_GAUSS), P(WS.CUM_TILES), P(WS.ROWS), P(WS.ROW_BASE),
+                P(WS.QMASK), _ptr(v_colors)), "gs_channel_grads"))
         if holder.grad_out is not None:
             holder.grad_out["_written"] = True   # (the caller's own dict: it can tell that its tensors were filled by THIS backward)
         if dbg is not None:
@@ -1052,7 +1087,7 @@ def rasterization(
     quats: Tensor,  # [N, 4]  wxyz, need not be normalised
     scales: Tensor,  # [N, 3]
     opacities: Tensor,  # [N]
-    colors,  # Tensor [N, K, 3] SH coefficients (sh_degree given) or [N, 3] / [C, N, 3]; or (sh_0, sh_rest)
+    colors,  # Tensor [N, K, 3] SH coefficients (sh_degree given) or features [N, D] / [C, N, D], D = 1..4; or (sh_0, sh_rest)
     viewmats: Tensor,  # [C, 4, 4] world -> camera
     Ks: Tensor,  # [C, 3, 3]
     width: int,
@@ -1083,7 +1118,13 @@ def rasterization(
     """Rasterize 3D Gaussians to images; same tensor signature and return value as
     `gsplat.rendering.rasterization` (gsplat 1.0.0).
 
-    Returns `(render_colors [C,H,W,3], render_alphas [C,H,W,1], meta)`.  `meta["means2d"]`
+    Returns `(render_colors [C,H,W,D], render_alphas [C,H,W,1], meta)`; D = 3 with SH colours.
+
+    Colour features (`sh_degree=None`): `colors` [N,D] or [C,N,D] with D in 1..4, `backgrounds` [C,D]; gsplat's semantics -- no
+    clamp, background added as (1 - alpha) * bg per channel, gradients to means, quats, scales, opacities, colours and `.absgrad`.
+    D = 3 is the RGB path; D = 1, 2, 4 go through the channel entry points (include/gs_raster.h), always in ONE depth round
+    whatever `_rounds` / GS_ROUNDS say.  D > 4 raises `NotImplementedError` (no `channel_chunk` splitting).  A depth map is a
+    channel: INTEGRATION.md "Depth as a channel".  `meta["means2d"]`
     receives the attribute `.absgrad` ([C,N,2]) during backward when `absgrad=True`, and -- a leaf that requires grad whenever
     the render does -- `.grad` = dL/d means2d ([C,N,2]; gsplat: after `meta["means2d"].retain_grad()`, a no-op here);
     `meta["radii"]` is int32 [C,N] with `> 0` marking visible Gaussians.
@@ -1156,8 +1197,10 @@ def rasterization(
     if sh_degree is None:
         assert (colors.dim() == 2 and colors.shape[0] == N) or (
             colors.dim() == 3 and colors.shape[:2] == (C, N)), colors.shape
-        if colors.shape[-1] != 3:
-            raise NotImplementedError("only 3-channel colours are implemented on the HIP path")
+        assert colors.shape[-1] >= 1, colors.shape
+        if colors.shape[-1] > 4:
+            raise NotImplementedError(f"colour features of at most 4 channels are implemented on the HIP path (got {colors.shape[-1]}; "
+                                      "channel_chunk splitting is not implemented)")
     else:
         assert colors.dim() == 3 and colors.shape[0] == N and colors.shape[2] == 3, colors.shape
         k_store = colors.shape[1] + (0 if colors_rest is None else colors_rest.shape[1])
@@ -1165,7 +1208,7 @@ def rasterization(
         if sh_degree > 3 or k_store > 16:
             raise NotImplementedError("SH degree > 3 is not implemented")
     if backgrounds is not None:
-        assert backgrounds.shape == (C, 3), backgrounds.shape
+        assert backgrounds.shape == (C, 3 if sh_degree is not None else colors.shape[-1]), backgrounds.shape
     if packed:
         raise NotImplementedError("packed=True is not implemented (the reference passes packed=False)")
     if render_mode != "RGB":

@@ -45,7 +45,7 @@ _DTYPES = {INFO: torch.int64, REC: torch.float32, BBOX: torch.int32, TILES_PER_G
            QMASK: torch.uint8, ROWS: torch.float32, QLIST: torch.int32, UNIT_DESC: torch.int32,
            CKPT: torch.float32}
 
-stats = {"leases_created": 0, "acquires": 0, "fixed_allocs": 0, "list_allocs": 0, "walk_allocs": 0, "list_grows": 0, "walk_grows": 0, "binds": 0}
+stats = {"leases_created": 0, "acquires": 0, "fixed_allocs": 0, "list_allocs": 0, "walk_allocs": 0, "list_grows": 0, "walk_grows": 0, "binds": 0, "ckpt_ext_allocs": 0}
 
 
 class Layout:
@@ -73,6 +73,7 @@ class Lease:
         self.fixed: Optional[torch.Tensor] = None
         self.lists: Optional[torch.Tensor] = None
         self.walk: Optional[torch.Tensor] = None
+        self._ckpt_ext: Optional[torch.Tensor] = None
         self.layout: Optional[Layout] = None
         self.cap = 0
         self.busy = False
@@ -136,6 +137,16 @@ class Lease:
         self.layout = layout
         self._bound = (self.fixed.data_ptr(), self.lists.data_ptr(), self.walk.data_ptr(), layout.key)
         stats["walk_grows"] += 1
+
+    def ckpt_ext(self) -> int:
+        """Device address of the fourth colour channel's checkpoint plane (gs_blend_fwd_ch with 4 channels, training): cap_units * 64
+        floats of the current layout -- it follows grow_walk like the walk arena.  Kept with the lease, outside the three arenas
+        (gs_workspace_query's layout is the 3-channel one); allocated on first use only."""
+        n = self.layout.cap_units * 64
+        if self._ckpt_ext is None or self._ckpt_ext.numel() < n:
+            self._ckpt_ext = torch.empty((n + (n >> 3) + 1024,), dtype=torch.float32, device=self.device)
+            stats["ckpt_ext_allocs"] += 1
+        return self._ckpt_ext.data_ptr()
 
     def ptr(self, slot: int) -> Optional[int]:
         off = self.layout.offsets[slot]

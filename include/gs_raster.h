@@ -371,6 +371,41 @@ int gs_blend_bwd(void* stream, int C, int width, int height, const float* rec,
                  const float* render_colors, const float* render_alphas, const float* v_render_colors,
                  const float* v_render_alphas, float* rows, int32_t* unit_classes);
 
+/* Colour features of 1 .. 4 channels (gsplat's colors[N,D] / [C,N,D] with sh_degree = None; channels = D).  The record's colour
+ * quad (floats 8..11) and the gradient row's colour quad (floats 8..11) carry up to four channels, zero above D; channels = 3 is
+ * gs_blend_fwd / gs_blend_bwd itself.  A call sequence:
+ *   forward   gs_project_fwd(sh_degree = -1, stage = 1), gs_rec_colors, the list stages, gs_blend_fwd_ch
+ *   backward  gs_blend_bwd_ch, gs_project_bwd(sh_degree = -1, colors_per_camera = 1, v_colors = [C*N*3] scratch) for the geometry
+ *             gradients, gs_channel_grads for v_colors
+ * Depth rounds are 3-channel only (tile_state holds T, r, g, b): these entry points refuse gs_rounds_set phases other than 0.
+ * Every entry point checks channels in {1, 2, 3, 4} and its pointers before it launches anything.
+ * gs_rec_colors: rec[C*N*12] floats 8..11 = colors[D] of the Gaussians with radii > 0 (colors[N,D], or [C,N,D] with
+ *   colors_per_camera = 1), no clamp; everything else in rec is left as gs_project_fwd(stage = 1) wrote it.
+ * gs_blend_fwd_ch: gs_blend_fwd with backgrounds[C,D] (may be NULL) and render_colors[C,H,W,D].  channels = 4 in training mode also
+ *   needs ckpt_ext[cap_units*64] f32 (the fourth channel's accumulated value in front of each work unit; the same cap_units as ckpt);
+ *   NULL otherwise.
+ * gs_blend_bwd_ch: gs_blend_bwd with render_colors / v_render_colors [C,H,W,D]; rows' floats 8..8+D = the channel gradients (zero
+ *   above D).  channels = 4 needs the forward's ckpt_ext.
+ * gs_channel_grads: v_colors[N,D] (summed over the cameras in camera order) or [C,N,D] (colors_per_camera = 1) = the sums of the
+ *   colour quads of each Gaussian's rows (gathered as gs_project_bwd gathers them); zero for culled Gaussians.  Honours the step
+ *   guard. */
+int gs_rec_colors(void* stream, int C, int64_t N, int channels, const float* colors, int colors_per_camera, const int32_t* radii,
+                  float* rec);
+int gs_blend_fwd_ch(void* stream, int C, int width, int height, int channels, const float* rec,
+                    const float* backgrounds, const int32_t* isect_offsets, const int32_t* tile_order,
+                    const int32_t* flatten_ids, const int32_t* slots, int64_t n_isects, float* render_colors,
+                    float* render_alphas, float* ckpt, int32_t* qlist, int32_t* qcnt, uint8_t* qmask,
+                    int32_t* unit_desc, int64_t cap_units, int32_t* row_base, int64_t cap_rows, int32_t* walk_state,
+                    float* ckpt_ext);
+int gs_blend_bwd_ch(void* stream, int C, int width, int height, int channels, const float* rec,
+                    const int32_t* qlist, const int32_t* qcnt, const int32_t* unit_desc, int64_t cap_units,
+                    const float* ckpt, const uint8_t* qmask, const int32_t* row_base, const int32_t* walk_state,
+                    const float* render_colors, const float* render_alphas, const float* v_render_colors,
+                    const float* v_render_alphas, float* rows, int32_t* unit_classes, const float* ckpt_ext);
+int gs_channel_grads(void* stream, int C, int64_t N, int channels, int colors_per_camera, const int32_t* radii,
+                     const int32_t* tiles_per_gauss, const int32_t* cum_tiles, const float* rows, const int32_t* row_base,
+                     const uint8_t* qmask, float* v_colors);
+
 /* Row reduction + SH-bwd + P-bwd fused (replaces the atomics of the blend backward,
  * spherical_harmonics backward and fully_fused_projection backward).  Sums each Gaussian's rows
  * (slots [cum_tiles[f], cum_tiles[f]+tiles_per_gauss[f]) = rows [rows_before(first slot), rows_before(last slot + 1)): row_base + qmask) and

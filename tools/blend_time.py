@@ -1,31 +1,48 @@
 #!/usr/bin/env python3
 """Kernel times of the rasterizer's stages on a FIXED scene (no optimizer in the loop): rasterization forward + backward of the
 bench workload, HIP events around every stage (rendering.profile_stages), 30 repetitions.  For A/B runs of library variants
-whose backward may be numerically wrong on purpose (timing experiments):  GS_LIB_PATH=... tools/blend_time.py [n_gauss]"""
+whose backward may be numerically wrong on purpose (timing experiments):  GS_LIB_PATH=... tools/blend_time.py [n_gauss]
+`--channels D` (D = 1 .. 4): non-SH colour features [N, D] with backgrounds [1, D] instead of the SH colours (D = 3: the RGB path
+with pre-activated colours; D = 1, 2, 4: the channel entry points)."""
 import json, os, sys
 ROOT = os.environ.get("GRAFT_REPO_ROOT", os.path.dirname(os.path.dirname(os.path.abspath(__file__)))); sys.path.insert(0, ROOT)
 import numpy as np, torch
 from easy_gaussian_splatting_amd import rendering
 from easy_gaussian_splatting_amd.synthetic import config_bench_1m
-n = int(sys.argv[1]) if len(sys.argv) > 1 else 1_000_000
+args = sys.argv[1:]
+channels = None
+if "--channels" in args:
+    i = args.index("--channels")
+    channels = int(args[i + 1])
+    del args[i:i + 2]
+n = int(args[0]) if args else 1_000_000
 dev = torch.device("cuda:0")
 sc = config_bench_1m(n=n)
 t = {k: torch.from_numpy(v).to(dev) for k, v in sc.items() if isinstance(v, np.ndarray)}
 ins = [t[k].clone().requires_grad_(True) for k in ("means", "quats", "scales", "opacities")]
 sh0, shr = t["shs"][:, :1].contiguous().requires_grad_(True), t["shs"][:, 1:].contiguous().requires_grad_(True)
+if channels is not None:
+    feats = torch.rand((n, channels), generator=torch.Generator().manual_seed(0)).to(dev).requires_grad_(True)
+    bg = torch.ones((1, channels), device=dev)
 vc = None
 def step():
     global vc
-    img, _, meta = rendering.rasterization(*ins, (sh0, shr), t["viewmats"], t["Ks"], 1920, 1080, sh_degree=3, packed=False,
-                                           backgrounds=t["backgrounds"], absgrad=True, _tile_culling="tight")
+    if channels is None:
+        img, _, meta = rendering.rasterization(*ins, (sh0, shr), t["viewmats"], t["Ks"], 1920, 1080, sh_degree=3, packed=False,
+                                               backgrounds=t["backgrounds"], absgrad=True, _tile_culling="tight")
+        params = ins + [sh0, shr]
+    else:
+        img, _, meta = rendering.rasterization(*ins, feats, t["viewmats"], t["Ks"], 1920, 1080, sh_degree=None, packed=False,
+                                               backgrounds=bg, absgrad=True, _tile_culling="tight")
+        params = ins + [feats]
     if vc is None:
         vc = torch.randn_like(img) / (1920 * 1080)
-    torch.autograd.grad((img * vc).sum(), ins + [sh0, shr])
+    torch.autograd.grad((img * vc).sum(), params)
     return meta
 meta = step()
 for _ in range(5): step()
 rendering.profile_stages(True)
 for _ in range(30): step()
 st = rendering.profile_stages(False) or {}
-print(json.dumps({"lib": os.path.basename(os.environ.get("GS_LIB_PATH", "libgsraster.so")), "n_isects": int(meta["flatten_ids"].shape[0]),
+print(json.dumps({"lib": os.path.basename(os.environ.get("GS_LIB_PATH", "libgsraster.so")), "channels": channels, "n_isects": int(meta["flatten_ids"].shape[0]),
                   **{k[3:]: round(float(np.median(v)), 4) for k, v in sorted(st.items())}}))
