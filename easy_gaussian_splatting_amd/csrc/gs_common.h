@@ -177,6 +177,52 @@ __device__ __forceinline__ void adam1(float& p, float g, float& m, float& v, flo
     p = p - ss * (m / denom);
 }
 
+// x as it is, hidden from the optimizer: a product behind it is rounded on its own instead of fused into the add that reads it
+// (the library is built with -ffp-contract=fast; autograd rounds every product and every sum separately)
+__device__ __forceinline__ float fp_opaque(float x) {
+    asm volatile("" : "+v"(x));
+    return x;
+}
+
+// exp(x) as the compiler lowers expf without -ffp-contract=fast (torch.exp's device kernel, bit for bit): 2^(x log2 e) with log2 e in
+// two parts, the integer part split off, v_exp_f32 of the rest, ldexp.  The library's own expf is built with contraction on, which
+// fuses the product in front of `ph - e` into an fma and counts its rounding error twice (up to a few ulp off).
+__device__ __forceinline__ float exp_ref(float x) {
+    const float c = 0x1.715476p+0f, cc = 0x1.4ae0bep-26f;
+    const float ph = fp_opaque(x * c);
+    const float pl = fmaf(x, cc, fmaf(x, c, -ph));
+    const float e = __builtin_rintf(ph);
+    const float a = fp_opaque(ph - e) + pl;
+    float r = __builtin_amdgcn_ldexpf(__builtin_amdgcn_exp2f(a), (int)e);
+    r = x < -0x1.9d1da0p+6f ? 0.f : r;
+    return x > 0x1.62e430p+6f ? __builtin_huge_valf() : r;
+}
+
+// Scale-ratio regulariser of one Gaussian (the reference's GaussianModel.get_regularization_dict): l = its log-scales, R = the
+// largest ratio left free, g = the upstream gradient of its term (lambda * (1 / N) as torch forms it on the device).  Returns
+// max(max_k s_k / min_k s_k, R) - R, s = exp(l) (exp_ref), and writes d(g * term)/dl into gl[3] in torch autograd's fp32 sequence:
+// clamp(min=R) passes g where ratio >= R; div: g / amin for the max, -g * ((amax / amin) / amin) for the min; amax / amin
+// backward: (part / count) * mask, so tied maxima or minima share evenly; the two parts summed, then * s (exp backward).
+// Every gl[k] is a rounded value of its own (fp_opaque): the caller adds it to a render gradient as autograd does.
+__device__ __forceinline__ float scale_reg_term(float l0, float l1, float l2, float R, float g, float gl[3]) {
+    const float s[3] = {exp_ref(l0), exp_ref(l1), exp_ref(l2)};
+    const float mx = fmaxf(fmaxf(s[0], s[1]), s[2]), mn = fminf(fminf(s[0], s[1]), s[2]);
+    const float ratio = mx / mn;
+    const float gc = ratio >= R ? g : 0.f;
+    const float pmax = gc / mn, pmin = -gc * ((mx / mn) / mn);
+    const float cmax = (float)((s[0] == mx) + (s[1] == mx) + (s[2] == mx)), cmin = (float)((s[0] == mn) + (s[1] == mn) + (s[2] == mn));
+    const float qmax = pmax / cmax, qmin = pmin / cmin;
+#pragma unroll
+    for (int k = 0; k < 3; ++k) {
+        const float a = fp_opaque(qmax * (s[k] == mx ? 1.f : 0.f)), b = fp_opaque(qmin * (s[k] == mn ? 1.f : 0.f));
+        gl[k] = fp_opaque(fp_opaque(a + b) * s[k]);
+    }
+    return fmaxf(ratio, R) - R;
+}
+// g of scale_reg_term as torch forms it on the device: lambda (the mul by a Python float) times 1 / N (mean backward divides by a
+// scalar, which torch's device kernel does as a multiply by the scalar's reciprocal)
+inline float scale_reg_upstream(float lambda, int64_t N) { return lambda * (1.0f / (float)N); }
+
 // streaming (non-temporal) 16-byte accesses for data that is touched once and then dead
 #ifdef __HIPCC__
 typedef float f4v __attribute__((ext_vector_type(4)));

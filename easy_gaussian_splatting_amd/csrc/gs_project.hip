@@ -398,6 +398,9 @@ struct ProjBwdArgs {
     const float* row_sums;            // optional [C*N][12]
     float *st_gn_out, *st_cnt_out;    // optional [N] each (single camera)
     const int64_t* rblk;              // depth rounds (gs_rounds_set phase 3): the rows are two ranges, split at slot rblk[GS_ROUND_BASE]
+    // Scale-ratio regulariser (gs_project_bwd_adam_reg; project_bwd_kernel<.., REG = true> only): the free ratio R and the upstream
+    // gradient of one term, lambda * (1 / N) -- its gradient joins v_scale of every in-range Gaussian in front of the Adam update
+    float reg_ratio, reg_grad;
 };
 
 __device__ __forceinline__ float* adam_p(const ProjBwdArgs& a, int t) { return a.ad_pbase + a.ad_off[t]; }
@@ -729,7 +732,8 @@ __device__ __forceinline__ void row_sum_wave(const A& a, int nr, int r0, int bas
 
 // SUMS: the row sums come from gs_row_sums (a.row_sums) -- an instantiation of its own, so that the row-walking form keeps the
 // registers it had (a run-time branch cost it its third wave per SIMD and put the fused form into scratch).
-template <int DEG, bool ADAM, bool SUMS = false>
+// REG (with ADAM only): the scale-ratio regulariser's gradient is added to v_scale -- likewise an instantiation of its own.
+template <int DEG, bool ADAM, bool SUMS = false, bool REG = false>
 __global__ __launch_bounds__(kProjThreads) void project_bwd_kernel(const ProjBwdArgs a) {
     extern __shared__ __attribute__((aligned(16))) float smem[];
     if (guard_tripped(a.guard)) return;
@@ -856,6 +860,11 @@ __global__ __launch_bounds__(kProjThreads) void project_bwd_kernel(const ProjBwd
     if (in_range) {
         if (a.activations && vis) { const float o = act_opacity(p_opac[n], 1); op_fac = o * (1.f - o); }
         v_scale[0] *= sc_fac[0]; v_scale[1] *= sc_fac[1]; v_scale[2] *= sc_fac[2];
+        if (REG) {   // + the regulariser's gradient (culled Gaussians too: every Gaussian has a term), from the parameters before the update
+            float gl[3];
+            scale_reg_term(p_scales[3 * n], p_scales[3 * n + 1], p_scales[3 * n + 2], a.reg_ratio, a.reg_grad, gl);
+            v_scale[0] = fp_opaque(v_scale[0]) + gl[0]; v_scale[1] = fp_opaque(v_scale[1]) + gl[1]; v_scale[2] = fp_opaque(v_scale[2]) + gl[2];
+        }
         const float v_op = s.v[7] * op_fac;
         float* vm = a.v_means + 3 * n; float* vq = a.v_quats + 4 * n; float* vs = a.v_scales + 3 * n;
         if (ADAM) {
@@ -1228,6 +1237,7 @@ extern "C" int gs_project_bwd(void* stream, int C, int64_t N, int K, int sh_degr
     a.row_sums = row_sums; a.st_gn_out = stat_grad_norm; a.st_cnt_out = stat_count;
     a.ad_pbase = a.ad_mbase = a.ad_vbase = nullptr;
     for (int t = 0; t < 6; ++t) a.ad_off[t] = 0;
+    a.reg_ratio = a.reg_grad = 0.f;
     dim3 grid((unsigned)((N + kProjThreads - 1) / kProjThreads));
     const size_t lds = proj_bwd_lds_bytes(K, sh_degree);
     hipStream_t st = (hipStream_t)stream;
@@ -1258,13 +1268,13 @@ extern "C" int gs_project_bwd(void* stream, int C, int64_t N, int K, int sh_degr
 // where the gradient is formed.  params / exp_avg / exp_avg_sq: the flat buffers of gs_adam_step, the six tensors
 // of param_names at offsets_host[6] floats.  hyper_dev: gs_adam_hyper.  Only v_means2d_abs (the `.absgrad`
 // side channel) is still written; with max_radii / grad_norm_accum / counts given, update_statistics is applied too.
-extern "C" int gs_project_bwd_adam(void* stream, int64_t N, int K, int sh_degree, float* params, float* exp_avg, float* exp_avg_sq,
-                                   const int64_t* offsets_host, const float* viewmats, const float* Ks, int width, int height,
-                                   float eps2d, float near_plane, float far_plane, const int32_t* radii, const float* colors_post,
-                                   const int32_t* tiles_per_gauss, const int32_t* cum_tiles, const float* rows, const int32_t* row_base, const uint8_t* qmask,
-                                   float* v_means2d_abs, float beta1, float beta2, float eps, const float* hyper_dev,
-                                   int64_t* applied_dev, float* max_radii, float* grad_norm_accum, float* counts,
-                                   const float* sh_jac) {
+static int project_bwd_adam(void* stream, int64_t N, int K, int sh_degree, float* params, float* exp_avg, float* exp_avg_sq,
+                            const int64_t* offsets_host, const float* viewmats, const float* Ks, int width, int height,
+                            float eps2d, float near_plane, float far_plane, const int32_t* radii, const float* colors_post,
+                            const int32_t* tiles_per_gauss, const int32_t* cum_tiles, const float* rows, const int32_t* row_base, const uint8_t* qmask,
+                            float* v_means2d_abs, float beta1, float beta2, float eps, const float* hyper_dev,
+                            int64_t* applied_dev, float* max_radii, float* grad_norm_accum, float* counts,
+                            const float* sh_jac, bool reg, float max_ratio, float lambda) {
     GS_REQUIRE(N >= 0 && width > 0 && height > 0, "N>=0, positive image size");
     GS_REQUIRE(sh_degree >= 0 && sh_degree <= 3 && K >= (sh_degree + 1) * (sh_degree + 1) && K <= 16, "SH colours: 0 <= degree <= 3, (degree+1)^2 <= K <= 16");
     if (N == 0) return GS_OK;
@@ -1293,12 +1303,15 @@ extern "C" int gs_project_bwd_adam(void* stream, int64_t N, int K, int sh_degree
     a.ad_pbase = params; a.ad_mbase = exp_avg; a.ad_vbase = exp_avg_sq;
     for (int t = 0; t < 6; ++t) a.ad_off[t] = offsets_host[t];
     a.cam = 0; a.accumulate = 0;
+    a.reg_ratio = max_ratio; a.reg_grad = reg ? scale_reg_upstream(lambda, N) : 0.f;
     dim3 grid((unsigned)((N + kProjThreads - 1) / kProjThreads));
     const size_t lds = proj_bwd_lds_bytes(K, sh_degree);
     hipStream_t st = (hipStream_t)stream;
     // (no row_sums form of the fused kernel: its instantiation kept a dead 36-byte stack object, and a kernel that declares
     //  scratch makes the runtime provision it -- gs_blend.hip, GS_FWD_TRAIN_WAVES_PER_EU)
-#define GS_PB(D) hipLaunchKernelGGL((project_bwd_kernel<D, true, false>), grid, dim3(kProjThreads), lds, st, a)
+#define GS_PB(D)                                                                                                        \
+    if (reg) hipLaunchKernelGGL((project_bwd_kernel<D, true, false, true>), grid, dim3(kProjThreads), lds, st, a);     \
+    else hipLaunchKernelGGL((project_bwd_kernel<D, true, false>), grid, dim3(kProjThreads), lds, st, a)
     switch (sh_degree) {
         case 0: GS_PB(0); break;
         case 1: GS_PB(1); break;
@@ -1308,4 +1321,30 @@ extern "C" int gs_project_bwd_adam(void* stream, int64_t N, int K, int sh_degree
 #undef GS_PB
     GS_LAUNCH_CHECK("project_bwd_kernel (fused Adam)");
     return GS_OK;
+}
+
+extern "C" int gs_project_bwd_adam(void* stream, int64_t N, int K, int sh_degree, float* params, float* exp_avg, float* exp_avg_sq,
+                                   const int64_t* offsets_host, const float* viewmats, const float* Ks, int width, int height,
+                                   float eps2d, float near_plane, float far_plane, const int32_t* radii, const float* colors_post,
+                                   const int32_t* tiles_per_gauss, const int32_t* cum_tiles, const float* rows, const int32_t* row_base, const uint8_t* qmask,
+                                   float* v_means2d_abs, float beta1, float beta2, float eps, const float* hyper_dev,
+                                   int64_t* applied_dev, float* max_radii, float* grad_norm_accum, float* counts,
+                                   const float* sh_jac) {
+    return project_bwd_adam(stream, N, K, sh_degree, params, exp_avg, exp_avg_sq, offsets_host, viewmats, Ks, width, height, eps2d,
+                            near_plane, far_plane, radii, colors_post, tiles_per_gauss, cum_tiles, rows, row_base, qmask, v_means2d_abs,
+                            beta1, beta2, eps, hyper_dev, applied_dev, max_radii, grad_norm_accum, counts, sh_jac, false, 0.f, 0.f);
+}
+
+// ... with the scale-ratio regulariser's gradient in v_scale (its value: gs_scale_reg in front of this call)
+extern "C" int gs_project_bwd_adam_reg(void* stream, int64_t N, int K, int sh_degree, float* params, float* exp_avg, float* exp_avg_sq,
+                                       const int64_t* offsets_host, const float* viewmats, const float* Ks, int width, int height,
+                                       float eps2d, float near_plane, float far_plane, const int32_t* radii, const float* colors_post,
+                                       const int32_t* tiles_per_gauss, const int32_t* cum_tiles, const float* rows, const int32_t* row_base,
+                                       const uint8_t* qmask, float* v_means2d_abs, float beta1, float beta2, float eps, const float* hyper_dev,
+                                       int64_t* applied_dev, float* max_radii, float* grad_norm_accum, float* counts,
+                                       const float* sh_jac, float max_ratio, float lambda) {
+    GS_REQUIRE(((uintptr_t)params & 3) == 0, "params must be 4-byte aligned");
+    return project_bwd_adam(stream, N, K, sh_degree, params, exp_avg, exp_avg_sq, offsets_host, viewmats, Ks, width, height, eps2d,
+                            near_plane, far_plane, radii, colors_post, tiles_per_gauss, cum_tiles, rows, row_base, qmask, v_means2d_abs,
+                            beta1, beta2, eps, hyper_dev, applied_dev, max_radii, grad_norm_accum, counts, sh_jac, true, max_ratio, lambda);
 }

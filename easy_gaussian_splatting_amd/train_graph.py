@@ -98,8 +98,15 @@ class TrainStepGraph:
             raise TypeError("TrainStepGraph drives optim.FusedAdam (flat parameter / moment buffers)")
         if not getattr(loss_computer, "clamp_input", False) or not getattr(loss_computer, "fused", True):
             raise ValueError("TrainStepGraph needs LossComputer(fused=True, clamp_input=True)")
-        if getattr(loss_computer, "model", None) is not None and getattr(model, "USE_SCALE_REGULARIZATION", False):
-            raise NotImplementedError("the scale regulariser is not part of the captured step")
+        # the scale-ratio regulariser (LossComputer(model=..., lambda_scale=...) with use_scale_regularization): its value joins the
+        # loss total and its gradient the log-scales' (gs_scale_reg / gs_project_bwd_adam_reg); R and lambda are read once, here
+        self.scale_reg = getattr(loss_computer, "model", None) is not None and bool(getattr(model, "USE_SCALE_REGULARIZATION", False))
+        if self.scale_reg:
+            if loss_computer.model is not model:
+                raise ValueError("TrainStepGraph: the LossComputer regularises another model than the one it trains")
+            r = model.MAX_SCALE_RATIO
+            self.max_scale_ratio = float(r.detach().cpu()) if isinstance(r, Tensor) else float(r)   # (a 0-d tensor from a checkpoint)
+            self.lambda_scale = float(loss_computer.lambda_scale)
         self.model, self.opt, self.lc = model, optimizer, loss_computer
         self.margin, self.use_graph, self.check_every = float(margin), bool(use_graph), int(check_every)
         # fuse_adam: gs_project_bwd_adam -- the projection / SH backward applies Adam in place where each gradient is
@@ -203,6 +210,8 @@ class TrainStepGraph:
             "sh_rest": torch.empty((N, self.K - 1, 3), **f32) if self.K > 1 else None,
             "logit_opacities": torch.empty((N,), **f32)}
         b["hyper"] = torch.zeros((16,), **f32)
+        # {reg, -, fp64 block partials}: the regulariser's value and its reduction scratch (gs_scale_reg)
+        b["scale_reg"] = self._take("scale_reg", (int(L.gs_scale_reg_workspace_floats(N)),), torch.float32) if self.scale_reg else None
         self._stage_inputs(max(self.opt._step, 0) + 1, [float(grp["lr"]) for grp, _ in self.opt._plist], data["w2c"], data["K"], gt_img, mask)
         probe_walk = False
         front_before, self.front_only = self.front_only, False   # (the probes below run both rounds)
@@ -624,6 +633,8 @@ class TrainStepGraph:
                                              _p(b["loss3"])), "gs_l1_ssim_fwd_slots")
             self._ck(L.gs_l1_ssim_bwd_slots(st, H, W, lam, _p(b["render_colors"]), _p(b["img_slots"]), 1, _p(b["loss_ws"]),
                                              _p(b["one"]), _p(b["v_render"])), "gs_l1_ssim_bwd_slots")
+            if self.scale_reg and self.fuse_adam:   # the value, from the parameters before the in-place update; the gradient: below
+                self._scale_reg(None)
             self._ck(L.gs_blend_bwd(st, 1, W, H, _p(b["rec"]), _p(b["qlist"]), _p(b["qcnt"]), _p(b["unit_desc"]), self.cap_units,
                                      _p(b["ckpt"]), _p(b["qmask"]), _p(b["row_base"]), _p(b["walk_state"]),
                                      _p(b["render_colors"]), _p(b["render_alphas"]), _p(b["v_render"]), None, _p(b["rows"]), _p(b["unit_cls"])),
@@ -631,12 +642,16 @@ class TrainStepGraph:
             b1, b2 = opt.defaults["betas"]
             if self.fuse_adam:
                 offs = (ct.c_int64 * 6)(*opt._offs)
-                self._ck(L.gs_project_bwd_adam(st, N, self.K, int(m.active_sh_degree), _p(opt.flat_param), _p(opt.exp_avg),
-                                               _p(opt.exp_avg_sq), offs, _p(b["viewmats"]), _p(b["Ks"]), W, H, 0.3, 0.01, 1e10,
-                                               _p(b["radii"]), _p(b["colors_post"]), self._tpg(), _p(b["cum_tiles"]),
-                                               _p(b["rows"]), _p(b["row_base"]), _p(b["qmask"]), _p(b["v_abs"]), float(b1), float(b2),
-                                               float(opt.defaults["eps"]), _p(b["hyper"]), _p(b["applied"]), _p(m.max_radii),
-                                               _p(m.grad_norm_accum), _p(m.collecting_counts), _p(b["sh_jac"])), "gs_project_bwd_adam")
+                args = (st, N, self.K, int(m.active_sh_degree), _p(opt.flat_param), _p(opt.exp_avg),
+                        _p(opt.exp_avg_sq), offs, _p(b["viewmats"]), _p(b["Ks"]), W, H, 0.3, 0.01, 1e10,
+                        _p(b["radii"]), _p(b["colors_post"]), self._tpg(), _p(b["cum_tiles"]),
+                        _p(b["rows"]), _p(b["row_base"]), _p(b["qmask"]), _p(b["v_abs"]), float(b1), float(b2),
+                        float(opt.defaults["eps"]), _p(b["hyper"]), _p(b["applied"]), _p(m.max_radii),
+                        _p(m.grad_norm_accum), _p(m.collecting_counts), _p(b["sh_jac"]))
+                if self.scale_reg:
+                    self._ck(L.gs_project_bwd_adam_reg(*args, self.max_scale_ratio, self.lambda_scale), "gs_project_bwd_adam_reg")
+                else:
+                    self._ck(L.gs_project_bwd_adam(*args), "gs_project_bwd_adam")
             else:
                 g = self.grads
                 self._ck(L.gs_project_bwd(st, 1, N, self.K, int(m.active_sh_degree), _p(m.means), _p(m.quats), _p(m.log_scales),
@@ -645,6 +660,8 @@ class TrainStepGraph:
                                           _p(b["cum_tiles"]), _p(b["rows"]), _p(b["row_base"]), _p(b["qmask"]), _p(g["means"]), _p(g["quats"]),
                                           _p(g["log_scales"]), _p(g["logit_opacities"]), _p(g["sh_0"]), _p(g["sh_rest"]), _p(b["v_abs"]),
                                           None, None, None, None, _p(m.logit_opacities), 1, _p(b["sh_jac"]), None, None, None), "gs_project_bwd")
+                if self.scale_reg:   # value into the loss total, gradient onto the render's
+                    self._scale_reg(g["log_scales"])
                 self._ck(L.gs_update_statistics(st, N, float(max(H, W)), _p(b["radii"]), _p(b["v_abs"]), _p(m.max_radii),
                                                 _p(m.grad_norm_accum), _p(m.collecting_counts)), "gs_update_statistics")
                 ns = len(opt._plist)
@@ -661,6 +678,14 @@ class TrainStepGraph:
         finally:
             L.gs_guard_set(None, 0, 0)
             L.gs_rounds_set(None, None, None, None, 0)
+
+    def _scale_reg(self, v_log_scales: Optional[Any], check=None):
+        """The scale-ratio regulariser on the current stream: lambda * reg into loss3[2], reg into buf["scale_reg"][0], and (a gradient
+        tensor or a device address given) its gradient added to that log-scale gradient."""
+        b, m = self.buf, self.model
+        v = v_log_scales if (v_log_scales is None or isinstance(v_log_scales, int)) else v_log_scales.data_ptr()
+        (check or self._ck)(nat.lib().gs_scale_reg(self._st(), self.N, _p(m.log_scales), self.max_scale_ratio, self.lambda_scale, _p(b["loss3"]),
+                                        _p(b["scale_reg"]), v), "gs_scale_reg")
 
     def _tail(self, t: int, lrs):
         """What a step enqueues behind its graph (nothing: the single-GPU step is the graph)."""
@@ -837,8 +862,10 @@ class TrainStepGraph:
         self._issue([opt._step, [float(grp["lr"]) for grp, _ in opt._plist], w2c, K, gt, mk, bool(inputs_ready), conv, ready_event, host_src])
         if self.issued % self.check_every == 0:
             self._poll(block=False)
-        return TrainStepGraph._StepOutputs(self, {"render_img": b["render_colors"][0], "loss3": b["loss3"], "batch_radii": b["radii"],
-                                                  "absgrad": b["v_abs"]}, lazy=self.handback == "lazy")
+        outs = {"render_img": b["render_colors"][0], "loss3": b["loss3"], "batch_radii": b["radii"], "absgrad": b["v_abs"]}
+        if self.scale_reg:
+            outs["scale_reg"] = b["scale_reg"][0]   # (0-d, the eager loss dict's "scale_reg")
+        return TrainStepGraph._StepOutputs(self, outs, lazy=self.handback == "lazy")
 
     def _poll(self, block: bool):
         """Reads the device-written status words (plain host memory) and retires the steps known to be applied."""
@@ -907,7 +934,8 @@ class TrainStepGraph:
         return self.buf["loss_ring"][idx]
 
     def report(self) -> Dict[str, Any]:
-        return dict(self.stats, binning=self.binning, probed_isects=self.probed[0], probed_longest_list=self.probed[1],
+        extra = dict(scale_reg=True, max_scale_ratio=self.max_scale_ratio, lambda_scale=self.lambda_scale) if self.scale_reg else {}
+        return dict(self.stats, **extra, binning=self.binning, probed_isects=self.probed[0], probed_longest_list=self.probed[1],
                     probed_coarse_entries=getattr(self, "probed_coarse", (0, 0))[0] if self.binning == "bins" else 0,
                     capacity_isects=self.cap, capacity_tile_list=self.cap_tile, capacity_work_units=self.cap_units,
                     capacity_rows=self.cap_rows, probed_work_units=self.probed_walk[0], probed_rows=self.probed_walk[1],
@@ -998,6 +1026,8 @@ class ViewParallelGraphStep(TrainStepGraph):
                                        _p(b["colors_post"]), self._tpg(), _p(b["cum_tiles"]), _p(b["rows"]), _p(b["row_base"]), _p(b["qmask"]),
                                        seg(0, 3 * N), seg(2, 4 * N), seg(1, 3 * N), seg(3, N), None, None, _p(b["v_abs"]), None, None, None, None,
                                        _p(m.logit_opacities), 1, _p(b["sh_jac"]), _p(b["row_sums"]), seg(4, N), seg(5, N)), "gs_project_bwd")
+            if self.scale_reg:   # each replica adds it (the eager exchange: flat[o:o+n].add_(p.grad)); Adam's 1 / world makes it count once
+                self._scale_reg(seg(1, 3 * N), nat.check)
             w_sum = dist.all_reduce(flat, op=dist.ReduceOp.SUM, group=vp.group, async_op=True)
             vp.collectives += 1
             w_gather.wait()

@@ -586,6 +586,27 @@ int gs_project_bwd_adam(void* stream, int64_t N, int K, int sh_degree, float* pa
                         float* v_means2d_abs, float beta1, float beta2, float eps, const float* hyper_dev, int64_t* applied_dev,
                         float* max_radii, float* grad_norm_accum, float* counts, const float* sh_jac);
 
+/* Scale-ratio regulariser (the reference's use_scale_regularization / max_scale_ratio / lambda_scale): with s = exp(log_scales[n]),
+ *   reg = mean over ALL N Gaussians (visible or not) of  max(max_k s_k / min_k s_k, max_ratio) - max_ratio,
+ * and the loss gains lambda * reg.  Gradient w.r.t. the log-scales as torch autograd forms it in fp32: it passes where the ratio
+ * is >= max_ratio (equality included), tied maxima / minima share their part evenly, upstream lambda * (1 / N).
+ * gs_scale_reg: reg_ws[gs_scale_reg_workspace_floats(N)] f32, 16-byte aligned -- reg_ws[0] = reg, the rest is scratch; loss3
+ *   (optional, {l1, 1 - ssim, total} of gs_l1_ssim_fwd*): loss3[2] += lambda * reg; v_log_scales[N*3] (optional): += the gradient.
+ *   The sum runs in a fixed order without float atomics (replays give the same bits).  Honours the step guard.  N = 0: no launch.
+ * gs_project_bwd_adam_reg: gs_project_bwd_adam with the regulariser's gradient added to every in-range Gaussian's log-scale
+ *   gradient in front of the update (read from the parameters before it); the value comes from gs_scale_reg, called before it
+ *   with v_log_scales = NULL.  Same update, bit for bit, as gs_project_bwd, gs_scale_reg into its v_scales, gs_adam_step_dev. */
+size_t gs_scale_reg_workspace_floats(int64_t N);
+int gs_scale_reg(void* stream, int64_t N, const float* log_scales, float max_ratio, float lambda, float* loss3, float* reg_ws,
+                 float* v_log_scales);
+int gs_project_bwd_adam_reg(void* stream, int64_t N, int K, int sh_degree, float* params, float* exp_avg, float* exp_avg_sq,
+                            const int64_t* offsets_host, const float* viewmats, const float* Ks, int width, int height, float eps2d,
+                            float near_plane, float far_plane, const int32_t* radii, const float* colors_post,
+                            const int32_t* tiles_per_gauss, const int32_t* cum_tiles, const float* rows, const int32_t* row_base,
+                            const uint8_t* qmask, float* v_means2d_abs, float beta1, float beta2, float eps, const float* hyper_dev,
+                            int64_t* applied_dev, float* max_radii, float* grad_norm_accum, float* counts, const float* sh_jac,
+                            float max_ratio, float lambda);
+
 /* Row e: this rank's contribution to the SUM all-reduce of the view-parallel step in one pass: the four
  * geometry gradients and this view's two additive statistics (|absgrad|_2 * max_hw, visibility count)
  * packed into flat = [means 3N | log_scales 3N | quats 4N | logit_opacities N | grad_norm N | count N],
