@@ -151,10 +151,9 @@ constexpr float kDoneScale = 18446744073709551616.f;   // 2^64
 constexpr float kDoneInv = 5.421010862427522e-20f;      // 2^-64
 __device__ __forceinline__ bool px_live(float T) { return T <= 1.f; }
 __device__ __forceinline__ float px_final_T(float T) { return T > 2.f ? T * kDoneInv : T; }
-__device__ __forceinline__ void blend_pair(const float alpha, const bool ok, const float r,
-                                           const float g, const float b, float& T, float& cr,
-                                           float& cg, float& cb) {
-    const float am = ok ? alpha : 0.f;
+// blend_masked: the same with the alpha already masked (am = ok ? alpha : 0).
+__device__ __forceinline__ void blend_masked(const float am, const float r, const float g, const float b, float& T, float& cr,
+                                             float& cg, float& cb) {
     float w = am * T;
     float Tn = fmaf(-am, T, T);   // explicit: fwd and bwd must round identically
     const bool stop = Tn <= kTMin;
@@ -165,10 +164,14 @@ __device__ __forceinline__ void blend_pair(const float alpha, const bool ok, con
     cr = fmaf(r, w, cr); cg = fmaf(g, w, cg); cb = fmaf(b, w, cb);
     T = Tn;
 }
+__device__ __forceinline__ void blend_pair(const float alpha, const bool ok, const float r,
+                                           const float g, const float b, float& T, float& cr,
+                                           float& cg, float& cb) {
+    blend_masked(ok ? alpha : 0.f, r, g, b, T, cr, cg, cb);
+}
 // The same pair with a fourth colour channel (gs_blend_fwd_ch, channels = 4): channels 0..2 round exactly as above.
-__device__ __forceinline__ void blend_pair4(const float alpha, const bool ok, const float r, const float g, const float b,
-                                            const float c3, float& T, float& cr, float& cg, float& cb, float& ca) {
-    const float am = ok ? alpha : 0.f;
+__device__ __forceinline__ void blend_masked4(const float am, const float r, const float g, const float b, const float c3, float& T,
+                                              float& cr, float& cg, float& cb, float& ca) {
     float w = am * T;
     float Tn = fmaf(-am, T, T);
     const bool stop = Tn <= kTMin;
@@ -179,8 +182,13 @@ __device__ __forceinline__ void blend_pair4(const float alpha, const bool ok, co
     cr = fmaf(r, w, cr); cg = fmaf(g, w, cg); cb = fmaf(b, w, cb); ca = fmaf(c3, w, ca);
     T = Tn;
 }
+__device__ __forceinline__ void blend_pair4(const float alpha, const bool ok, const float r, const float g, const float b,
+                                            const float c3, float& T, float& cr, float& cg, float& cb, float& ca) {
+    blend_masked4(ok ? alpha : 0.f, r, g, b, c3, T, cr, cg, cb, ca);
+}
 
-// The training instantiation is held to 5 waves / SIMD (the 8160 tile-waves of a 1080p frame then run in 1.6 rounds); held
+// The training instantiation is held to at least 5 waves / SIMD (the 8160 tile-waves of a 1080p frame then run in 1.6 rounds;
+// round 7: with the unit storage words in LDS and the tile index wave-uniform it needs 72-76 VGPRs and runs 6-7); held
 // to 80 VGPRs (5 spilled to scratch) it keeps 6 resident and is 2-3 % faster back to back -- but a kernel
 // that needs SCRATCH makes the runtime (re-)provision scratch memory for the queue it is launched on: once another
 // stream of the process had run the captured step, every eager launch of this kernel on the caller's stream stalled 0.5-2 ms
@@ -235,9 +243,17 @@ __device__ __forceinline__ void blend_fwd_body(const BlendFwdArgs& a, float* __r
     static_assert(NC >= 1 && NC <= 4 && (NC == 3 || ROUND == 0), "channels 1..4; depth rounds with 3 channels only");
     __shared__ float4 srec_all[WAVES][GS_BUCKET * 3];
     __shared__ int2 ulog_all[CKPT ? WAVES : 1][CKPT ? kUnitLog : 1];
+    __shared__ int uring_all[CKPT ? WAVES : 1][CKPT ? 16 : 1];
     float4* srec = srec_all[threadIdx.x >> 6];
     int2* ulog = ulog_all[CKPT ? (threadIdx.x >> 6) : 0];
-    const int ti = (int)blockIdx.x * WAVES + (int)(threadIdx.x >> 6);
+    // storage of the work units a bucket's sublist entries can fall into, by quadrant and unit index modulo 4 (a bucket adds at
+    // most 64 entries: they fall into the part-filled unit and at most two opened behind it).  In LDS, written by the unit opens
+    // and read by the sublist stores at the end of the bucket: kept in registers, the twelve words and their upkeep in every
+    // unit open held the training walk at 96 VGPRs.
+    int* uring = uring_all[CKPT ? (threadIdx.x >> 6) : 0];
+    // (wave-uniform; said so for the training walk, whose storage bookkeeping then stays in scalar registers)
+    const int ti = CKPT ? __builtin_amdgcn_readfirstlane((int)blockIdx.x * WAVES + (int)(threadIdx.x >> 6))
+                        : (int)blockIdx.x * WAVES + (int)(threadIdx.x >> 6);
     if (ti >= a.C * a.tiles) return;   // wave-uniform
     if (CKPT ? a.walk[kWalkSkip] != 0 : guard_tripped(a.guard)) return;   // (training: the guard at the start of the call, qmask_clear_kernel)
     if (ROUND == 2 && a.rblk[GS_ROUND_LIVE] == 0) return;   // the front round finished every tile
@@ -259,10 +275,8 @@ __device__ __forceinline__ void blend_fwd_body(const BlendFwdArgs& a, float* __r
     float T[4], cr[4], cg[4], cb[4];   // T <= 1: live; T > 2^32: finished, T * 2^-64 final (blend_pair)
     float ca[4];                       // (NC = 4: the fourth channel)
     int cnt[4] = {0, 0, 0, 0};   // wave-uniform sublist lengths
-    // storage of the work units a bucket's sublist entries can fall into (wave-uniform): [k][0] the unit that holds position
-    // cnt[k] at the start of the bucket (carried over when it is part-filled), [k][1..2] the units opened behind it
-    int us[4][3] = {{0, 0, 0}, {0, 0, 0}, {0, 0, 0}, {0, 0, 0}};
     int pool_next = 0, pool_left = 0, log_n = 0;   // this tile's chunk of storage units; unpublished work units in `ulog`
+    int room[4] = {0, 0, 0, 0};   // wave-uniform: free positions of the unit that holds a sublist's last entry (0: the next opens one)
     // the storage range this tile draws from: 1/32 of [0, cap_units) with a counter in a cache line of its own (launch slots
     // take the ranges in turn: the tiles come longest list first, every range sees the same mix)
     const int range_len = (a.cap_units / GS_WALK_RANGES) & ~(kChunk - 1), range0 = (ti & (GS_WALK_RANGES - 1)) * range_len;
@@ -284,8 +298,13 @@ __device__ __forceinline__ void blend_fwd_body(const BlendFwdArgs& a, float* __r
             const int4 rc = a.trec[2 * (size_t)t], ru = a.trec[2 * (size_t)t + 1];
             cnt[0] = __builtin_amdgcn_readfirstlane(rc.x); cnt[1] = __builtin_amdgcn_readfirstlane(rc.y);
             cnt[2] = __builtin_amdgcn_readfirstlane(rc.z); cnt[3] = __builtin_amdgcn_readfirstlane(rc.w);
-            us[0][0] = __builtin_amdgcn_readfirstlane(ru.x); us[1][0] = __builtin_amdgcn_readfirstlane(ru.y);
-            us[2][0] = __builtin_amdgcn_readfirstlane(ru.z); us[3][0] = __builtin_amdgcn_readfirstlane(ru.w);
+            // the unit that holds a sublist's last entry (part-filled or not: a full one is never written again)
+            const int ru4[4] = {ru.x, ru.y, ru.z, ru.w};
+#pragma unroll
+            for (int k = 0; k < 4; ++k) {
+                room[k] = -cnt[k] & (kUnit - 1);
+                if (lane == 0 && cnt[k] > 0) uring[4 * k + (((cnt[k] - 1) / kUnit) & 3)] = ru4[k];
+            }
         }
     }
     // pixel-centre bounds of the four quadrants
@@ -372,43 +391,50 @@ __device__ __forceinline__ void blend_fwd_body(const BlendFwdArgs& a, float* __r
                     const float sigma = fmaf(dy, fmaf(q1.x, dy, q0.w * dx), q0.z * dx * dx);
                     const float alpha = fminf(kAlphaMax, op * fast_exp2(-sigma));
                     const bool ok = px_live(T[k]) && sigma >= 0.f && alpha >= kAlphaMin;
+                    const float am = ok ? alpha : 0.f;
                     if (CKPT) {
-                        if (__builtin_amdgcn_ballot_w64(ok) == 0ull) continue;   // no pixel of the quadrant takes it: nothing to blend, nothing to list
-                        // the sublist entry that opens a new work unit takes a storage unit and saves the pixel states before it
-                        const int pos = cnt[k] + (int)__popcll(cq[k]);
-                        if ((pos & (kUnit - 1)) == 0) {
-                            if (pool_left == 0) {
-                                int base = 0;
-                                if (lane == 0) base = atomicAdd(range_ctr, kChunk);
-                                base = __builtin_amdgcn_readfirstlane(base);
-                                if (base + kChunk > range_len) {
-                                    // out of storage: the call is void (flag; every kernel behind it is a no-op under the step guard,
-                                    // the caller re-sizes from the counters, which keep counting) -- its stores land in the range's
-                                    // first chunk
-                                    // (front round: the step guard learns of it behind the back round -- row_chunk_scan_kernel --, whose
-                                    //  list stages run under the same guard and must not find it tripped by the walk in between)
-                                    if (lane == 0) {
-                                        atomicOr(a.walk + kWalkFlags, GS_FLAG_UNITS);
-                                        if (ROUND != 1 && a.flags) atomicOr(a.flags, (unsigned long long)GS_FLAG_UNITS);
+                        // An entry no pixel of the quadrant takes stays out of the sublist and is blended all the same (no
+                        // `continue`: an all-false `ok` leaves every state bit for bit as it is, as the inference walk relies on).
+                        // A taken entry opens a work unit only while the quadrant's current unit is full: `room` counts down to
+                        // that instead of a popcount of the taken mask per pair, and the open path lies behind a not-taken branch.
+                        if (__builtin_amdgcn_ballot_w64(ok) != 0ull) {
+                            if (__builtin_expect(room[k] == 0, 0)) {
+                                // the sublist entry that opens a new work unit takes a storage unit and saves the pixel states before it
+                                const int pos = cnt[k] + (int)__popcll(cq[k]);
+                                if (pool_left == 0) {
+                                    int base = 0;
+                                    if (lane == 0) base = atomicAdd(range_ctr, kChunk);
+                                    base = __builtin_amdgcn_readfirstlane(base);
+                                    if (base + kChunk > range_len) {
+                                        // out of storage: the call is void (flag; every kernel behind it is a no-op under the step guard,
+                                        // the caller re-sizes from the counters, which keep counting) -- its stores land in the range's
+                                        // first chunk
+                                        // (front round: the step guard learns of it behind the back round -- row_chunk_scan_kernel --, whose
+                                        //  list stages run under the same guard and must not find it tripped by the walk in between)
+                                        if (lane == 0) {
+                                            atomicOr(a.walk + kWalkFlags, GS_FLAG_UNITS);
+                                            if (ROUND != 1 && a.flags) atomicOr(a.flags, (unsigned long long)GS_FLAG_UNITS);
+                                        }
+                                        base = 0;
                                     }
-                                    base = 0;
+                                    pool_next = range0 + base; pool_left = kChunk;
                                 }
-                                pool_next = range0 + base; pool_left = kChunk;
+                                const int su = pool_next++;
+                                --pool_left;
+                                a.ckpt[(size_t)su * 64 + lane] = make_float4(px_live(T[k]) ? T[k] : -1.f, cr[k], cg[k], cb[k]);   // (the backward's "finished" is T < 0)
+                                if constexpr (NC == 4) ckpt_ext[(size_t)su * 64 + lane] = ca[k];
+                                if (lane == 0) ulog[log_n] = make_int2(su, (pos / kUnit) * 4 + k);
+                                ++log_n;
+                                if (lane == 0) uring[4 * k + ((pos / kUnit) & 3)] = su;
+                                room[k] = kUnit;
                             }
-                            const int su = pool_next++;
-                            --pool_left;
-                            a.ckpt[(size_t)su * 64 + lane] = make_float4(px_live(T[k]) ? T[k] : -1.f, cr[k], cg[k], cb[k]);   // (the backward's "finished" is T < 0)
-                            if constexpr (NC == 4) ckpt_ext[(size_t)su * 64 + lane] = ca[k];
-                            if (lane == 0) ulog[log_n] = make_int2(su, (pos / kUnit) * 4 + k);
-                            ++log_n;
-                            const int w = pos / kUnit - cnt[k] / kUnit;
-                            if (w == 0) us[k][0] = su; else if (w == 1) us[k][1] = su; else us[k][2] = su;
+                            --room[k];
+                            cq[k] |= 1ull << j;
                         }
-                        cq[k] |= 1ull << j;
                     }
                     GS_IF_CHECK(const float T_before = T[k];)
-                    if constexpr (NC == 4) blend_pair4(alpha, ok, r, g, bl, q2.w, T[k], cr[k], cg[k], cb[k], ca[k]);
-                    else blend_pair(alpha, ok, r, g, bl, T[k], cr[k], cg[k], cb[k]);
+                    if constexpr (NC == 4) blend_masked4(am, r, g, bl, q2.w, T[k], cr[k], cg[k], cb[k], ca[k]);
+                    else blend_masked(am, r, g, bl, T[k], cr[k], cg[k], cb[k]);
                     GS_IF_CHECK(taken[k] += T[k] < T_before ? 1 : 0;)   // (blended: T shrinks and stays live; stop rule: T jumps beyond 2^32; not taken: unchanged)
                 }
             }
@@ -420,16 +446,11 @@ __device__ __forceinline__ void blend_fwd_body(const BlendFwdArgs& a, float* __r
                 const int n_new = (int)__popcll(cq[k]);
                 if ((cq[k] >> lane) & 1) {
                     const int p = cnt[k] + (int)__popcll(cq[k] & lt_mask);
-                    const int w = p / kUnit - cnt[k] / kUnit;
-                    const int su = w == 0 ? us[k][0] : (w == 1 ? us[k][1] : us[k][2]);
+                    const int su = uring[4 * k + ((p / kUnit) & 3)];
                     a.qlist[(size_t)su * kUnit + (p & (kUnit - 1))] = make_int2(my_gid, my_slot);
                     mybits |= 1 << k;
                 }
-                if (n_new) {   // (wave-uniform) the unit the next bucket's first entry falls into, if it is part-filled
-                    const int w = (cnt[k] + n_new - 1) / kUnit - cnt[k] / kUnit;
-                    us[k][0] = w == 0 ? us[k][0] : (w == 1 ? us[k][1] : us[k][2]);
-                    cnt[k] += n_new;
-                }
+                cnt[k] += n_new;
             }
             // a scattered one-byte store leaves L2 as a 32-byte partial write (profiles/r03_traffic_calibration.json): only the
             // entries some quadrant takes store their mask, the others keep the clear's zero
@@ -454,7 +475,10 @@ __device__ __forceinline__ void blend_fwd_body(const BlendFwdArgs& a, float* __r
             for (int k = 0; k < 4; ++k) a.tstate[((size_t)t * 4 + k) * 64 + lane] = make_float4(T[k], cr[k], cg[k], cb[k]);
             if (CKPT && lane == 0) {
                 a.trec[2 * (size_t)t] = make_int4(cnt[0], cnt[1], cnt[2], cnt[3]);
-                a.trec[2 * (size_t)t + 1] = make_int4(us[0][0], us[1][0], us[2][0], us[3][0]);
+                int ru[4];
+#pragma unroll
+                for (int k = 0; k < 4; ++k) ru[k] = cnt[k] > 0 ? uring[4 * k + (((cnt[k] - 1) / kUnit) & 3)] : 0;
+                a.trec[2 * (size_t)t + 1] = make_int4(ru[0], ru[1], ru[2], ru[3]);
             }
         }
     }
@@ -485,8 +509,8 @@ template <bool CKPT, int WAVES, int ROUND>
 __global__ __launch_bounds__(64 * WAVES) GS_FWD_ATTR void blend_fwd_kernel(const BlendFwdArgs a) {
     blend_fwd_body<CKPT, WAVES, ROUND, 3>(a, nullptr);
 }
-// channels != 3 (gs_blend_fwd_ch; one list per tile).  The four-channel training form needs more than the 102 VGPRs of five waves
-// per SIMD: it is held to four (no scratch, see above).
+// channels != 3 (gs_blend_fwd_ch; one list per tile).  The four-channel training form is held to at least four waves per SIMD
+// (no scratch, see above); it needs 82 VGPRs and runs five.
 template <bool CKPT, int WAVES, int NC>
 __global__ __launch_bounds__(64 * WAVES) __attribute__((amdgpu_waves_per_eu(CKPT ? (NC == 4 ? 4 : 5) : 1, 8))) void chan_fwd_kernel(const BlendFwdArgs a, float* ckpt_ext) {
     blend_fwd_body<CKPT, WAVES, 0, NC>(a, ckpt_ext);
