@@ -22,9 +22,6 @@
 // The "slot" carried in the key's low word is the index of this intersection's gradient row
 // (cum_tiles[f] + k): rows of one Gaussian are contiguous, which lets the backward reduce them
 // with plain coalesced loads instead of float atomics.
-#include <map>
-#include <mutex>
-#include <utility>
 
 #include "gs_common.h"
 
@@ -1155,24 +1152,6 @@ static int list_round(int64_t*& rblk) {
 
 extern "C" size_t gs_bin_workspace_bytes(int C, int64_t N, int tile_w, int tile_h) {
     return bin_layout(C, N, tile_w * tile_h).total;
-}
-
-// (the attribute is raised once per kernel and size: nothing but launches reaches the stream afterwards, which
-//  keeps a warmed-up pipeline capturable into a hipGraph)
-static int ensure_lds(const void* fn, size_t bytes) {
-    if (bytes > 64 * 1024) {
-        static std::mutex mu;
-        static std::map<std::pair<int, const void*>, size_t> done;
-        int dev = 0;
-        GS_HIP_CHECK(hipGetDevice(&dev));
-        std::lock_guard<std::mutex> lock(mu);
-        size_t& have = done[{dev, fn}];
-        if (have < bytes) {
-            GS_HIP_CHECK(hipFuncSetAttribute(fn, hipFuncAttributeMaxDynamicSharedMemorySize, (int)bytes));
-            have = bytes;
-        }
-    }
-    return GS_OK;
 }
 
 #define GS_SORT1K_THREADS 256

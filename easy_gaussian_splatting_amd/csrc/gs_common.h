@@ -5,6 +5,10 @@
 #include <stdio.h>
 #include <string.h>
 
+#include <map>
+#include <mutex>
+#include <utility>
+
 #include "../../include/gs_raster.h"
 
 namespace gs {
@@ -29,6 +33,24 @@ void set_error(const char* fmt, ...);
             return GS_ERR_HIP;                                                               \
         }                                                                                    \
     } while (0)
+
+// (the attribute is raised once per kernel and size: nothing but launches reaches the stream afterwards, which
+//  keeps a warmed-up pipeline capturable into a hipGraph)
+inline int ensure_lds(const void* fn, size_t bytes) {
+    if (bytes > 64 * 1024) {
+        static std::mutex mu;
+        static std::map<std::pair<int, const void*>, size_t> done;
+        int dev = 0;
+        GS_HIP_CHECK(hipGetDevice(&dev));
+        std::lock_guard<std::mutex> lock(mu);
+        size_t& have = done[{dev, fn}];
+        if (have < bytes) {
+            GS_HIP_CHECK(hipFuncSetAttribute(fn, hipFuncAttributeMaxDynamicSharedMemorySize, (int)bytes));
+            have = bytes;
+        }
+    }
+    return GS_OK;
+}
 
 #define GS_REQUIRE(cond, msg)                                                                \
     do {                                                                                     \

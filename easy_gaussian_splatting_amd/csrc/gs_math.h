@@ -245,6 +245,10 @@ constexpr float kC1 = 0.4886025119029199f;
 constexpr float kC20 = 1.0925484305920792f, kC21 = 0.31539156525252005f, kC22 = 0.5462742152960396f;
 constexpr float kC30 = 0.5900435899266435f, kC31 = 2.890611442640554f, kC32 = 0.4570457994644658f,
                 kC33 = 0.3731763325901154f, kC34 = 1.445305721320277f;
+constexpr float kC40 = 2.5033429417967046f, kC41 = -1.7701307697799304f, kC42 = 0.9461746957575601f,
+                kC43 = -0.6690465435572892f, kC44 = 0.10578554691520431f, kC45 = -0.6690465435572892f,
+                kC46 = 0.47308734787878004f, kC47 = -1.7701307697799304f, kC48 = 0.6258357354491761f;
+constexpr int kMaxShCoeffs = 25;   // (degree 4)
 
 GS_HD void sh_basis(int degree, float x, float y, float z, float* Y) {
     Y[0] = kC0;
@@ -259,6 +263,14 @@ GS_HD void sh_basis(int degree, float x, float y, float z, float* Y) {
     Y[11] = -kC32 * y * (4.f * zz - xx - yy); Y[12] = kC33 * z * (2.f * zz - 3.f * xx - 3.f * yy);
     Y[13] = -kC32 * x * (4.f * zz - xx - yy); Y[14] = kC34 * z * (xx - yy);
     Y[15] = -kC30 * x * (xx - 3.f * yy);
+    if (degree < 4) return;
+    // degree 4: gsplat's band (Sloan's recurrence) in closed form, signs of the C4 table included
+    const float z7m1 = 7.f * zz - 1.f, z7m3 = 7.f * zz - 3.f;
+    Y[16] = kC40 * x * y * (xx - yy); Y[17] = kC41 * y * z * (3.f * xx - yy);
+    Y[18] = kC42 * x * y * z7m1; Y[19] = kC43 * y * z * z7m3;
+    Y[20] = kC44 * (zz * (35.f * zz - 30.f) + 3.f); Y[21] = kC45 * x * z * z7m3;
+    Y[22] = kC46 * (xx - yy) * z7m1; Y[23] = kC47 * x * z * (xx - 3.f * yy);
+    Y[24] = kC48 * (xx * (xx - 3.f * yy) - yy * (3.f * xx - yy));
 }
 
 // Unit view direction from the camera centre to the Gaussian; returns |d| (0 => degenerate).
@@ -273,7 +285,7 @@ GS_HD float view_dir(const float* mean, const Camera& cam, float& ux, float& uy,
 // Appendix A.2: rgb = max(sum_k Y_k sh[k] + 0.5, 0).  `sh` points at this Gaussian's [K,3] block
 // (any float pointer: global memory or an LDS staging row).
 GS_HD void sh_to_rgb(int degree, const float* sh, float ux, float uy, float uz, float* rgb) {
-    float Y[16];
+    float Y[kMaxShCoeffs];
     sh_basis(degree, ux, uy, uz, Y);
     const int Ka = (degree + 1) * (degree + 1);
     float r = 0.f, g = 0.f, b = 0.f;
@@ -303,6 +315,19 @@ GS_HD void sh_dir_grad(int degree, const float* d, float x, float y, float z, fl
               + kC33 * (6.f * zz - 3.f * xx - 3.f * yy) * d[12] - 8.f * kC32 * x * z * d[13]
               + kC34 * (xx - yy) * d[14];
     }
+    if (degree >= 4) {   // the partial derivatives of sh_basis's degree-4 polynomials as written there
+        const float xx = x * x, yy = y * y, zz = z * z;
+        const float z7m1 = 7.f * zz - 1.f, z7m3 = 7.f * zz - 3.f, z21m3 = 21.f * zz - 3.f;
+        gx += kC40 * y * (3.f * xx - yy) * d[16] + 6.f * kC41 * x * y * z * d[17] + kC42 * y * z7m1 * d[18]
+              + kC45 * z * z7m3 * d[21] + 2.f * kC46 * x * z7m1 * d[22] + 3.f * kC47 * z * (xx - yy) * d[23]
+              + 4.f * kC48 * x * (xx - 3.f * yy) * d[24];
+        gy += kC40 * x * (xx - 3.f * yy) * d[16] + 3.f * kC41 * z * (xx - yy) * d[17] + kC42 * x * z7m1 * d[18]
+              + kC43 * z * z7m3 * d[19] - 2.f * kC46 * y * z7m1 * d[22] - 6.f * kC47 * x * y * z * d[23]
+              + 4.f * kC48 * y * (yy - 3.f * xx) * d[24];
+        gz += kC41 * y * (3.f * xx - yy) * d[17] + 14.f * kC42 * x * y * z * d[18] + kC43 * y * z21m3 * d[19]
+              + kC44 * z * (140.f * zz - 60.f) * d[20] + kC45 * x * z21m3 * d[21] + 14.f * kC46 * (xx - yy) * z * d[22]
+              + kC47 * x * (xx - 3.f * yy) * d[23];
+    }
 }
 
 // v_mean += d(unit direction)/d(mean)^T g   (direction = (mean - camera centre) / dnorm)
@@ -319,10 +344,10 @@ GS_HD void sh_vjp(int degree, const float* sh, const float* rgb, const float* v_
     const float vr = rgb[0] > 0.f ? v_rgb[0] : 0.f;
     const float vg = rgb[1] > 0.f ? v_rgb[1] : 0.f;
     const float vb = rgb[2] > 0.f ? v_rgb[2] : 0.f;
-    float Y[16];
+    float Y[kMaxShCoeffs];
     sh_basis(degree, ux, uy, uz, Y);
     const int Ka = (degree + 1) * (degree + 1);
-    float d[16];  // d[k] = sh[k] . v_pre
+    float d[kMaxShCoeffs];  // d[k] = sh[k] . v_pre
     for (int k = 0; k < Ka; ++k) {
         d[k] = sh[3 * k] * vr + sh[3 * k + 1] * vg + sh[3 * k + 2] * vb;
         if (accumulate) {
@@ -342,7 +367,7 @@ GS_HD void sh_vjp(int degree, const float* sh, const float* rgb, const float* v_
 GS_HD void sh_dir_jacobian(int degree, const float* sh, float ux, float uy, float uz, float* G) {
     const int Ka = (degree + 1) * (degree + 1);
     for (int c = 0; c < 3; ++c) {
-        float d[16];
+        float d[kMaxShCoeffs];
         for (int k = 0; k < Ka; ++k) d[k] = sh[3 * k + c];
         float gx, gy, gz;
         sh_dir_grad(degree, d, ux, uy, uz, gx, gy, gz);
@@ -357,7 +382,7 @@ GS_HD void sh_vjp_jac(int degree, const float* G, const float* rgb, const float*
     const float vr = rgb[0] > 0.f ? v_rgb[0] : 0.f;
     const float vg = rgb[1] > 0.f ? v_rgb[1] : 0.f;
     const float vb = rgb[2] > 0.f ? v_rgb[2] : 0.f;
-    float Y[16];
+    float Y[kMaxShCoeffs];
     sh_basis(degree, ux, uy, uz, Y);
     const int Ka = (degree + 1) * (degree + 1);
     for (int k = 0; k < Ka; ++k) { v_sh[3 * k] = Y[k] * vr; v_sh[3 * k + 1] = Y[k] * vg; v_sh[3 * k + 2] = Y[k] * vb; }

@@ -3,7 +3,7 @@
 //                        also leaves d colour / d view direction (sh_jac), so that the backward reads no coefficient
 //   project_bwd_kernel : gradient-row reduction (compact rows, a row per lane: row_sum_wave) + SH-bwd + P-bwd fused, no atomics;
 //                        <DEG, true>: Adam and update_statistics applied in the same pass (gs_project_bwd_adam)
-// The [N,K,3] SH block (192 B per Gaussian at SH3) is moved through LDS with coalesced 16-byte accesses and read per
+// The [N,K,3] SH block (192 B per Gaussian at SH3, 300 B at SH4) is moved through LDS with coalesced 16-byte accesses and read per
 // thread at an odd row stride (3K+1 dwords) so the per-thread walk over its own row is bank-conflict free.  The
 // geometry half of the forward is VALU-bound (the fp64 chain), the rest HBM streams and gathers.
 #include "gs_common.h"
@@ -132,7 +132,7 @@ __device__ __forceinline__ void stage_sh_rows_split(const float* __restrict__ sh
     const int total = rows * rest_f;
     if (kr == rest_f) {  // whole rows needed: one contiguous, 16-byte aligned stream for the block
         const float4* src4 = reinterpret_cast<const float4*>(src);
-        constexpr int kMaxQ = 12;   // <= 45 floats per Gaussian -> at most 12 quads per thread
+        constexpr int kMaxQ = KC == 25 ? 18 : 12;   // <= 45 floats per Gaussian -> at most 12 quads per thread (72 at SH4: 18)
         const int total4 = total >> 2;
         float4 v[kMaxQ];
         bool ld[kMaxQ];
@@ -330,10 +330,12 @@ __global__ __launch_bounds__(kProjThreads) void project_fwd_kernel(const ProjFwd
             if (STAGE == 0 && DEG == 3 && prefetch_sh) {
                 sh_rows_commit(pf, a.sh_rest, n0, rows, tile);
             } else if (a.sh_rest) {
-                if (a.K == 16) stage_sh_rows_split<16>(a.colors_in, a.sh_rest, n0, rows, 16, ka3, vis_s, tile);
+                if (DEG == 4) stage_sh_rows_split<25>(a.colors_in, a.sh_rest, n0, rows, 25, ka3, vis_s, tile);   // (SH4: K = 25)
+                else if (a.K == 16) stage_sh_rows_split<16>(a.colors_in, a.sh_rest, n0, rows, 16, ka3, vis_s, tile);
                 else stage_sh_rows_split<0>(a.colors_in, a.sh_rest, n0, rows, a.K, ka3, vis_s, tile);
             } else {
-                if (a.K == 16) stage_sh_rows<16>(a.colors_in, n0, rows, 16, ka3, vis_s, tile);
+                if (DEG == 4) stage_sh_rows<25>(a.colors_in, n0, rows, 25, ka3, vis_s, tile);
+                else if (a.K == 16) stage_sh_rows<16>(a.colors_in, n0, rows, 16, ka3, vis_s, tile);
                 else stage_sh_rows<0>(a.colors_in, n0, rows, a.K, ka3, vis_s, tile);
             }
             __syncthreads();
@@ -802,10 +804,12 @@ __global__ __launch_bounds__(kProjThreads) void project_bwd_kernel(const ProjBwd
         const int rows = (int)min((int64_t)kProjThreads, a.N - n0);
         if (!use_jac) {
             if (a.sh_rest) {
-                if (a.K == 16) stage_sh_rows_split<16>(a.colors_in, a.sh_rest, n0, rows, 16, ka3, vis_s, tile);
+                if (DEG == 4) stage_sh_rows_split<25>(a.colors_in, a.sh_rest, n0, rows, 25, ka3, vis_s, tile);   // (SH4: K = 25)
+                else if (a.K == 16) stage_sh_rows_split<16>(a.colors_in, a.sh_rest, n0, rows, 16, ka3, vis_s, tile);
                 else stage_sh_rows_split<0>(a.colors_in, a.sh_rest, n0, rows, a.K, ka3, vis_s, tile);
             } else {
-                if (a.K == 16) stage_sh_rows<16>(a.colors_in, n0, rows, 16, ka3, vis_s, tile);
+                if (DEG == 4) stage_sh_rows<25>(a.colors_in, n0, rows, 25, ka3, vis_s, tile);
+                else if (a.K == 16) stage_sh_rows<16>(a.colors_in, n0, rows, 16, ka3, vis_s, tile);
                 else stage_sh_rows<0>(a.colors_in, n0, rows, a.K, ka3, vis_s, tile);
             }
             __syncthreads();
@@ -827,11 +831,13 @@ __global__ __launch_bounds__(kProjThreads) void project_bwd_kernel(const ProjBwd
         }
         if (ADAM) {
             __syncthreads();
-            if (a.K == 16) adam_sh_tile<16>(tile, rows, 16, n0, a);
+            if (DEG == 4) adam_sh_tile<25>(tile, rows, 25, n0, a);
+            else if (a.K == 16) adam_sh_tile<16>(tile, rows, 16, n0, a);
             else adam_sh_tile<0>(tile, rows, a.K, n0, a);
         } else if (a.v_colors) {  // NULL: the caller rebuilds the SH gradients from v_colors_pre (gs_sh_grad_views)
             __syncthreads();
-            write_sh_tile(tile, rows, a.K, n0, a.v_colors, a.v_sh_rest, a.accumulate);
+            if (DEG == 4) write_sh_tile_k<25>(tile, rows, 25, n0, a.v_colors, a.v_sh_rest, a.accumulate);
+            else write_sh_tile(tile, rows, a.K, n0, a.v_colors, a.v_sh_rest, a.accumulate);
         }
     } else if (in_range) {
         if (a.colors_per_camera) {
@@ -990,7 +996,7 @@ __global__ __launch_bounds__(kProjThreads) void sh_grad_views_kernel(const ShGra
             if (vr == 0.f && vg == 0.f && vb == 0.f) continue;   // not visible in view r (x + 0 is exact)
             Camera cam;
             cam.pos[0] = cam_pos[3 * r]; cam.pos[1] = cam_pos[3 * r + 1]; cam.pos[2] = cam_pos[3 * r + 2];
-            float ux, uy, uz, Y[16];
+            float ux, uy, uz, Y[kMaxShCoeffs];
             view_dir(mean, cam, ux, uy, uz);
             sh_basis(DEG, ux, uy, uz, Y);
 #pragma unroll
@@ -1007,8 +1013,11 @@ __global__ __launch_bounds__(kProjThreads) void sh_grad_views_kernel(const ShGra
     __syncthreads();
     const int rows = (int)min((int64_t)kProjThreads, a.N - n0);
     if (ADAM) {
-        if (a.K == 16) adam_sh_tile<16>(tile, rows, 16, n0, a);
+        if (DEG == 4) adam_sh_tile<25>(tile, rows, 25, n0, a);
+        else if (a.K == 16) adam_sh_tile<16>(tile, rows, 16, n0, a);
         else adam_sh_tile<0>(tile, rows, a.K, n0, a);
+    } else if (DEG == 4) {
+        write_sh_tile_k<25>(tile, rows, 25, n0, a.v_colors, a.v_sh_rest, false);
     } else {
         write_sh_tile(tile, rows, a.K, n0, a.v_colors, a.v_sh_rest, false);
     }
@@ -1067,17 +1076,22 @@ __global__ __launch_bounds__(256) void row_sums_kernel(const RowSumsArgs a) {
 
 using namespace gs;
 
+// Above K = 20 the SH tile takes more than 64 KB of LDS (77 KB at K = 25: two blocks per CU instead of three); the kernel's
+// dynamic-LDS limit is raised before its first such launch (ensure_lds: once per kernel, a no-op at or below 64 KB)
+#define GS_LDS(fn) if (int rc_ = ensure_lds((const void*)fn, lds)) return rc_
+
 static int sh_views_launch(hipStream_t st, int sh_degree, bool adam, const ShGradArgs& a) {
     dim3 grid((unsigned)((a.N + kProjThreads - 1) / kProjThreads));
     const size_t lds = sizeof(float) * (kMaxViews * 3 + (size_t)kProjThreads * (3 * a.K + 1));
 #define GS_SHV(D)                                                                                           \
-    if (adam) hipLaunchKernelGGL((sh_grad_views_kernel<D, true>), grid, dim3(kProjThreads), lds, st, a);    \
-    else hipLaunchKernelGGL((sh_grad_views_kernel<D, false>), grid, dim3(kProjThreads), lds, st, a)
+    if (adam) { GS_LDS((sh_grad_views_kernel<D, true>)); hipLaunchKernelGGL((sh_grad_views_kernel<D, true>), grid, dim3(kProjThreads), lds, st, a); }  \
+    else { GS_LDS((sh_grad_views_kernel<D, false>)); hipLaunchKernelGGL((sh_grad_views_kernel<D, false>), grid, dim3(kProjThreads), lds, st, a); }
     switch (sh_degree) {
         case 0: GS_SHV(0); break;
         case 1: GS_SHV(1); break;
         case 2: GS_SHV(2); break;
-        default: GS_SHV(3); break;
+        case 3: GS_SHV(3); break;
+        default: GS_SHV(4); break;
     }
 #undef GS_SHV
     GS_LAUNCH_CHECK("sh_grad_views_kernel");
@@ -1088,8 +1102,8 @@ extern "C" int gs_sh_grad_views(void* stream, int R, int64_t N, int K, int sh_de
                                 const float* viewmats, const float* v_colors_pre, float* v_colors,
                                 float* v_sh_rest) {
     GS_REQUIRE(R >= 1 && R <= kMaxViews, "1..64 views");
-    GS_REQUIRE(N >= 0 && sh_degree >= 0 && sh_degree <= 3, "N >= 0 and sh_degree in 0..3");
-    GS_REQUIRE(K >= (sh_degree + 1) * (sh_degree + 1) && K <= 16, "K must hold (sh_degree+1)^2 coefficients and be <= 16");
+    GS_REQUIRE(N >= 0 && sh_degree >= 0 && sh_degree <= 4, "N >= 0 and sh_degree in 0..4");
+    GS_REQUIRE(K >= (sh_degree + 1) * (sh_degree + 1) && K <= 25, "K must hold (sh_degree+1)^2 coefficients and be <= 25");
     if (N == 0) return GS_OK;
     GS_REQUIRE(means && viewmats && v_colors_pre && v_colors, "null pointer");
     ShGradArgs a = {};
@@ -1104,8 +1118,8 @@ extern "C" int gs_sh_adam_views(void* stream, int R, int64_t N, int K, int sh_de
                                 float* sh_rest_exp_avg, float* sh_rest_exp_avg_sq, float lr_sh_0, float lr_sh_rest, float beta1,
                                 float beta2, float eps, int64_t step, float grad_scale, float* max_radii) {
     GS_REQUIRE(R >= 1 && R <= kMaxViews, "1..64 views");
-    GS_REQUIRE(N >= 0 && sh_degree >= 0 && sh_degree <= 3, "N >= 0 and sh_degree in 0..3");
-    GS_REQUIRE(K >= (sh_degree + 1) * (sh_degree + 1) && K <= 16, "K must hold (sh_degree+1)^2 coefficients and be <= 16");
+    GS_REQUIRE(N >= 0 && sh_degree >= 0 && sh_degree <= 4, "N >= 0 and sh_degree in 0..4");
+    GS_REQUIRE(K >= (sh_degree + 1) * (sh_degree + 1) && K <= 25, "K must hold (sh_degree+1)^2 coefficients and be <= 25");
     GS_REQUIRE(step >= 1, "step counts from 1");
     GS_REQUIRE(payload_stride >= 4 * N + 16, "payload_stride must hold [3N colour gradients | N radii | 16 camera floats]");
     if (N == 0) return GS_OK;
@@ -1157,8 +1171,8 @@ extern "C" int gs_project_fwd(void* stream, int C, int64_t N, int K, int sh_degr
                               float* means2d, float* depths, float* conics, float* colors_out, float* rec,
                               uint32_t* bbox, int32_t* tiles_per_gauss, uint32_t* rect_ref, float* sh_jac) {
     GS_REQUIRE(C >= 1 && N >= 0 && width > 0 && height > 0, "C>=1, N>=0, positive image size");
-    GS_REQUIRE(sh_degree <= 3, "sh_degree must be <= 3");
-    GS_REQUIRE(sh_degree < 0 || (K >= (sh_degree + 1) * (sh_degree + 1) && K <= 16), "K must hold (sh_degree+1)^2 coefficients and be <= 16");
+    GS_REQUIRE(sh_degree <= 4, "sh_degree must be <= 4");
+    GS_REQUIRE(sh_degree < 0 || (K >= (sh_degree + 1) * (sh_degree + 1) && K <= 25), "K must hold (sh_degree+1)^2 coefficients and be <= 25");
     GS_REQUIRE((width + GS_TILE - 1) / GS_TILE < 65536 && (height + GS_TILE - 1) / GS_TILE < 65536, "tile grid must fit 16 bits per axis");
     if (N == 0) return GS_OK;
     GS_REQUIRE(means && quats && scales && opacities && colors_in && viewmats && Ks, "null input pointer");
@@ -1179,13 +1193,16 @@ extern "C" int gs_project_fwd(void* stream, int C, int64_t N, int K, int sh_degr
     const size_t lds = proj_lds_bytes(K, sh_degree);
     hipStream_t st = (hipStream_t)stream;
     GS_REQUIRE(stage >= 0 && stage <= 2, "stage: 0 = geometry+colour, 1 = geometry, 2 = colour");
-#define GS_PF(D, S) hipLaunchKernelGGL((project_fwd_kernel<D, S>), grid, dim3(kProjThreads), (S) == 1 ? proj_lds_bytes(K, -1) : lds, st, a)
+#define GS_PF(D, S)                                                                                              \
+    { if ((S) != 1) GS_LDS((project_fwd_kernel<D, S>));                                                          \
+      hipLaunchKernelGGL((project_fwd_kernel<D, S>), grid, dim3(kProjThreads), (S) == 1 ? proj_lds_bytes(K, -1) : lds, st, a); }
 #define GS_PF_DEG(S)                                                      \
     switch (sh_degree) {                                                  \
         case 0: GS_PF(0, S); break;                                       \
         case 1: GS_PF(1, S); break;                                       \
         case 2: GS_PF(2, S); break;                                       \
         case 3: GS_PF(3, S); break;                                       \
+        case 4: GS_PF((S) == 1 ? -1 : 4, S); break;   /* (stage 1: no SH) */ \
         default: GS_PF(-1, S); break;                                     \
     }
     if (stage == 0) { GS_PF_DEG(0) } else if (stage == 1) { GS_PF_DEG(1) } else { GS_PF_DEG(2) }
@@ -1210,8 +1227,8 @@ extern "C" int gs_project_bwd(void* stream, int C, int64_t N, int K, int sh_degr
     GS_REQUIRE(C >= 1 && N >= 0 && width > 0 && height > 0, "C>=1, N>=0, positive image size");
     GS_REQUIRE((stat_grad_norm == nullptr) == (stat_count == nullptr) && (!stat_count || (C == 1 && row_sums)),
                "stat_grad_norm / stat_count: both or neither, single camera, together with row_sums");
-    GS_REQUIRE(sh_degree <= 3, "sh_degree must be <= 3");
-    GS_REQUIRE(sh_degree < 0 || (K >= (sh_degree + 1) * (sh_degree + 1) && K <= 16), "K must hold (sh_degree+1)^2 coefficients and be <= 16");
+    GS_REQUIRE(sh_degree <= 4, "sh_degree must be <= 4");
+    GS_REQUIRE(sh_degree < 0 || (K >= (sh_degree + 1) * (sh_degree + 1) && K <= 25), "K must hold (sh_degree+1)^2 coefficients and be <= 25");
     if (N == 0) return GS_OK;
     GS_REQUIRE(means && quats && scales && colors_in && viewmats && Ks && radii && colors_post && tiles_per_gauss && cum_tiles, "null input pointer");
     GS_REQUIRE(row_sums || (rows && row_base && qmask), "the gradient rows (rows + row_base + qmask) or their sums (row_sums, from gs_row_sums)");
@@ -1246,13 +1263,14 @@ extern "C" int gs_project_bwd(void* stream, int C, int64_t N, int K, int sh_degr
     for (int c = 0; c < C; ++c) {
         a.cam = c; a.accumulate = c > 0;
 #define GS_PB(D)                                                                                                        \
-        if (row_sums) hipLaunchKernelGGL((project_bwd_kernel<D, false, true>), grid, dim3(kProjThreads), lds, st, a);      \
-        else hipLaunchKernelGGL((project_bwd_kernel<D, false, false>), grid, dim3(kProjThreads), lds, st, a)
+        if (row_sums) { GS_LDS((project_bwd_kernel<D, false, true>)); hipLaunchKernelGGL((project_bwd_kernel<D, false, true>), grid, dim3(kProjThreads), lds, st, a); } \
+        else { GS_LDS((project_bwd_kernel<D, false, false>)); hipLaunchKernelGGL((project_bwd_kernel<D, false, false>), grid, dim3(kProjThreads), lds, st, a); }
         switch (sh_degree) {
             case 0: GS_PB(0); break;
             case 1: GS_PB(1); break;
             case 2: GS_PB(2); break;
             case 3: GS_PB(3); break;
+            case 4: GS_PB(4); break;
             default: GS_PB(-1); break;
         }
 #undef GS_PB
@@ -1276,7 +1294,7 @@ static int project_bwd_adam(void* stream, int64_t N, int K, int sh_degree, float
                             int64_t* applied_dev, float* max_radii, float* grad_norm_accum, float* counts,
                             const float* sh_jac, bool reg, float max_ratio, float lambda) {
     GS_REQUIRE(N >= 0 && width > 0 && height > 0, "N>=0, positive image size");
-    GS_REQUIRE(sh_degree >= 0 && sh_degree <= 3 && K >= (sh_degree + 1) * (sh_degree + 1) && K <= 16, "SH colours: 0 <= degree <= 3, (degree+1)^2 <= K <= 16");
+    GS_REQUIRE(sh_degree >= 0 && sh_degree <= 4 && K >= (sh_degree + 1) * (sh_degree + 1) && K <= 25, "SH colours: 0 <= degree <= 4, (degree+1)^2 <= K <= 25");
     if (N == 0) return GS_OK;
     GS_REQUIRE(params && exp_avg && exp_avg_sq && offsets_host && viewmats && Ks && radii && colors_post && tiles_per_gauss &&
                cum_tiles && rows && row_base && qmask && v_means2d_abs && hyper_dev, "null pointer");
@@ -1310,13 +1328,14 @@ static int project_bwd_adam(void* stream, int64_t N, int K, int sh_degree, float
     // (no row_sums form of the fused kernel: its instantiation kept a dead 36-byte stack object, and a kernel that declares
     //  scratch makes the runtime provision it -- gs_blend.hip, GS_FWD_TRAIN_WAVES_PER_EU)
 #define GS_PB(D)                                                                                                        \
-    if (reg) hipLaunchKernelGGL((project_bwd_kernel<D, true, false, true>), grid, dim3(kProjThreads), lds, st, a);     \
-    else hipLaunchKernelGGL((project_bwd_kernel<D, true, false>), grid, dim3(kProjThreads), lds, st, a)
+    if (reg) { GS_LDS((project_bwd_kernel<D, true, false, true>)); hipLaunchKernelGGL((project_bwd_kernel<D, true, false, true>), grid, dim3(kProjThreads), lds, st, a); } \
+    else { GS_LDS((project_bwd_kernel<D, true, false>)); hipLaunchKernelGGL((project_bwd_kernel<D, true, false>), grid, dim3(kProjThreads), lds, st, a); }
     switch (sh_degree) {
         case 0: GS_PB(0); break;
         case 1: GS_PB(1); break;
         case 2: GS_PB(2); break;
-        default: GS_PB(3); break;
+        case 3: GS_PB(3); break;
+        default: GS_PB(4); break;
     }
 #undef GS_PB
     GS_LAUNCH_CHECK("project_bwd_kernel (fused Adam)");

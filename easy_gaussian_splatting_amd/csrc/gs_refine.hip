@@ -237,7 +237,7 @@ extern "C" int gs_refine_apply(void* stream, int64_t n_old, int num_splits, int 
                                const float* old_params, const float* old_exp_avg, const float* old_exp_avg_sq,
                                const int64_t* old_offsets_host, float* new_params, float* new_exp_avg, float* new_exp_avg_sq,
                                const int64_t* new_offsets_host, int32_t* src_scratch, int8_t* tag_scratch) {
-    GS_REQUIRE(n_old >= 0 && num_splits >= 1 && K >= 1 && K <= 16, "n_old >= 0, num_splits >= 1, 1 <= K <= 16");
+    GS_REQUIRE(n_old >= 0 && num_splits >= 1 && K >= 1 && K <= 25, "n_old >= 0, num_splits >= 1, 1 <= K <= 25");
     GS_REQUIRE(tot_old >= 0 && tot_child >= 0 && tot_clone >= 0, "negative totals");
     const int64_t n_new = tot_old + (int64_t)num_splits * tot_child + tot_clone;
     GS_REQUIRE(n_new < (1ll << 31) && n_old < (1ll << 31), "Gaussian counts must fit int32");

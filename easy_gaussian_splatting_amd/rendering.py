@@ -1205,8 +1205,8 @@ def rasterization(
         assert colors.dim() == 3 and colors.shape[0] == N and colors.shape[2] == 3, colors.shape
         k_store = colors.shape[1] + (0 if colors_rest is None else colors_rest.shape[1])
         assert (sh_degree + 1) ** 2 <= k_store, (colors.shape, k_store)
-        if sh_degree > 3 or k_store > 16:
-            raise NotImplementedError("SH degree > 3 is not implemented")
+        if sh_degree > 4 or k_store > 25:   # (gsplat evaluates degrees 0-4)
+            raise NotImplementedError("SH degree > 4 is not implemented")
     if backgrounds is not None:
         assert backgrounds.shape == (C, 3 if sh_degree is not None else colors.shape[-1]), backgrounds.shape
     if packed:

@@ -234,6 +234,8 @@ size_t gs_bin_workspace_bytes(int C, int64_t N, int tile_w, int tile_h);
 
 /* P-fwd + SH-fwd fused (replaces gsplat fully_fused_projection + spherical_harmonics +
  * clamp_min(rgb+0.5, 0); call site /root/reference/model/gaussian.py:353-367).
+ * sh_degree 0..4 (gsplat's range) with (sh_degree+1)^2 <= K <= 25, the same for every SH entry point below
+ * (gs_project_bwd, gs_project_bwd_adam[_reg], gs_sh_grad_views, gs_sh_adam_views; gs_refine_apply: 1 <= K <= 25).
  * sh_degree >= 0: `colors_in` is shs[N,K,3] and sh_rest is NULL, or -- the reference model's own
  * parameter layout (/root/reference/model/gaussian.py:49-50, cat at :105-107) -- `colors_in` is
  * sh_0[N,1,3] and `sh_rest` is [N,K-1,3] (no concatenated copy is ever made).
