@@ -330,7 +330,15 @@ GS_HD void sh_dir_grad(int degree, const float* d, float x, float y, float z, fl
     }
 }
 
-// v_mean += d(unit direction)/d(mean)^T g   (direction = (mean - camera centre) / dnorm)
+// term = d(unit direction)/d(mean)^T g   (direction = (mean - camera centre) / dnorm): the gradient the colour sends to the mean
+// through the view direction -- and, with the opposite sign, to the camera centre (sh_dir_term)
+GS_HD void dir_grad_term(float gx, float gy, float gz, float x, float y, float z, float dnorm, float* term) {
+    const float ud = x * gx + y * gy + z * gz;
+    const float inv = 1.0f / dnorm;
+    term[0] = (gx - x * ud) * inv; term[1] = (gy - y * ud) * inv; term[2] = (gz - z * ud) * inv;
+}
+
+// v_mean += that term  (written out, not through dir_grad_term: the projection backward keeps its code register for register)
 GS_HD void dir_grad_to_mean(float gx, float gy, float gz, float x, float y, float z, float dnorm, float* v_mean) {
     const float ud = x * gx + y * gy + z * gz;
     const float inv = 1.0f / dnorm;
@@ -393,11 +401,48 @@ GS_HD void sh_vjp_jac(int degree, const float* G, const float* rgb, const float*
     dir_grad_to_mean(gx, gy, gz, ux, uy, uz, dnorm, v_mean);
 }
 
+// The direction term of sh_vjp on its own (what it adds to v_mean; no v_sh): term[3], zero where sh_vjp adds nothing.  The camera
+// centre receives minus this term (the direction is mean - centre): the SH part of the camera gradient.  `sh_from_1` points at
+// coefficient 1 ([K-1][3]: `sh + 3` of a dense block, or the sh_rest row of the split layout; coefficient 0 has no direction).
+GS_HD void sh_dir_term(int degree, const float* sh_from_1, const float* rgb, const float* v_rgb, float ux, float uy, float uz,
+                       float dnorm, float* term) {
+    term[0] = term[1] = term[2] = 0.f;
+    if (degree < 1 || !(dnorm > 0.f)) return;
+    const float vr = rgb[0] > 0.f ? v_rgb[0] : 0.f;
+    const float vg = rgb[1] > 0.f ? v_rgb[1] : 0.f;
+    const float vb = rgb[2] > 0.f ? v_rgb[2] : 0.f;
+    const int Ka = (degree + 1) * (degree + 1);
+    float d[kMaxShCoeffs];
+    d[0] = 0.f;
+    for (int k = 1; k < Ka; ++k) d[k] = sh_from_1[3 * k - 3] * vr + sh_from_1[3 * k - 2] * vg + sh_from_1[3 * k - 1] * vb;
+    float gx, gy, gz;
+    sh_dir_grad(degree, d, ux, uy, uz, gx, gy, gz);
+    dir_grad_term(gx, gy, gz, ux, uy, uz, dnorm, term);
+}
+
+// ... and of sh_vjp_jac, from the forward's direction Jacobian G
+GS_HD void sh_dir_term_jac(int degree, const float* G, const float* rgb, const float* v_rgb, float ux, float uy, float uz,
+                           float dnorm, float* term) {
+    term[0] = term[1] = term[2] = 0.f;
+    if (degree < 1 || !(dnorm > 0.f)) return;
+    const float vr = rgb[0] > 0.f ? v_rgb[0] : 0.f;
+    const float vg = rgb[1] > 0.f ? v_rgb[1] : 0.f;
+    const float vb = rgb[2] > 0.f ? v_rgb[2] : 0.f;
+    const float gx = G[0] * vr + G[1] * vg + G[2] * vb;
+    const float gy = G[4] * vr + G[5] * vg + G[6] * vb;
+    const float gz = G[8] * vr + G[9] * vg + G[10] * vb;
+    dir_grad_term(gx, gy, gz, ux, uy, uz, dnorm, term);
+}
+
 // Appendix A.6 projection VJP for one (camera, Gaussian): adds into v_mean[3], v_quat[4], v_scale[3].
-template <typename T>
-GS_HD void project_vjp(const float* scale, const Camera& cam, const ProjChainT<T>& p, float v_mx_f,
-                       float v_my_f, float vA_f, float vB_f, float vC_f, float v_depth_f, float* v_mean,
-                       float* v_quat, float* v_scale) {
+// CAMG (project_vjp_cam): also yields the gradient of the view matrix's rows 0-2, viewmat = [[A, t], [0, 1]], in the chain's own
+// type -- v_t = v_pc (the camera-space gradient of the mean, formed here and otherwise only rotated back to world space) and
+// v_A = v_pc mean^T + 2 v_covc A Sigma, Sigma = M M^T (U = v_covc A is formed for v_cov anyway) -- SET, not added: the caller
+// sums them over the Gaussians of a camera.
+template <typename T, bool CAMG>
+GS_HD void project_vjp_impl(const float* mean, const float* scale, const Camera& cam, const ProjChainT<T>& p, float v_mx_f,
+                            float v_my_f, float vA_f, float vB_f, float vC_f, float v_depth_f, float* v_mean,
+                            float* v_quat, float* v_scale, T* v_A, T* v_t) {
     const T v_mx = v_mx_f, v_my = v_my_f, vA = vA_f, vB = vB_f, vC = vC_f, v_depth = v_depth_f;
     const T fx = cam.fx, fy = cam.fy;
     T limx, limy;
@@ -448,6 +493,20 @@ GS_HD void project_vjp(const float* scale, const Camera& cam, const ProjChainT<T
     const T w22 = V[2] * u02 + V[5] * u12 + V[8] * u22;
     // v_M = 2 v_cov M
     const T* M = p.M;
+    if (CAMG) {
+        v_t[0] = vx; v_t[1] = vy; v_t[2] = vz;
+        const T U[9] = {u00, u01, u02, u10, u11, u12, u20, u21, u22};
+        const T px = mean[0], py = mean[1], pz = mean[2];
+        for (int i = 0; i < 3; ++i) {
+            // row i of (U M) M^T
+            const T a0 = U[3 * i] * M[0] + U[3 * i + 1] * M[3] + U[3 * i + 2] * M[6];
+            const T a1 = U[3 * i] * M[1] + U[3 * i + 1] * M[4] + U[3 * i + 2] * M[7];
+            const T a2 = U[3 * i] * M[2] + U[3 * i + 1] * M[5] + U[3 * i + 2] * M[8];
+            v_A[3 * i] = v_t[i] * px + T(2) * (a0 * M[0] + a1 * M[1] + a2 * M[2]);
+            v_A[3 * i + 1] = v_t[i] * py + T(2) * (a0 * M[3] + a1 * M[4] + a2 * M[5]);
+            v_A[3 * i + 2] = v_t[i] * pz + T(2) * (a0 * M[6] + a1 * M[7] + a2 * M[8]);
+        }
+    }
     T vM[9];
     vM[0] = T(2) * (w00 * M[0] + w01 * M[3] + w02 * M[6]); vM[1] = T(2) * (w00 * M[1] + w01 * M[4] + w02 * M[7]); vM[2] = T(2) * (w00 * M[2] + w01 * M[5] + w02 * M[8]);
     vM[3] = T(2) * (w01 * M[0] + w11 * M[3] + w12 * M[6]); vM[4] = T(2) * (w01 * M[1] + w11 * M[4] + w12 * M[7]); vM[5] = T(2) * (w01 * M[2] + w11 * M[5] + w12 * M[8]);
@@ -466,6 +525,24 @@ GS_HD void project_vjp(const float* scale, const Camera& cam, const ProjChainT<T
     const T dot = w * vq0 + x * vq1 + y * vq2 + z * vq3;
     v_quat[0] += (float)((vq0 - w * dot) * p.qinv); v_quat[1] += (float)((vq1 - x * dot) * p.qinv);
     v_quat[2] += (float)((vq2 - y * dot) * p.qinv); v_quat[3] += (float)((vq3 - z * dot) * p.qinv);
+}
+
+template <typename T>
+GS_HD void project_vjp(const float* scale, const Camera& cam, const ProjChainT<T>& p, float v_mx_f,
+                       float v_my_f, float vA_f, float vB_f, float vC_f, float v_depth_f, float* v_mean,
+                       float* v_quat, float* v_scale) {
+    project_vjp_impl<T, false>(nullptr, scale, cam, p, v_mx_f, v_my_f, vA_f, vB_f, vC_f, v_depth_f, v_mean, v_quat, v_scale,
+                               (T*)nullptr, (T*)nullptr);
+}
+
+// The camera-gradient form: project_vjp (same v_mean / v_quat / v_scale, bit for bit) plus v_A[9] (row-major) and v_t[3] of
+// this (camera, Gaussian) in T -- fp64 in the product, not rounded to fp32 per Gaussian: the sum over a camera's Gaussians
+// cancels heavily (DESIGN.md "Camera gradients").  `mean`: the Gaussian's world-space mean.
+template <typename T>
+GS_HD void project_vjp_cam(const float* mean, const float* scale, const Camera& cam, const ProjChainT<T>& p, float v_mx_f,
+                           float v_my_f, float vA_f, float vB_f, float vC_f, float v_depth_f, float* v_mean,
+                           float* v_quat, float* v_scale, T* v_A, T* v_t) {
+    project_vjp_impl<T, true>(mean, scale, cam, p, v_mx_f, v_my_f, vA_f, vB_f, vC_f, v_depth_f, v_mean, v_quat, v_scale, v_A, v_t);
 }
 
 // Camera constants from raw viewmat[16] / K[9] (row-major), incl. the general 3x3 inverse for the

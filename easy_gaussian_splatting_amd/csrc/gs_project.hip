@@ -3,6 +3,8 @@
 //                        also leaves d colour / d view direction (sh_jac), so that the backward reads no coefficient
 //   project_bwd_kernel : gradient-row reduction (compact rows, a row per lane: row_sum_wave) + SH-bwd + P-bwd fused, no atomics;
 //                        <DEG, true>: Adam and update_statistics applied in the same pass (gs_project_bwd_adam)
+//   project_cam_kernel : camera gradients (gs_project_bwd_cam): the chain recomputed from the projection backward's per-Gaussian
+//                        outputs, 15 fp64 terms reduced per block without atomics; cam_sum_kernel adds a camera's block partials
 // The [N,K,3] SH block (192 B per Gaussian at SH3, 300 B at SH4) is moved through LDS with coalesced 16-byte accesses and read per
 // thread at an odd row stride (3K+1 dwords) so the per-thread walk over its own row is bank-conflict free.  The
 // geometry half of the forward is VALU-bound (the fp64 chain), the rest HBM streams and gathers.
@@ -1072,6 +1074,119 @@ __global__ __launch_bounds__(256) void row_sums_kernel(const RowSumsArgs a) {
     if (a.radii_norm) a.radii_norm[f] = vis ? (float)radius * (1.f / a.max_hw) : 0.f;   // (update_statistics_kernel's arithmetic)
 }
 
+// ------------------------------------------------------------------------------------------------
+// Camera gradients (gs_project_bwd_cam): dL/d viewmats rows 0-2 and dL/d camera centre, per camera, from what the projection
+// backward leaves per (camera, Gaussian) -- the row sums it hands out as v_means2d / v_conics / v_colors_post.  A kernel of its
+// own that recomputes the projection chain (project_bwd_kernel keeps its code and its registers: see the note at its template
+// parameters), 15 fp64 terms per visible Gaussian: v_A[9], v_t[3] (project_vjp_cam) and minus the SH direction term [3].
+// No atomics: lanes -> wave (shuffles, fixed order) -> the block's four waves through LDS -> ONE plain store of the block's
+// partial cam_partials[c][block][16]; cam_sum_kernel adds a camera's partials in a fixed order.  fp64 throughout: the sum runs
+// over up to millions of signed terms that cancel to a fraction of a per cent of their absolute sum (DESIGN.md "Camera gradients").
+struct ProjCamArgs {
+    int K, W, H, activations;
+    int64_t N;
+    float eps2d, near_p, far_p;
+    const float *means, *quats, *scales, *sh_from_1, *viewmats, *Ks, *colors_post;
+    int64_t sh_stride;        // floats between two Gaussians' coefficient-1 rows: 3K dense, 3(K-1) in the split layout
+    const int32_t* radii;
+    const float4* sh_jac;     // optional (gs_project_fwd): the coefficients are then not read
+    const float *v_means2d, *v_conics, *v_colors_post;
+    double* cam_partials;     // [C][gridDim.x][16]
+    const int64_t* guard;
+};
+
+constexpr int kCamTerms = 15;
+
+template <int DEG>
+__global__ __launch_bounds__(kProjThreads) void project_cam_kernel(const ProjCamArgs a) {
+    __shared__ float lds_cam[32];
+    __shared__ double wave_sums[kProjThreads / 64][16];
+    if (guard_tripped(a.guard)) return;
+    const int c = blockIdx.y;
+    const int64_t n = (int64_t)blockIdx.x * kProjThreads + threadIdx.x;
+    const int64_t f = (int64_t)c * a.N + n;
+    Camera cam;
+    load_camera(a.viewmats, a.Ks, c, a.W, a.H, lds_cam, cam);
+    double acc[kCamTerms];
+#pragma unroll
+    for (int i = 0; i < kCamTerms; ++i) acc[i] = 0.0;
+    if (n < a.N && a.radii[f] > 0) {
+        const float mean[3] = {a.means[3 * n], a.means[3 * n + 1], a.means[3 * n + 2]};
+        const float4 q4 = reinterpret_cast<const float4*>(a.quats)[n];
+        const float quat[4] = {q4.x, q4.y, q4.z, q4.w};
+        const float scale[3] = {act_scale(a.scales[3 * n], a.activations), act_scale(a.scales[3 * n + 1], a.activations),
+                                act_scale(a.scales[3 * n + 2], a.activations)};
+        if (DEG >= 1) {   // the SH colour's dependence on the camera centre: minus the direction term of v_mean
+            const float rgb[3] = {a.colors_post[3 * f], a.colors_post[3 * f + 1], a.colors_post[3 * f + 2]};
+            const float v_rgb[3] = {a.v_colors_post[3 * f], a.v_colors_post[3 * f + 1], a.v_colors_post[3 * f + 2]};
+            float ux, uy, uz, term[3];
+            const float dn = view_dir(mean, cam, ux, uy, uz);
+            if (a.sh_jac) {   // (project_bwd_kernel's layout)
+                float G[12];
+                const float4 j0 = a.sh_jac[2 * f], j1 = a.sh_jac[2 * f + 1];
+                G[10] = reinterpret_cast<const float*>(a.sh_jac + 2 * (int64_t)gridDim.y * a.N)[f];
+                G[0] = j0.x; G[1] = j0.y; G[2] = j0.z; G[4] = j0.w; G[5] = j1.x; G[6] = j1.y; G[8] = j1.z; G[9] = j1.w;
+                sh_dir_term_jac(DEG, G, rgb, v_rgb, ux, uy, uz, dn, term);
+            } else {
+                sh_dir_term(DEG, a.sh_from_1 + a.sh_stride * n, rgb, v_rgb, ux, uy, uz, dn, term);
+            }
+            acc[12] = -(double)term[0]; acc[13] = -(double)term[1]; acc[14] = -(double)term[2];
+        }
+        ProjChainT<preal> p;
+        if (project_chain<preal>(mean, quat, scale, cam, a.eps2d, a.near_p, a.far_p, p)) {
+            float v_mean[3] = {0.f, 0.f, 0.f}, v_quat[4] = {0.f, 0.f, 0.f, 0.f}, v_scale[3] = {0.f, 0.f, 0.f};   // (not used here)
+            const float2 vm = reinterpret_cast<const float2*>(a.v_means2d)[f];
+            project_vjp_cam<preal>(mean, scale, cam, p, vm.x, vm.y, a.v_conics[3 * f], a.v_conics[3 * f + 1], a.v_conics[3 * f + 2], 0.f,
+                                   v_mean, v_quat, v_scale, acc, acc + 9);
+        }
+    }
+    const int lane = lane_id(), wave = threadIdx.x >> 6;
+#pragma unroll
+    for (int i = 0; i < kCamTerms; ++i) {
+        const double t = wave_reduce_add(acc[i]);
+        if (lane == 0) wave_sums[wave][i] = t;
+    }
+    __syncthreads();
+    if (threadIdx.x < 16) {
+        double t = 0.0;
+        if (threadIdx.x < kCamTerms) {
+#pragma unroll
+            for (int w = 0; w < kProjThreads / 64; ++w) t += wave_sums[w][threadIdx.x];
+        }
+        a.cam_partials[((int64_t)c * gridDim.x + blockIdx.x) * 16 + threadIdx.x] = t;
+    }
+}
+
+// One block per camera: every one of the 16 values is walked by 64 threads, each over the camera's partials at a stride of 64
+// blocks (two interleaved chains per thread, so that two loads are in flight), and the 64 strided sums are added in order.
+// Writes v_viewmats[c] (rows 0-2 = [v_A | v_t], row 3 = 0) and v_campos[c].
+constexpr int kCamSumChains = 64;
+__global__ __launch_bounds__(16 * kCamSumChains) void cam_sum_kernel(const double* __restrict__ cam_partials, int n_blocks,
+                                                                     float* __restrict__ v_viewmats, float* __restrict__ v_campos,
+                                                                     const int64_t* __restrict__ guard) {
+    __shared__ double part[kCamSumChains][16];
+    if (guard_tripped(guard)) return;
+    const int c = blockIdx.x, term = threadIdx.x & 15, j = threadIdx.x >> 4;
+    const double* src = cam_partials + (int64_t)c * n_blocks * 16 + term;
+    double t0 = 0.0, t1 = 0.0;
+    for (int b = j; b < n_blocks; b += 2 * kCamSumChains) {
+        t0 += src[(int64_t)b * 16];
+        if (b + kCamSumChains < n_blocks) t1 += src[(int64_t)(b + kCamSumChains) * 16];
+    }
+    part[j][term] = t0 + t1;
+    __syncthreads();
+    if (threadIdx.x < 16) {
+        double sum = 0.0;
+#pragma unroll 8
+        for (int k = 0; k < kCamSumChains; ++k) sum += part[k][term];
+        float* vv = v_viewmats + 16 * c;
+        if (term < 9) vv[4 * (term / 3) + term % 3] = (float)sum;
+        else if (term < 12) vv[4 * (term - 9) + 3] = (float)sum;
+        else if (term < 15) v_campos[3 * c + (term - 12)] = (float)sum;
+        if (term < 4) vv[12 + term] = 0.f;
+    }
+}
+
 }  // namespace gs
 
 using namespace gs;
@@ -1279,6 +1394,69 @@ extern "C" int gs_project_bwd(void* stream, int C, int64_t N, int K, int sh_degr
     return GS_OK;
 }
 
+
+extern "C" size_t gs_cam_partials_doubles(int C, int64_t N) {
+    if (C < 1 || N < 0) return 0;
+    return (size_t)C * (size_t)((N + kProjThreads - 1) / kProjThreads) * 16;
+}
+
+extern "C" int gs_project_bwd_cam(void* stream, int C, int64_t N, int K, int sh_degree, const float* means,
+                                  const float* quats, const float* scales, const float* colors_in,
+                                  const float* sh_rest, int colors_per_camera, const float* viewmats,
+                                  const float* Ks, int width,
+                                  int height, float eps2d, float near_plane, float far_plane,
+                                  const int32_t* radii, const float* colors_post,
+                                  const int32_t* tiles_per_gauss, const int32_t* cum_tiles,
+                                  const float* rows, const int32_t* row_base, const uint8_t* qmask, float* v_means, float* v_quats, float* v_scales,
+                                  float* v_opacities, float* v_colors, float* v_sh_rest, float* v_means2d_abs,
+                                  float* v_means2d, float* v_conics, float* v_colors_post, float* v_colors_pre,
+                                  const float* opacities, int activations, const float* sh_jac, const float* row_sums,
+                                  float* stat_grad_norm, float* stat_count, double* cam_partials, float* v_viewmats,
+                                  float* v_campos) {
+    GS_REQUIRE(C >= 1 && N >= 0, "C>=1, N>=0");
+    GS_REQUIRE(v_viewmats && v_campos && (N == 0 || cam_partials), "null camera-gradient pointer");
+    GS_REQUIRE(N == 0 || (v_means2d && v_conics && (sh_degree < 1 || v_colors_post)),
+               "the camera gradients are formed from v_means2d / v_conics (and v_colors_post with SH degree >= 1): not optional here");
+    hipStream_t st = (hipStream_t)stream;
+    if (N == 0) {
+        GS_HIP_CHECK(hipMemsetAsync(v_viewmats, 0, sizeof(float) * 16 * C, st));
+        GS_HIP_CHECK(hipMemsetAsync(v_campos, 0, sizeof(float) * 3 * C, st));
+        return GS_OK;
+    }
+    GS_REQUIRE(((uintptr_t)quats & 15) == 0 && ((uintptr_t)v_means2d & 7) == 0 && ((uintptr_t)cam_partials & 7) == 0,
+               "quats 16-byte, v_means2d and cam_partials 8-byte aligned");
+    if (int rc = gs_project_bwd(stream, C, N, K, sh_degree, means, quats, scales, colors_in, sh_rest, colors_per_camera, viewmats, Ks,
+                                width, height, eps2d, near_plane, far_plane, radii, colors_post, tiles_per_gauss, cum_tiles, rows,
+                                row_base, qmask, v_means, v_quats, v_scales, v_opacities, v_colors, v_sh_rest, v_means2d_abs,
+                                v_means2d, v_conics, v_colors_post, v_colors_pre, opacities, activations, sh_jac, row_sums,
+                                stat_grad_norm, stat_count))
+        return rc;
+    ProjCamArgs a;
+    a.K = K; a.W = width; a.H = height; a.activations = activations != 0; a.N = N;
+    a.eps2d = eps2d; a.near_p = near_plane; a.far_p = far_plane;
+    a.means = means; a.quats = quats; a.scales = scales; a.viewmats = viewmats; a.Ks = Ks; a.colors_post = colors_post;
+    // coefficient 1 onwards: the sh_rest rows of the split layout, or behind coefficient 0 of the dense block
+    const bool split = sh_degree >= 0 && sh_rest != nullptr;
+    a.sh_from_1 = split ? sh_rest : colors_in + 3; a.sh_stride = split ? 3 * (int64_t)(K - 1) : 3 * (int64_t)K;
+    a.radii = radii; a.sh_jac = sh_degree >= 1 ? reinterpret_cast<const float4*>(sh_jac) : nullptr;
+    a.v_means2d = v_means2d; a.v_conics = v_conics; a.v_colors_post = v_colors_post;
+    a.cam_partials = cam_partials; a.guard = current_guard().info;
+    const int n_blocks = (int)((N + kProjThreads - 1) / kProjThreads);
+    dim3 grid((unsigned)n_blocks, (unsigned)C);
+#define GS_PC(D) hipLaunchKernelGGL((project_cam_kernel<D>), grid, dim3(kProjThreads), 0, st, a)
+    switch (sh_degree) {
+        case 1: GS_PC(1); break;
+        case 2: GS_PC(2); break;
+        case 3: GS_PC(3); break;
+        case 4: GS_PC(4); break;
+        default: GS_PC(0); break;   // (degree 0 and colour features: no direction term)
+    }
+#undef GS_PC
+    GS_LAUNCH_CHECK("project_cam_kernel");
+    hipLaunchKernelGGL(cam_sum_kernel, dim3((unsigned)C), dim3(16 * kCamSumChains), 0, st, (const double*)cam_partials, n_blocks, v_viewmats, v_campos, a.guard);
+    GS_LAUNCH_CHECK("cam_sum_kernel");
+    return GS_OK;
+}
 
 // Row reduction + SH-bwd + P-bwd + Adam in ONE pass (train-step graph, single camera): gs_project_bwd with the
 // reference model's raw parameters (log-scales, logit opacities, split SH), but instead of writing the 59 gradients

@@ -106,7 +106,10 @@ class ViewParallelStep:
       (B) all-reduce SUM of [means 3N | log_scales 3N | quats 4N | logit_opacities N | grad_norm N | count N] -- on the GPU
           written in place by the projection backward (`_grad_out`), statistics segments included: no pack pass.
     Then the SH half of Adam straight from the gathered records (`gs_sh_adam_views`: the dense SH gradient is never written)
-    while (B) is in flight, the geometry half of Adam and the two additive statistics after it."""
+    while (B) is in flight, the geometry half of Adam and the two additive statistics after it.
+
+    Cameras are constants here: with the exchange on the model renders with `sh_grads = "colors_pre"`, and `rasterization()`
+    refuses camera gradients in that mode (`ValueError`) -- a `data["w2c"]` that requires grad has no place in the exchange yet."""
 
     SH = ("sh_0", "sh_rest")
     GEOMETRY = ("means", "log_scales", "quats", "logit_opacities")

@@ -389,7 +389,10 @@ class GaussianModel(nn.Module):
 
     def forward(self, data: Dict[str, Any], clamp: bool = True) -> Dict[str, Optional[Tensor]]:
         """`clamp=False` returns the un-clamped image for `LossComputer(clamp_input=True)` (the clamp of
-        /root/reference/model/gaussian.py:368 then happens inside the loss kernels)."""
+        /root/reference/model/gaussian.py:368 then happens inside the loss kernels).
+        A `data["w2c"]` that requires grad (e.g. from `pose.CameraDeltas`) receives its gradient: the render is then asked for
+        camera gradients (`rasterization(_camera_grads=True)`).  Eager loop only: `TrainStepGraph` refuses such a `w2c`, and a
+        model with `sh_grads = "colors_pre"` (`ViewParallelStep` with its exchange on) is refused by `rasterization()`."""
         w2c = data["w2c"]
         # on the GPU the raw parameters go in and exp / sigmoid happen inside the projection kernels
         raw = self.means.is_cuda and getattr(self, "fuse_activations", True)
@@ -416,6 +419,7 @@ class GaussianModel(nn.Module):
             _on_colors_pre=getattr(self, "on_colors_pre", None),
             _grad_out=self.grad_out() if callable(getattr(self, "grad_out", None)) else None,
             _view_payload=self.view_payload() if callable(getattr(self, "view_payload", None)) else None,
+            _camera_grads=bool(w2c.requires_grad),
         )
         render_img = batch_render_imgs.squeeze(0)   # (a view both ways: `[0]` would cost a zero-fill + copy in backward)
         if clamp:

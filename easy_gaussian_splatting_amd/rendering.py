@@ -890,10 +890,14 @@ class _Rasterize(torch.autograd.Function):
     """One autograd node for the whole path (P-fwd .. B-fwd | B-bwd .. P-bwd)."""
 
     @staticmethod
-    def forward(ctx, means, quats, scales, opacities, colors, colors_rest, viewmats, Ks, backgrounds, cfg, holder):
+    def forward(ctx, means, quats, scales, opacities, colors, colors_rest, viewmats, Ks, backgrounds, cfg, holder, campos=None):
         # (needs_input_grad reflects requires_grad of the inputs even under torch.no_grad(); the grad mode
         #  is captured by the caller, forward() itself always runs with grad disabled)
-        need_grad = bool(cfg.get("grad_enabled", True)) and any(ctx.needs_input_grad[:6])
+        # `campos` (camera gradients with SH degree >= 1): inverse(viewmats)[:, :3, 3] formed under autograd by the caller.  The
+        # kernels keep computing their own camera centre; the input exists to receive v_campos, which autograd then carries to
+        # the view matrices through the inverse.  viewmats alone requiring grad (a frozen scene) is a training call too.
+        ctx.camera_grads = bool(cfg.get("camera_grads")) and ctx.needs_input_grad[6]
+        need_grad = bool(cfg.get("grad_enabled", True)) and (any(ctx.needs_input_grad[:6]) or ctx.camera_grads)
         ctx.set_materialize_grads(False)   # an unused render_alphas must not cost a zero-filled image
         render_colors, render_alphas, meta, state = _forward_stages(
             means, quats, scales, opacities, colors, colors_rest, viewmats, Ks, backgrounds, cfg, need_grad)
@@ -999,14 +1003,28 @@ class _Rasterize(torch.autograd.Function):
         if dbg is not None:
             v_cn = torch.empty((C, N, 3), **f32)
             v_cp = torch.empty((C, N, 3), **f32)
-        _stage("gs_project_bwd", dev, lambda: nat.check(L.gs_project_bwd(st, C, N, K, s["deg"], _ptr(means), _ptr(quats), _ptr(scales), _ptr(colors),
-                                   _ptr(colors_rest), pc_cam, _ptr(viewmats), _ptr(Ks), W, H, cfg["eps2d"],
-                                   cfg["near_plane"], cfg["far_plane"], _ptr(s["radii"]),
-                                   P(WS.COLORS_POST), P(WS.TILES_PER_GAUSS), P(WS.CUM_TILES),
-                                   P(WS.ROWS), P(WS.ROW_BASE), P(WS.QMASK), _ptr(v_means), _ptr(v_quats), _ptr(v_scales), _ptr(v_opac),
-                                   _ptr(v_pc), _ptr(v_rest), _ptr(v_abs), _ptr(v_m2), _ptr(v_cn), _ptr(v_cp), None,
-                                   _ptr(opacities), cfg.get("activations", 0), P(WS.SH_JAC) if s.get("sh_jac") else None,
-                                   _ptr(row_sums), _ptr(go.get("grad_norm")), _ptr(go.get("count"))), "gs_project_bwd"))
+        v_viewmats = v_campos = None
+        bwd_args = lambda: (st, C, N, K, s["deg"], _ptr(means), _ptr(quats), _ptr(scales), _ptr(colors),
+                            _ptr(colors_rest), pc_cam, _ptr(viewmats), _ptr(Ks), W, H, cfg["eps2d"],
+                            cfg["near_plane"], cfg["far_plane"], _ptr(s["radii"]),
+                            P(WS.COLORS_POST), P(WS.TILES_PER_GAUSS), P(WS.CUM_TILES),
+                            P(WS.ROWS), P(WS.ROW_BASE), P(WS.QMASK), _ptr(v_means), _ptr(v_quats), _ptr(v_scales), _ptr(v_opac),
+                            _ptr(v_pc), _ptr(v_rest), _ptr(v_abs), _ptr(v_m2), _ptr(v_cn), _ptr(v_cp), None,
+                            _ptr(opacities), cfg.get("activations", 0), P(WS.SH_JAC) if s.get("sh_jac") else None,
+                            _ptr(row_sums), _ptr(go.get("grad_norm")), _ptr(go.get("count")))
+        if ctx.camera_grads:
+            # gs_project_bwd_cam: the same projection backward (same bits), then the camera terms from the per-(camera, Gaussian)
+            # sums it hands out -- which are therefore written -- reduced per camera in fp64 without atomics.  The partials are
+            # scratch of this call alone: the leased workspace and an ordinary call do not change.
+            v_m2 = torch.empty((C, N, 2), **f32) if v_m2 is None else v_m2
+            v_cn = torch.empty((C, N, 3), **f32) if v_cn is None else v_cn
+            v_cp = torch.empty((C, N, 3), **f32) if v_cp is None else v_cp
+            partials = torch.empty((int(L.gs_cam_partials_doubles(C, N)),), dtype=torch.float64, device=dev)
+            v_viewmats, v_campos = torch.empty((C, 4, 4), **f32), torch.empty((C, 3), **f32)
+            _stage("gs_project_bwd", dev, lambda: nat.check(L.gs_project_bwd_cam(*bwd_args(), _ptr(partials), _ptr(v_viewmats), _ptr(v_campos)),
+                                                            "gs_project_bwd_cam"))
+        else:
+            _stage("gs_project_bwd", dev, lambda: nat.check(L.gs_project_bwd(*bwd_args()), "gs_project_bwd"))
         if ch != 3:
             _stage("gs_channel_grads", dev, lambda: nat.check(L.gs_channel_grads(
                 st, C, N, ch, s["per_cam"], _ptr(s["radii"]), P(WS.TILES_PER_GAUSS), P(WS.CUM_TILES), P(WS.ROWS), P(WS.ROW_BASE),
@@ -1029,7 +1047,7 @@ class _Rasterize(torch.autograd.Function):
                 v_scales if (ni[2] and "scales" not in go) else None,
                 v_opac if (ni[3] and "opacities" not in go) else None, v_colors if (ni[4] and not factorised) else None,
                 v_rest if (ctx.split and ni[5] and not factorised) else None,
-                None, None, None, None, None)
+                v_viewmats, None, None, None, None, v_campos if (len(ni) > 11 and ni[11]) else None)
 
 
 def _lease_pack_hook(holder):
@@ -1114,6 +1132,7 @@ def rasterization(
     _rounds: Optional[str] = None,
     _grad_out: Optional[Dict[str, Tensor]] = None,
     _view_payload: Optional[Tensor] = None,
+    _camera_grads: bool = False,
 ) -> Tuple[Tensor, Tensor, Dict]:
     """Rasterize 3D Gaussians to images; same tensor signature and return value as
     `gsplat.rendering.rasterization` (gsplat 1.0.0).
@@ -1163,6 +1182,14 @@ def rasterization(
     in ONE launch right after the blend backward, with this rank's record of the view-parallel all-gather: [3N pre-clamp colour
     gradients | N radii / max(W, H) (0 for culled Gaussians) | the 16 floats of the view matrix] (`gs_row_sums`;
     `meta["means2d"].colors_pre_grad` is then a view of its first segment).
+
+    `_camera_grads=True`: `viewmats` may require grad and receives gsplat's `v_viewmats` (`gs_project_bwd_cam`): the projection's
+    dependence on rows 0-2 of each view matrix, and -- SH colours of degree >= 1 -- the view direction's dependence on the camera
+    centre `inverse(viewmats)[:, :3, 3]`, carried through `torch.linalg.inv` by autograd (bottom row included, as in gsplat).  All
+    colour paths, C >= 1; every other output and gradient is bit-identical to the call without it.  Opt-in: without the keyword
+    a `viewmats` that requires grad raises `NotImplementedError` as before; `Ks.requires_grad` always does (gsplat 1.0.0 has no
+    `v_Ks`).  Not together with `_sh_grads="colors_pre"`, `_grad_out` or `_view_payload` (`ValueError`): the view-parallel step has
+    no place for a camera gradient.  INTEGRATION.md "Refining camera poses".
 
     `_rounds` ("auto" | "on" | "off"; default: env GS_ROUNDS or "auto"): depth rounds of the list stages for INFERENCE calls with
     one camera -- the front slab by depth is listed, sorted and blended first, the rest only into tiles it has not finished
@@ -1219,10 +1246,16 @@ def rasterization(
         raise NotImplementedError(f"only tile_size={_TILE} is implemented")
     if sparse_grad:
         raise NotImplementedError("sparse_grad requires packed=True")
-    if viewmats.requires_grad or Ks.requires_grad:
-        # gsplat returns camera gradients; the reference never asks for them and this path
-        # does not compute them -- refuse instead of handing back None silently
-        raise NotImplementedError("gradients w.r.t. viewmats / Ks are not implemented (the reference's cameras are constants)")
+    if Ks.requires_grad:
+        raise NotImplementedError("gradients w.r.t. Ks are not implemented (gsplat 1.0.0 has no v_Ks either)")
+    if viewmats.requires_grad and not _camera_grads:
+        # gsplat returns camera gradients; the reference never asks for them: they are computed on request only
+        # -- refuse instead of handing back None silently
+        raise NotImplementedError("gradients w.r.t. viewmats are computed on request only: pass _camera_grads=True "
+                                  "(the reference's cameras are constants)")
+    if _camera_grads and (_sh_grads == "colors_pre" or _grad_out is not None or _view_payload is not None):
+        raise ValueError("_camera_grads cannot be combined with _sh_grads='colors_pre', _grad_out or _view_payload "
+                         "(the view-parallel step has no place for a camera gradient)")
     if not means.is_cuda:
         raise RuntimeError("rasterization() runs on the GPU only: tensors must live on a HIP device "
                            "(there is no CPU fallback in this package)")
@@ -1250,7 +1283,8 @@ def rasterization(
                sh_degree=sh_degree, tile_culling={"gsplat": 1, "tight": 1, "gsplat_eager": 0}[_tile_culling],
                lazy_ref_lists=_tile_culling == "gsplat", sh_grads=_sh_grads,
                activations={"none": 0, "exp_sigmoid": 1}[_activations], grad_enabled=torch.is_grad_enabled(),
-               defer_size_check=size_check == "deferred", rounds=_rounds)
+               defer_size_check=size_check == "deferred", rounds=_rounds,
+               camera_grads=bool(_camera_grads and viewmats.requires_grad and torch.is_grad_enabled()))
     if _sh_grads not in ("dense", "colors_pre") or (_sh_grads == "colors_pre" and sh_degree is None):
         raise ValueError("_sh_grads: 'dense', or 'colors_pre' together with sh_degree")
     holder = _Holder(absgrad)
@@ -1260,10 +1294,14 @@ def rasterization(
     holder.view_payload = _view_payload
     if _view_payload is not None and _sh_grads != "colors_pre":
         raise ValueError("_view_payload needs _sh_grads='colors_pre'")
+    # camera gradients with direction-dependent colours: the camera centre as a graph tensor (see _Rasterize.forward)
+    campos = None
+    if cfg["camera_grads"] and sh_degree is not None and sh_degree >= 1:
+        campos = torch.linalg.inv(viewmats_c)[:, :3, 3].contiguous()
     # (pack hook: every tensor the node saves for backward carries the workspace lease -- see _Rasterize.forward)
     with torch.cuda.device(means.device), torch.autograd.graph.saved_tensors_hooks(_lease_pack_hook(holder), lambda p: p[0]):
         render_colors, render_alphas = _Rasterize.apply(means_c, quats_c, scales_c, opac_c, colors_c, rest_c,
-                                                        viewmats_c, Ks_c, bg_c, cfg, holder)
+                                                        viewmats_c, Ks_c, bg_c, cfg, holder, campos)
     holder.lease_ref = None   # (held by the saved tensors now, if anything was saved)
     meta = holder.meta
     holder.meta = {}

@@ -56,6 +56,13 @@ def _p(t: Optional[Tensor]):
     return None if t is None else t.data_ptr()
 
 
+def _refuse_camera_grads(data) -> None:
+    if data is not None and isinstance(data.get("w2c"), Tensor) and data["w2c"].requires_grad:
+        raise ValueError("TrainStepGraph: data['w2c'] requires grad, but the captured step has no camera gradient (its fused-Adam "
+                         "projection backward writes none): detach it, or refine poses in the eager loop (model(data) with "
+                         "pose.CameraDeltas)")
+
+
 class TrainStepGraph:
     def __init__(self, model, optimizer: FusedAdam, loss_computer, data: Dict[str, Any], gt_img: Tensor,
                  mask: Optional[Tensor] = None, margin: float = 1.3, use_graph: bool = True, check_every: int = 16,
@@ -68,7 +75,10 @@ class TrainStepGraph:
         A loop that looks at nothing between steps then leaves its own stream idle, and the wait every step performs on
         entry (below) costs nothing; with the eager form that wait sits behind the previous step's hand-back on the caller's
         stream -- two cross-queue signal hops, 24 us of idle GPU per step in the kernel trace of the bench loop.  Parameters
-        and statistics are NOT intercepted: a lazy caller that reads them between steps calls `fence()` first."""
+        and statistics are NOT intercepted: a lazy caller that reads them between steps calls `fence()` first.
+        Cameras are constants here: a `data["w2c"]` that requires grad raises `ValueError` (here and in `step`) -- the captured
+        step's fused-Adam projection backward has no camera output; refine poses in the eager loop."""
+        _refuse_camera_grads(data)
         if handback not in ("eager", "lazy"):
             raise ValueError("handback: 'eager' or 'lazy'")
         self.handback = handback
@@ -779,7 +789,8 @@ class TrainStepGraph:
         `ready_event`: an event the step's stream waits for before it reads anything (the upload of the inputs on a copy stream:
         `HostFeed`).  `host_src = {"w2c", "K", "image"[, "mask"]}` host tensors the device inputs were uploaded from: a feeder that
         recycles its device slots hands them in, and an overflow recovery replays the step from a FRESH upload of those instead
-        of from slots that have been refilled since."""
+        of from slots that have been refilled since.  A `data["w2c"]` that requires grad raises `ValueError` (see `__init__`)."""
+        _refuse_camera_grads(data)
         W, H = (self.W, self.H) if data is None else (int(data["width"]), int(data["height"]))
         if self._state_key(W, H) != self._key:
             self.finish()

@@ -442,6 +442,32 @@ int gs_project_bwd(void* stream, int C, int64_t N, int K, int sh_degree, const f
                    const float* opacities, int activations, const float* sh_jac, const float* row_sums,
                    float* stat_grad_norm, float* stat_count);
 
+/* gs_project_bwd plus the camera gradients (rasterization(_camera_grads=True)): the arguments and results of gs_project_bwd,
+ * bit for bit (it is called inside), and from what it leaves per (camera, Gaussian) the gradient of the view matrices.  For
+ * viewmats[c] = [[A, t], [0, 1]]:
+ *   v_viewmats[C,4,4]: rows 0-2 = [v_A | v_t], v_t = sum_n v_pc, v_A = sum_n (v_pc mean^T + 2 v_covc A Sigma) over the camera's
+ *     visible Gaussians (v_pc, v_covc: the camera-space gradients of the projection VJP); row 3 = 0.  The projection part only.
+ *   v_campos[C,3]: the gradient of the camera centre inverse(viewmat)[:3,3] the SH colours look from (SH degree >= 1; zero
+ *     otherwise) = minus the sum of the direction terms of v_means.  The caller carries it to the view matrix through the VJP
+ *     of the 4x4 inverse (as gsplat's torch.inverse does) and adds it to v_viewmats.
+ * v_means2d, v_conics and (SH degree >= 1) v_colors_post are NOT optional here: the camera terms are recomputed from them by a
+ * kernel of its own, 15 fp64 values per visible Gaussian, reduced without atomics -- wave, block, one partial per block in
+ * cam_partials[gs_cam_partials_doubles(C, N)] (fp64 scratch, 8-byte aligned, contents undefined before and after), then a
+ * fixed-order sum per camera: two calls give the same bits.  Honours the step guard like gs_project_bwd. */
+size_t gs_cam_partials_doubles(int C, int64_t N);
+int gs_project_bwd_cam(void* stream, int C, int64_t N, int K, int sh_degree, const float* means,
+                       const float* quats, const float* scales, const float* colors_in,
+                       const float* sh_rest, int colors_per_camera, const float* viewmats,
+                       const float* Ks, int width, int height, float eps2d, float near_plane, float far_plane,
+                       const int32_t* radii, const float* colors_post, const int32_t* tiles_per_gauss,
+                       const int32_t* cum_tiles, const float* rows, const int32_t* row_base, const uint8_t* qmask,
+                       float* v_means, float* v_quats, float* v_scales, float* v_opacities,
+                       float* v_colors, float* v_sh_rest, float* v_means2d_abs, float* v_means2d,
+                       float* v_conics, float* v_colors_post, float* v_colors_pre,
+                       const float* opacities, int activations, const float* sh_jac, const float* row_sums,
+                       float* stat_grad_norm, float* stat_count, double* cam_partials, float* v_viewmats,
+                       float* v_campos);
+
 /* Row e (view sharding): the row sums of every Gaussian as a pass of its own, and from them everything another rank needs of
  * this view before the long projection backward runs.  row_sums[C*N][12] = the 11 sums gs_project_bwd forms first (same
  * function, same bits; 12th float 0; rows of culled Gaussians are left unwritten) -> gs_project_bwd(..., row_sums);
