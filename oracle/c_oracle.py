@@ -92,7 +92,7 @@ def render(means, quats, scales, opacities, colors, viewmats, Ks, width, height,
                 tile_width=tw, tile_height=th, n_isects=I,
                 _inputs=dict(means=means, quats=quats, scales=scales, shs=shs, viewmats=viewmats, Ks=Ks,
                              bg=bg, width=width, height=height, sh_degree=sh_degree, tile_size=tile_size,
-                             eps2d=eps2d, near_plane=near_plane, far_plane=far_plane))
+                             eps2d=eps2d, near_plane=near_plane, far_plane=far_plane, radius_clip=radius_clip))
 
 
 def blend_margin(fwd: Dict[str, np.ndarray], means2d_other=None, conics_other=None, mu_tol_ulps: float = 0.0,

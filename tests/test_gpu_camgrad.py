@@ -30,12 +30,15 @@ def _rel(a, b):
     return float(np.abs(a - b).max() / (np.abs(b).max() + 1e-30))
 
 
-def _case(kind, C, seed):
-    """Scene + colour tensors of one case.  Returns (sc, geometry as float32 numpy in the form the GPU call takes, colours as a
-    list of float32 numpy leaves, kwargs of rasterization, the activated fp64 scales / opacities of the oracle)."""
+def _case(kind, C, seed, cameras=None):
+    """Scene + colour tensors of one case; `cameras`: (viewmats, Ks) that replace the scene's orbit.  Returns (sc, geometry as
+    float32 numpy in the form the GPU call takes, colours as a list of float32 numpy leaves, kwargs of rasterization, the
+    activated fp64 scales / opacities of the oracle)."""
     W, H, N = 160, 112, 3000
     deg = {"sh0": 0, "sh3": 3, "sh3_split_act": 3, "sh4": 4}.get(kind)
     sc = make_scene(N, W, H, sh_degree=deg if deg is not None else 0, n_views=C, seed=seed, scale_range=(0.02, 0.2), dist=4.0)
+    if cameras is not None:
+        sc["viewmats"], sc["Ks"] = cameras
     geo = {k: sc[k] for k in GEO}
     kw = dict(sh_degree=deg)
     if kind == "sh3_split_act":   # the model's raw parameters and its two SH tensors
@@ -107,6 +110,35 @@ def _check_cameras(got, ref):
         print(f"camera {c}: rel err of v_viewmats {_rel(got[c], ref[c]):.3g} (largest entry {np.abs(ref[c]).max():.4g})")
     for c in range(ref.shape[0]):
         assert _rel(got[c], ref[c]) < GRAD_RTOL, (c, _rel(got[c], ref[c]))
+    return [_rel(got[c], ref[c]) for c in range(ref.shape[0])]
+
+
+def _oracle_v_viewmats(sc, cols, kw, act, vc, va):
+    """dL/d viewmats by fp64 autograd of the torch oracle (SH up to degree 3, or colour features)."""
+    f64 = lambda x: torch.from_numpy(np.asarray(x, np.float64))
+    V = f64(sc["viewmats"]).requires_grad_(True)
+    colors64 = torch.cat([f64(c) for c in cols], dim=1) if len(cols) == 2 else f64(cols[0])
+    img, alpha, _ = TO.rasterization(f64(sc["means"]), f64(sc["quats"]), f64(act[0]), f64(act[1]), colors64, V, f64(sc["Ks"]),
+                                     int(sc["width"]), int(sc["height"]), sh_degree=kw["sh_degree"], packed=False,
+                                     backgrounds=f64(sc["backgrounds"]))
+    (ref,) = torch.autograd.grad((img * vc).sum() + (alpha * va).sum(), V)
+    if kw["sh_degree"] is not None and kw["sh_degree"] >= 1:
+        assert float(ref[:, 3].abs().max()) > 0   # (the inverse's VJP reaches the bottom row, as gsplat's torch.inverse does)
+    return ref
+
+
+def _oracle_v_viewmats_degree4(sc, act, vc, va):
+    """The oracle's SH stops at degree 3: the degree-4 colours restated in fp64 torch (tests/sh4_ref.py) with the camera centre
+    under autograd, fed to the oracle as [C,N,3] features of the same `viewmats` leaf."""
+    f64 = lambda x: torch.from_numpy(np.asarray(x, np.float64))
+    V = f64(sc["viewmats"]).requires_grad_(True)
+    campos = torch.linalg.inv(V)[:, :3, 3]
+    means64 = f64(sc["means"])
+    feats = sh4_ref.sh_colors(f64(sc["shs"]), means64, campos, 4)   # [C,N,3]  (culled Gaussians are in no list: no gradient)
+    img, alpha, _ = TO.rasterization(means64, f64(sc["quats"]), f64(act[0]), f64(act[1]), feats, V, f64(sc["Ks"]),
+                                     int(sc["width"]), int(sc["height"]), sh_degree=None, packed=False, backgrounds=f64(sc["backgrounds"]))
+    (ref,) = torch.autograd.grad((img * vc).sum() + (alpha * va).sum(), V)
+    return ref
 
 
 KINDS = ("sh0", "sh3", "sh3_split_act", "feat1", "feat3", "feat4")
@@ -124,36 +156,19 @@ def test_view_matrix_gradient_matches_the_oracle_and_nothing_else_moves(kind, C)
     plain = _gpu(sc, geo, cols, kw, vc, va, False, culling)
     _assert_nothing_else_moves(with_cam, plain)
 
-    f64 = lambda x: torch.from_numpy(np.asarray(x, np.float64))
-    V = f64(sc["viewmats"]).requires_grad_(True)
-    colors64 = torch.cat([f64(c) for c in cols], dim=1) if len(cols) == 2 else f64(cols[0])
-    img, alpha, _ = TO.rasterization(f64(sc["means"]), f64(sc["quats"]), f64(act[0]), f64(act[1]), colors64, V, f64(sc["Ks"]),
-                                     int(sc["width"]), int(sc["height"]), sh_degree=kw["sh_degree"], packed=False,
-                                     backgrounds=f64(sc["backgrounds"]))
-    (ref,) = torch.autograd.grad((img * vc).sum() + (alpha * va).sum(), V)
-    if kw["sh_degree"] is not None and kw["sh_degree"] >= 1:
-        assert float(ref[:, 3].abs().max()) > 0   # (the inverse's VJP reaches the bottom row, as gsplat's torch.inverse does)
+    ref = _oracle_v_viewmats(sc, cols, kw, act, vc, va)
     _check_cameras(with_cam["v_viewmats"], ref)
 
 
 @pytest.mark.parametrize("C", [1, 2])
 def test_view_matrix_gradient_at_degree4(C):
-    """The oracle's SH stops at degree 3: the degree-4 colours restated in fp64 torch (tests/sh4_ref.py) with the camera centre
-    under autograd, fed to the oracle as [C,N,3] features of the same `viewmats` leaf."""
     sc, geo, cols, kw, act = _case("sh4", C, seed=80 + C)
     vc, va = _upstream(sc, act, 3, seed=4)
     with_cam = _gpu(sc, geo, cols, kw, vc, va, True)
     plain = _gpu(sc, geo, cols, kw, vc, va, False)
     _assert_nothing_else_moves(with_cam, plain)
 
-    f64 = lambda x: torch.from_numpy(np.asarray(x, np.float64))
-    V = f64(sc["viewmats"]).requires_grad_(True)
-    campos = torch.linalg.inv(V)[:, :3, 3]
-    means64 = f64(sc["means"])
-    feats = sh4_ref.sh_colors(f64(sc["shs"]), means64, campos, 4)   # [C,N,3]  (culled Gaussians are in no list: no gradient)
-    img, alpha, _ = TO.rasterization(means64, f64(sc["quats"]), f64(act[0]), f64(act[1]), feats, V, f64(sc["Ks"]),
-                                     int(sc["width"]), int(sc["height"]), sh_degree=None, packed=False, backgrounds=f64(sc["backgrounds"]))
-    (ref,) = torch.autograd.grad((img * vc).sum() + (alpha * va).sum(), V)
+    ref = _oracle_v_viewmats_degree4(sc, act, vc, va)
     _check_cameras(with_cam["v_viewmats"], ref)
 
 

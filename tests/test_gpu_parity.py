@@ -34,8 +34,8 @@ def to_dev(sc):
     return {k: torch.from_numpy(np.ascontiguousarray(v, dtype=np.float32)).to(dev()) for k, v in sc.items() if isinstance(v, np.ndarray) and v.dtype.kind == "f"}
 
 
-def run_hip(sc, bwd=True, seed=0, use_bg=True, dbg=None, culling="gsplat", fw=None, upstream=None, max_flip_tile_frac=0.02):
-    """With `fw` (the oracle's forward of the same scene) the random upstream gradients are zeroed on the pixels
+def run_hip(sc, bwd=True, seed=0, use_bg=True, dbg=None, culling="gsplat", fw=None, upstream=None, max_flip_tile_frac=0.02, **proj):
+    """`proj`: near_plane / far_plane / radius_clip / eps2d, passed through to rasterization().  With `fw` (the oracle's forward of the same scene) the random upstream gradients are zeroed on the pixels
     where the contributor set itself is undecided between fp32 and fp64 (loose_pixels), so that check_backward
     compares like with like: the gradient of the pixels on which both sides blend the same list."""
     from easy_gaussian_splatting_amd.rendering import rasterization
@@ -44,7 +44,7 @@ def run_hip(sc, bwd=True, seed=0, use_bg=True, dbg=None, culling="gsplat", fw=No
     img, alpha, meta = rasterization(*ins, t["viewmats"], t["Ks"], int(sc["width"]), int(sc["height"]),
                                      sh_degree=int(sc["sh_degree"]), packed=False,
                                      backgrounds=t["backgrounds"] if use_bg else None, absgrad=True, _debug=dbg,
-                                     _tile_culling=culling)
+                                     _tile_culling=culling, **proj)
     out = dict(img=img, alpha=alpha, meta=meta, ins=ins)
     if bwd:
         g = torch.Generator().manual_seed(seed)
@@ -66,10 +66,10 @@ def mask_upstream(hip, fw, vc, va, lists=True, max_flip_tile_frac=0.02):
     return vc * keep[..., None], va * keep[..., None]
 
 
-def run_oracle(sc, use_bg=True, dtype=np.float64):
+def run_oracle(sc, use_bg=True, dtype=np.float64, **proj):
     return CO.render(sc["means"], sc["quats"], sc["scales"], sc["opacities"], sc["shs"], sc["viewmats"], sc["Ks"],
                      int(sc["width"]), int(sc["height"]), sh_degree=int(sc["sh_degree"]),
-                     backgrounds=sc["backgrounds"] if use_bg else None, dtype=dtype)
+                     backgrounds=sc["backgrounds"] if use_bg else None, dtype=dtype, **proj)
 
 
 MAX_RAZOR_FRAC = 0.05   # scenes are built to stay off the blend thresholds (synthetic.dense_scene)
@@ -163,7 +163,8 @@ def oracle_fp32(fw):
         inp = fw["_inputs"]
         colors = inp["shs"] if inp["shs"] is not None else fw["colors"]
         fw["_fw32"] = CO.render(inp["means"], inp["quats"], inp["scales"], fw["opacities"][0], colors, inp["viewmats"], inp["Ks"],
-                                inp["width"], inp["height"], sh_degree=inp["sh_degree"], backgrounds=inp["bg"], dtype=np.float32)
+                                inp["width"], inp["height"], sh_degree=inp["sh_degree"], backgrounds=inp["bg"], dtype=np.float32,
+                                **{k: inp[k] for k in ("near_plane", "far_plane", "radius_clip", "eps2d")})
     return fw["_fw32"]
 
 
@@ -386,13 +387,13 @@ def check_backward(hip, fw, rtol=GRAD_RTOL, ref_transform=None):
     return bw
 
 
-def check_backward_unmasked(sc, fw, culling="gsplat", use_bg=True, seed=17):
+def check_backward_unmasked(sc, fw, culling="gsplat", use_bg=True, seed=17, **proj):
     """ONE unmasked backward per scene: a random upstream gradient on EVERY pixel, razor pixels
     included, against the fp32 build of the oracle -- an independent implementation in the arithmetic the device blends
     in, which takes its own fp32 decisions at the thresholds.  Two fp32 implementations do not flip the same threshold
     contributors, so the criterion is the isolated-flip rule of the S3 train loop: L2 over the tensor <= 5e-4, no element
     beyond 1e-2 of the tensor's largest, and the fraction of Gaussians beyond the plain 1e-3 is recorded."""
-    hip = run_hip(sc, culling=culling, use_bg=use_bg, seed=seed)
+    hip = run_hip(sc, culling=culling, use_bg=use_bg, seed=seed, **proj)
     fw32 = oracle_fp32(fw)
     bw = CO.backward(fw32, hip["vc"].astype(np.float32), hip["va"].astype(np.float32))
     names = ["v_means", "v_quats", "v_scales", "v_opacities", "v_colors"]

@@ -212,21 +212,20 @@ def test_degree_schedule_0_to_4_with_refinement_in_the_captured_step():
     assert runner.report()["rebuilds"] >= 5
 
 
-@pytest.mark.parametrize("split", [False, True])
-def test_sh_grad_views_at_degree4_matches_dense_path(split):
-    """The view-parallel step's SH rebuild (gs_sh_grad_views) at degree 4 equals the dense projection backward."""
+def _sh_grad_views_check(sc, deg, split, **proj):
+    """The view-parallel step's SH rebuild (gs_sh_grad_views) against the dense projection backward on scene `sc`."""
     dev = _dev()
-    sc = make_scene(2500, 176, 112, sh_degree=4, n_views=3, seed=35, scale_range=(0.03, 0.2), dist=4.0)
+    W, H, C, K = int(sc["width"]), int(sc["height"]), sc["viewmats"].shape[0], sc["shs"].shape[1]
     t = {k: torch.from_numpy(v).to(dev) for k, v in sc.items() if isinstance(v, np.ndarray)}
-    vc = torch.randn((3, 112, 176, 3), generator=torch.Generator().manual_seed(1)).to(dev)
+    vc = torch.randn((C, H, W, 3), generator=torch.Generator().manual_seed(1)).to(dev)
 
     def run(mode):
         ins = [t[k].clone().requires_grad_(True) for k in ("means", "quats", "scales", "opacities")]
         sh0 = t["shs"][:, :1].contiguous().requires_grad_(True)
         shr = t["shs"][:, 1:].contiguous().requires_grad_(True)
         shs = t["shs"].clone().requires_grad_(True)
-        img, _, meta = rasterization(*ins, (sh0, shr) if split else shs, t["viewmats"], t["Ks"], 176, 112, sh_degree=4,
-                                     packed=False, backgrounds=t["backgrounds"], absgrad=True, _sh_grads=mode)
+        img, _, meta = rasterization(*ins, (sh0, shr) if split else shs, t["viewmats"], t["Ks"], W, H, sh_degree=deg,
+                                     packed=False, backgrounds=t["backgrounds"], absgrad=True, _sh_grads=mode, **proj)
         (img * vc).sum().backward()
         return [p.grad for p in ins], ((sh0.grad, shr.grad) if split else (shs.grad,)), meta
 
@@ -234,24 +233,36 @@ def test_sh_grad_views_at_degree4_matches_dense_path(split):
     g_fact, _, meta = run("colors_pre")
     for a, b in zip(g_fact, g_dense):
         assert _rel(a.cpu().numpy(), b.cpu().numpy()) < 1e-6
-    rebuilt = sh_grad_views(t["means"], t["viewmats"], meta["means2d"].colors_pre_grad, 4, 25, split=split)
+    rebuilt = sh_grad_views(t["means"], t["viewmats"], meta["means2d"].colors_pre_grad, deg, K, split=split)
     rebuilt = rebuilt if split else (rebuilt,)
     for a, b in zip(rebuilt, sh_dense):
-        assert a.shape == b.shape
+        assert a.shape == b.shape and float(b.abs().max()) > 0
         assert _rel(a.cpu().numpy(), b.cpu().numpy()) < 2e-6
 
 
-@pytest.mark.parametrize("deg", [4, 2])
-def test_sh_adam_views_at_k25_equals_rebuild_plus_adam(deg):
+@pytest.mark.parametrize("split", [False, True])
+def test_sh_grad_views_at_degree4_matches_dense_path(split):
+    """The view-parallel step's SH rebuild (gs_sh_grad_views) at degree 4 equals the dense projection backward."""
+    _sh_grad_views_check(make_scene(2500, 176, 112, sh_degree=4, n_views=3, seed=35, scale_range=(0.03, 0.2), dist=4.0), 4, split)
+
+
+def _identity_rotation_cameras(R, g):
+    cams = torch.eye(4).repeat(R, 1, 1)
+    cams[:, :3, 3] = torch.randn((R, 3), generator=g) + torch.tensor([0.0, 0.0, 6.0])
+    return cams
+
+
+def _sh_adam_views_check(deg, cams=None, K=25):
+    """gs_sh_adam_views (SH rebuild over the views' records + Adam in one launch) against sh_grad_views followed by FusedAdam,
+    two steps, bit for bit.  `cams` [R,4,4]: the view matrices of the records (default: identity rotations)."""
     from easy_gaussian_splatting_amd import _native as nat
     from easy_gaussian_splatting_amd.optim import FusedAdam
     dev = _dev()
-    N, R, K = 3001, 2, 25
+    N, R = 3001, 2
     g = torch.Generator().manual_seed(5 + deg)
     means = (torch.rand((N, 3), generator=g) * 2 - 1).to(dev)
-    cams = torch.eye(4).repeat(R, 1, 1)
-    cams[:, :3, 3] = torch.randn((R, 3), generator=g) + torch.tensor([0.0, 0.0, 6.0])
-    cams = cams.to(dev)
+    cams = (_identity_rotation_cameras(R, g) if cams is None else cams).to(dev)
+    assert cams.shape == (R, 4, 4)
 
     def make():
         gg = torch.Generator().manual_seed(11)
@@ -285,6 +296,11 @@ def test_sh_adam_views_at_k25_equals_rebuild_plus_adam(deg):
         for x, y in zip(oa.moments_of(pa[k]), ob.moments_of(pb[k])):
             assert torch.equal(x, y), k
     assert torch.equal(rad_a, rad_b)
+
+
+@pytest.mark.parametrize("deg", [4, 2])
+def test_sh_adam_views_at_k25_equals_rebuild_plus_adam(deg):
+    _sh_adam_views_check(deg)
 
 
 def test_degree4_checkpoint_round_trip(tmp_path):

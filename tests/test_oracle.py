@@ -9,6 +9,7 @@ import torch
 
 from oracle import c_oracle as CO
 from oracle import torch_oracle as TO
+import cameras
 from scenes import make_scene
 
 GOLD = os.path.join(os.path.dirname(__file__), "golden")
@@ -124,6 +125,56 @@ def test_c_oracle_matches_torch_oracle_and_autograd(deg, C):
     for name, t in zip(["v_means", "v_quats", "v_scales", "v_opacities", "v_colors"], grads):
         np.testing.assert_allclose(bw[name], t.numpy(), atol=1e-9 * max(1.0, float(t.abs().max())), err_msg=name)
     np.testing.assert_allclose(bw["v_means2d_abs"], meta["means2d"].absgrad.numpy(), atol=1e-10)
+
+
+@pytest.mark.parametrize("name", list(cameras.CONFIGS))
+def test_general_camera_configurations_are_what_the_gpu_tests_rely_on(name):
+    """tests/cameras.py at the seed and size tests/test_gpu_cameras.py uses: the two oracles agree under general poses, per-camera
+    intrinsics and non-default near / far / radius_clip / eps2d; each cull that a configuration sets removes Gaussians; no
+    rotation is symmetric, t_x and t_y are non-zero, fx != fy and the principal point is off the image centre; the razor pixels
+    stay rare (<= 0.01, half of check_forward's default cap)."""
+    W, H, C = 160, 112, 2
+    sc, proj = cameras.config_scene(name, W=W, H=H, C=C)
+    V3, K3 = cameras.general_cameras(3, W, H, cameras.SEED, cameras.CONFIGS[name]["centre_box"])   # (the camera tests take three)
+    assert np.array_equal(V3[:C], sc["viewmats"]) and np.array_equal(K3[:C], sc["Ks"])
+    V, Ks = V3.astype(np.float64), K3.astype(np.float64)
+    for c in range(3):
+        R, t = V[c, :3, :3], V[c, :3, 3]
+        assert np.abs(R @ R.T - np.eye(3)).max() < 1e-6 and np.linalg.det(R) > 0.999
+        assert np.abs(R - R.T).max() > 0.05, "a symmetric rotation hides a transposed R"
+        # non-zero everywhere; a fifth of a unit on the two cameras every test takes (a wrong use of t_x, t_y moves their gradient)
+        assert min(abs(t[0]), abs(t[1])) > (0.2 if c < 2 else 1e-4), (c, t)
+        assert abs(Ks[c, 0, 2] - W / 2) > 1.0 and abs(Ks[c, 1, 2] - H / 2) > 1.0 and abs(Ks[c, 0, 0] - Ks[c, 1, 1]) > 1.0
+    assert np.abs(Ks[0] - Ks[1]).min(where=Ks[0] > 1, initial=np.inf) > 0.1   # (one K per camera)
+    V, Ks = V[:C], Ks[:C]
+    fw = CO.render(sc["means"], sc["quats"], sc["scales"], sc["opacities"], sc["shs"], sc["viewmats"], sc["Ks"], W, H, sh_degree=3,
+                   backgrounds=sc["backgrounds"], dtype=np.float64, **proj)
+    T = lambda a: torch.tensor(a, dtype=torch.float64)
+    img, alpha, meta = TO.rasterization(*[T(sc[k]) for k in ("means", "quats", "scales", "opacities", "shs")], T(sc["viewmats"]), T(sc["Ks"]),
+                                        W, H, sh_degree=3, packed=False, backgrounds=T(sc["backgrounds"]), **proj)
+    np.testing.assert_allclose(fw["render_colors"], img.numpy(), atol=1e-12)
+    np.testing.assert_allclose(fw["render_alphas"], alpha.numpy(), atol=1e-12)
+    for k in ("radii", "tiles_per_gauss"):
+        assert np.array_equal(fw[k], meta[k].numpy()), k
+    # what each cull removes, from the inputs alone (fp64 depth; the default planes only cut what is behind the camera)
+    z = np.einsum("cj,nj->cn", V[:, 2, :3], sc["means"].astype(np.float64)) + V[:, 2, 3:4]
+    vis = fw["radii"] > 0
+    near, far = np.float32(proj["near_plane"]), np.float32(proj["far_plane"])
+    assert not vis[(z < near) | (z > far)].any() and 0.15 < vis.mean() < 0.85
+    if name.startswith("inside"):
+        assert (z < near).mean(1).min() > 0.05, "cameras inside the cloud leave Gaussians behind them"
+    if name == "inside_slab":
+        assert ((z > 0.01) & (z < near)).sum(1).min() > 0 and (z > far).mean(1).min() > 0.02
+    if name == "clip":
+        free = CO.render(sc["means"], sc["quats"], sc["scales"], sc["opacities"], sc["shs"], sc["viewmats"], sc["Ks"], W, H, sh_degree=3,
+                         backgrounds=sc["backgrounds"], dtype=np.float64, **{**proj, "radius_clip": 0.0})
+        clipped = (free["radii"] > 0) & ~vis
+        assert clipped.sum(1).min() > 0 and free["radii"][clipped].max() <= 3 and fw["radii"][vis].min() == 4
+    if name == "inside":
+        assert fw["radii"].max() > 20 * max(W, H), "a footprint that covers the whole image many times over"
+    assert fw["render_alphas"].max() > 0.9998   # (pixels saturate: the early-out is taken)
+    razor = CO.blend_margin(fw, mu_tol_ulps=1.0, conic_rtol=2.4e-7) < 1e-4
+    assert razor.mean(axis=(1, 2)).max() <= 0.01, razor.mean(axis=(1, 2))
 
 
 def test_hand_derived_blend_backward_vs_naive_autograd():
