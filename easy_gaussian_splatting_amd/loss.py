@@ -92,6 +92,26 @@ class _FusedL1SSIM(torch.autograd.Function):
         return v_render, None, None, None, None
 
 
+def _fused_inputs(render_img: Tensor, gt_img: Tensor, mask):
+    """Decides, from `.shape`, `.dtype` and `.device` alone, whether the HIP path may take these inputs.  Returns None when
+    `render_img` is not a 3-D `[H, W, 3]` float32 CUDA image (the plain torch path handles any channel count, rank, dtype and
+    device); otherwise `(cast_gt, cast_mask)`: whether `gt_img` / `mask` must be converted to float32 before their pointers are
+    taken.  The kernels read `gt_img` as `[H, W, 3]` and `mask` as `[H, W]` float32 on `render_img`'s device through bare
+    pointers, so anything else is refused here."""
+    if not (render_img.device.type == "cuda" and render_img.dtype == torch.float32 and len(render_img.shape) == 3 and render_img.shape[2] == 3):
+        return None
+    if tuple(gt_img.shape) != tuple(render_img.shape):
+        raise ValueError(f"gt_img has shape {tuple(gt_img.shape)}, render_img {tuple(render_img.shape)}")
+    if gt_img.device != render_img.device:
+        raise ValueError(f"gt_img is on {gt_img.device}, render_img on {render_img.device}")
+    if mask is not None:
+        if tuple(mask.shape) != tuple(render_img.shape[:2]):
+            raise ValueError(f"mask has shape {tuple(mask.shape)}, expected {tuple(render_img.shape[:2])}")
+        if mask.device != render_img.device:
+            raise ValueError(f"mask is on {mask.device}, render_img on {render_img.device}")
+    return gt_img.dtype != torch.float32, mask is not None and mask.dtype != torch.float32
+
+
 class LossComputer:
     """`clamp_input=True`: `render_img` is the model's UN-clamped image (`GaussianModel.forward(data, clamp=False)`)
     and `torch.clamp(., 0, 1)` of /root/reference/model/gaussian.py:368 happens inside the loss (both directions);
@@ -117,7 +137,12 @@ class LossComputer:
         return d
 
     def get_loss_dict(self, render_img: Tensor, gt_img: Tensor, mask: Tensor = None) -> Dict[str, Tensor]:
-        if self.fused and render_img.is_cuda and render_img.dtype == torch.float32:
+        fused = _fused_inputs(render_img, gt_img, mask) if self.fused else None
+        if fused is not None:
+            if fused[0]:
+                gt_img = gt_img.float()
+            if fused[1]:
+                mask = mask.float()
             total, l1, ssim_loss = _FusedL1SSIM.apply(render_img, gt_img, mask, self.lambda_ssim, self.clamp_input)
             return self._add_regularization({"l1": l1, "ssim": ssim_loss, "total": total})
         if self.clamp_input:

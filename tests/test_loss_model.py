@@ -194,3 +194,98 @@ def test_checkpoint_does_not_pickle_the_training_drivers_hooks(tmp_path):
         assert model.__dict__["on_colors_pre"].__self__ is vp     # the live model keeps its hooks
     finally:
         dist.destroy_process_group()
+
+
+def test_fp64_reference_matches_the_separable_restatement():
+    """tests/loss_ref.py (direct 11 x 11 window, no padding) and loss.ssim / LossComputer(fused=False) (separable, reflect-padded
+    and cropped) state the same metric: values and gradient agree in float64, with and without mask and folded clamp."""
+    import loss_ref as LR
+    for (H, W), regime, mask, clamp, lam in (((23, 37), "noisy", "frac", False, 0.2), ((41, 19), "unclamped", "binary", True, 0.7),
+                                             ((23, 37), "white_bg", "none", True, 1.0)):
+        render, gt, m = LR.make_case(regime, H, W, seed=5, mask=mask)
+        ref = LR.ref64(render, gt, m, lam, clamp, scale=1.7)
+        r = render.double().requires_grad_(True)
+        out = LossComputer(lam, fused=False, clamp_input=clamp).get_loss_dict(r, gt.double(), None if m is None else m.double())
+        (out["total"] * 1.7).backward()
+        for k in ("l1", "ssim", "total"):
+            assert abs(out[k].item() - ref[k]) <= 1e-12, (k, regime)
+        assert float((r.grad - ref["grad"]).abs().max()) <= 1e-12 * float(ref["grad"].abs().max()), regime
+        x, y = render.double().clamp(0, 1).permute(2, 0, 1)[None], gt.double().permute(2, 0, 1)[None]
+        assert abs(ssim(x, y).item() - LR.ssim64(render.double().clamp(0, 1), gt.double()).item()) <= 1e-12
+
+
+def test_loss_reference_regimes_and_sign_resolution():
+    """The regime generators hand out float32 images with the properties the GPU tests rely on, and `resolve_sign` moves the
+    reference only on the elements it declares ambiguous."""
+    import loss_ref as LR
+    for regime in LR.REGIMES:
+        render, gt, m = LR.make_case(regime, 38, 45, seed=3, mask="frac")
+        assert render.dtype == gt.dtype == m.dtype == torch.float32 and render.shape == gt.shape == (38, 45, 3) and m.shape == (38, 45)
+        assert abs(float((m == 0).float().mean()) - 0.1) < 0.04 and abs(float((m == 1).float().mean()) - 0.1) < 0.04
+        a, b, _ = LR.make_case(regime, 38, 45, seed=3)
+        assert torch.equal(a, render) and torch.equal(b, gt)
+    render, gt, _ = LR.make_case("white_bg", 38, 45, seed=3)
+    same = (render == gt).all(-1)
+    assert 0.4 < float(same.float().mean()) < 0.8 and bool((gt[same] == 1.0).all()) and not bool(same[19, 22])
+    assert abs(float(LR.make_mask("binary", 200, 200, 1).mean()) - 0.2) < 0.02
+    render, gt, _ = LR.make_case("unclamped", 38, 45, seed=3)
+    assert bool((render.view(-1)[::13][1::17] == 0).all()) and bool((render.view(-1)[5::17] == 1).all()) and float((render < 0).float().mean()) > 0.1
+    # render == gt under a fractional mask: every kept element is ambiguous, and any of the three signs is accepted there only
+    g = torch.Generator().manual_seed(0)
+    gt = torch.rand(12, 13, 3, generator=g)
+    m = torch.rand(12, 13, generator=g)
+    m[0, 0] = 1.0; m[0, 1] = 0.0
+    ref = LR.ref64(gt.clone(), gt, m, 0.0)
+    amb = ref["ambiguous"]
+    assert bool(amb[1:].all()) and not bool(amb[0, 0].any()) and not bool(amb[0, 1].any())
+    grad = ref["l1_unit"] * amb
+    assert float((LR.resolve_sign(ref, grad) - grad).abs().max()) == 0.0
+    grad[0, 1] = 1.0   # not ambiguous: the reference stays
+    assert float(LR.resolve_sign(ref, grad)[0, 1].abs().max()) == 0.0 and LR.errors(ref, grad, ref)["grad_max"] > 1.0
+
+
+class _Spec:
+    """What `_fused_inputs` looks at and nothing else: a CUDA tensor's description without a GPU."""
+    def __init__(self, shape, dtype=torch.float32, device="cuda:0"):
+        self.shape, self.dtype, self.device = torch.Size(shape), dtype, torch.device(device)
+
+
+def test_fused_inputs_decision():
+    import pytest
+    from easy_gaussian_splatting_amd.loss import _fused_inputs
+    T = _Spec
+    H, W = 20, 31
+    assert _fused_inputs(T((H, W, 3)), T((H, W, 3)), None) == (False, False)
+    assert _fused_inputs(T((H, W, 3)), T((H, W, 3)), T((H, W))) == (False, False)
+    # other dtypes are cast before their pointer is taken
+    assert _fused_inputs(T((H, W, 3)), T((H, W, 3), torch.float64), T((H, W))) == (True, False)
+    assert _fused_inputs(T((H, W, 3)), T((H, W, 3)), T((H, W), torch.float64)) == (False, True)
+    assert _fused_inputs(T((H, W, 3)), T((H, W, 3), torch.float16), T((H, W), torch.bool)) == (True, True)
+    # not an [H, W, 3] float32 CUDA image: the plain torch path, whatever the other two are
+    for r in (T((H, W, 4)), T((H, W, 1)), T((H, W, 2)), T((H, W)), T((1, H, W, 3)), T((H, W, 3), torch.float64), T((H, W, 3), torch.float16),
+              T((H, W, 3), device="cpu"), torch.empty(H, W, 3, device="meta"), torch.empty(H, W, 3)):
+        assert _fused_inputs(r, T((H, W, 3)), T((5, 5))) is None
+    # shapes and devices the kernels would read through a bare pointer
+    for gt in (T((H, W, 4)), T((H, W, 1)), T((H, W)), T((W, H, 3)), T((H * W * 3,)), T((H, W, 3), device="cpu"), T((H, W, 3), device="cuda:1"),
+               torch.empty(H, W, 3), torch.empty(H, W, 3, device="meta")):
+        with pytest.raises(ValueError):
+            _fused_inputs(T((H, W, 3)), gt, None)
+    for m in (T((H, W, 1)), T((W, H)), T((H, W, 3)), T((H * W,)), T((H, W), device="cpu"), T((H, W), torch.bool, "cuda:1"), torch.empty(H, W),
+              torch.empty(H, W, device="meta")):
+        with pytest.raises(ValueError):
+            _fused_inputs(T((H, W, 3)), T((H, W, 3)), m)
+
+
+def test_loss_computer_takes_the_torch_path_off_the_gpu_for_any_channel_count():
+    """`LossComputer()` (fused by default) on CPU images of 1 and 4 channels: the plain path, equal to the C-channel reference."""
+    import loss_ref as LR
+    g = torch.Generator().manual_seed(2)
+    for C in (1, 4):
+        gt = torch.rand(19, 24, C, generator=g)
+        render = (gt + 0.1 * torch.randn(19, 24, C, generator=g)).clamp(0, 1)
+        m = LR.make_mask("frac", 19, 24, C)
+        ref = LR.ref64(render, gt, m, 0.2)
+        r = render.double().requires_grad_(True)
+        out = LossComputer(0.2).get_loss_dict(r, gt.double(), m.double())
+        out["total"].backward()
+        assert abs(out["total"].item() - ref["total"]) <= 1e-12 and float((r.grad - ref["grad"]).abs().max()) <= 1e-12 * float(ref["grad"].abs().max())
