@@ -12,6 +12,8 @@ import subprocess
 import threading
 from typing import Optional
 
+from ._header import parse as parse_header
+
 _HERE = os.path.dirname(os.path.abspath(__file__))
 # The product loads the in-tree build.  GS_LIB_PATH names another build of the same library -- a diagnostic VARIANT
 # (`build_variant`: -DGS_BWD_CHECK, -DGS_BWD_ACC64, -DGS_EXACT_MATH, -DGS_CLOCK_PROBE, tuning constants) -- and is honoured only
@@ -21,97 +23,30 @@ _HERE = os.path.dirname(os.path.abspath(__file__))
 LIB_PATH = os.environ.get("GS_LIB_PATH") or os.path.join(_HERE, "libgsraster.so")
 CSRC_DIR = os.path.join(_HERE, "csrc")
 VARIANT_DIR = os.path.join(os.path.dirname(_HERE), "build", "variants")   # never the package directory
-
-GS_TILE = 16
-GS_BUCKET = 64
-GS_UNIT = 32
-GS_REC_FLOATS = 12
-GS_ROW_FLOATS = 12
-GS_ROUND_BASE, GS_ROUND_SPLIT, GS_ROUND_LIVE, GS_ROUND_FRONT_N, GS_ROUND_LISTED_ALL, GS_ROUND_WORDS = 0, 1, 2, 3, 4, 8   # words of a depth-rounds block
+HEADER_PATH = os.path.abspath(os.path.join(_HERE, "..", "include", "gs_raster.h"))
 
 _lib: Optional[ct.CDLL] = None
 _lock = threading.Lock()
 
-_P = ct.c_void_p
-_I = ct.c_int
-_L = ct.c_int64
-_F = ct.c_float
-_Z = ct.c_size_t
-
-# name -> (restype, argtypes); must list every symbol include/gs_raster.h declares
-SIGNATURES = {
-    "gs_version": (_I, []),
-    "gs_build_flags": (ct.c_char_p, []),
-    "gs_last_error": (ct.c_char_p, []),
-    "gs_arch": (ct.c_char_p, []),
-    "gs_bin_groups": (_I, [_L]),
-    "gs_bin_workspace_bytes": (_Z, [_I, _L, _I, _I]),
-    "gs_project_fwd": (_I, [_P, _I, _L, _I, _I, _P, _P, _P, _P, _P, _P, _I, _P, _P, _I, _I, _F, _F, _F, _F, _I, _I, _I,
-                            _P, _P, _P, _P, _P, _P, _P, _P, _P, _P]),
-    "gs_bin_count": (_I, [_P, _I, _L, _I, _I, _P, _P, _Z, _P, _P, _P, _P, _P]),
-    "gs_bin_emit_sort": (_I, [_P, _I, _L, _I, _I, _P, _P, _P, _Z, _P, _L, _L, _P, _P, _P, _P, _P, _P]),
-    "gs_bins_workspace_bytes": (_Z, [_I, _L, _I, _I, _I, _L]),
-    "gs_bins_count": (_I, [_P, _I, _L, _I, _I, _I, _P, _P, _P, _Z, _P, _L, _L, _P, _P, _P, _P, _P, _P]),
-    "gs_bins_lists": (_I, [_P, _I, _L, _I, _I, _I, _P, _P, _Z, _P, _L, _P, _P, _P, _P, _P, _P]),
-    "gs_walk_state_ints": (_Z, [_L]),
-    "gs_blend_fwd": (_I, [_P, _I, _I, _I, _P, _P, _P, _P, _P, _P, _L, _P, _P, _P, _P, _P, _P, _P, _L, _P, _L, _P]),
-    "gs_blend_bwd": (_I, [_P, _I, _I, _I, _P, _P, _P, _P, _L, _P, _P, _P, _P, _P, _P, _P, _P, _P, _P]),
-    "gs_unit_classes_ints": (_Z, [_L, _I, _I, _I]),
-    "gs_rec_colors": (_I, [_P, _I, _L, _I, _P, _I, _P, _P]),
-    "gs_blend_fwd_ch": (_I, [_P, _I, _I, _I, _I, _P, _P, _P, _P, _P, _P, _L, _P, _P, _P, _P, _P, _P, _P, _L, _P, _L, _P, _P]),
-    "gs_blend_bwd_ch": (_I, [_P, _I, _I, _I, _I, _P, _P, _P, _P, _L, _P, _P, _P, _P, _P, _P, _P, _P, _P, _P, _P]),
-    "gs_channel_grads": (_I, [_P, _I, _L, _I, _I, _P, _P, _P, _P, _P, _P, _P]),
-    "gs_project_bwd": (_I, [_P, _I, _L, _I, _I, _P, _P, _P, _P, _P, _I, _P, _P, _I, _I, _F, _F, _F,
-                            _P, _P, _P, _P, _P, _P, _P, _P, _P, _P, _P, _P, _P, _P, _P, _P, _P, _P, _P, _I, _P, _P, _P, _P]),
-    "gs_cam_partials_doubles": (_Z, [_I, _L]),
-    "gs_project_bwd_cam": (_I, [_P, _I, _L, _I, _I, _P, _P, _P, _P, _P, _I, _P, _P, _I, _I, _F, _F, _F,
-                                _P, _P, _P, _P, _P, _P, _P, _P, _P, _P, _P, _P, _P, _P, _P, _P, _P, _P, _P, _I, _P, _P, _P, _P,
-                                _P, _P, _P]),
-    "gs_row_sums": (_I, [_P, _I, _L, _P, _P, _P, _P, _P, _P, _P, _P, _P, _P, _F, _P, _P]),
-    "gs_sh_adam_views": (_I, [_P, _I, _L, _I, _I, _P, _P, _L, _P, _P, _P, _P, _P, _P, _F, _F, _F, _F, _F, _L, _F, _P]),
-    "gs_sh_grad_views": (_I, [_P, _I, _L, _I, _I, _P, _P, _P, _P, _P]),
-    "gs_loss_workspace_floats": (_Z, [_I, _I]),
-    "gs_l1_ssim_fwd": (_I, [_P, _I, _I, _F, _P, _P, _P, _I, _P, _P]),
-    "gs_l1_ssim_bwd": (_I, [_P, _I, _I, _F, _P, _P, _P, _I, _P, _P, _P]),
-    "gs_l1_ssim_fwd_slots": (_I, [_P, _I, _I, _F, _P, _P, _I, _I, _P, _P]),
-    "gs_l1_ssim_bwd_slots": (_I, [_P, _I, _I, _F, _P, _P, _I, _P, _P, _P]),
-    "gs_clamp01": (_I, [_P, _L, _P, _P, _P]),
-    "gs_pack_view_step": (_I, [_P, _L, _F, _P, _P, _P, _P, _P, _P, _P]),
-    "gs_update_statistics": (_I, [_P, _L, _F, _P, _P, _P, _P, _P]),
-    "gs_guard_set": (_I, [_P, _L, _L]),
-    "gs_guard_set_call": (_I, [_P, _L, _L]),
-    "gs_info_mirror_set": (_I, [_P]),
-    "gs_walk_mirror_set": (_I, [_P]),
-    "gs_rounds_set": (_I, [_P, _P, _P, _P, _I]),
-    "gs_round_split": (_I, [_P, _L, _P, _P, _F, _P, _P]),
-    "gs_round_footprints": (_I, [_P, _L, _I, _I, _P, _P, _P, _P]),
-    "gs_round_status": (_I, [_P, _P, _P]),
-    "gs_step_status": (_I, [_P, _P, _P, _P, _P, _P, _I, _P]),
-    "gs_guard_flag_out": (_I, [_P, _P, _P, _P]),
-    "gs_guard_merge": (_I, [_P, _P, _P, _I, _L]),
-    "gs_step_applied": (_I, [_P, _P, _P]),
-    "gs_adam_hyper": (_I, [_P, _I, _P, _F, _F, _L, _P]),
-    "gs_step_inputs": (_I, [_P, _I, _P, _F, _F, _L, _P, _P, _P, _P, _P, _P, _P, _P]),
-    "gs_adam_step_dev": (_I, [_P, _L, _P, _P, _P, _I, _P, _P, _P, _F, _F, _F, _F, _P, _P]),
-    "gs_scan_rows_workspace_ints": (_Z, [_I, _L]),
-    "gs_scan_rows_i32": (_I, [_P, _I, _L, _P, _P, _P]),
-    "gs_refine_flags": (_I, [_P, _L, _I, _F, _F, _F, _F, _F, _P, _P, _P, _P, _P, _P, _P]),
-    "gs_refine_apply": (_I, [_P, _L, _I, _I, _P, _P, _L, _L, _L, _P, _P, _P, _P, _P, _P, _P, _P, _P, _P, _P]),
-    "gs_project_bwd_adam": (_I, [_P, _L, _I, _I, _P, _P, _P, _P, _P, _P, _I, _I, _F, _F, _F, _P, _P, _P, _P, _P, _P, _P, _P, _F, _F, _F, _P, _P,
-                                  _P, _P, _P, _P]),
-    "gs_project_bwd_adam_reg": (_I, [_P, _L, _I, _I, _P, _P, _P, _P, _P, _P, _I, _I, _F, _F, _F, _P, _P, _P, _P, _P, _P, _P, _P, _F, _F, _F, _P,
-                                      _P, _P, _P, _P, _P, _F, _F]),
-    "gs_scale_reg_workspace_floats": (_Z, [_L]),
-    "gs_scale_reg": (_I, [_P, _L, _P, _F, _F, _P, _P, _P]),
-    "gs_workspace_query": (_I, [_I, _L, _I, _I, _L, _L, _L, _L, _I, _I, _P, _P]),
-    "gs_workspace_bind": (_I, [_P, _P, _L, _P, _L, _P, _L, _P, _P]),
-    "gs_adam_step": (_I, [_P, _L, _P, _P, _P, _I, _P, _P, _P, _P, _F, _F, _F, _L, _F]),
-    "gs_adam_step_stats": (_I, [_P, _L, _P, _P, _P, _I, _P, _P, _P, _P, _F, _F, _F, _L, _F, _L, _P, _P, _P, _P]),
-}
-
 
 class NativeLibraryError(RuntimeError):
     pass
+
+
+def _read_header() -> str:
+    try:
+        with open(HEADER_PATH) as f:
+            return f.read()
+    except OSError as e:
+        raise NativeLibraryError(f"{HEADER_PATH} cannot be read ({e.strerror}): the binding of libgsraster.so is derived from that "
+                                 "header and there is no second copy of the ABI") from None
+
+
+# The header is the one description of the ABI.  SIGNATURES: name -> (restype, [argtypes]) and PARAMS: name -> [parameter names]
+# of every gs_* entry point it declares; DEFINES: every integer #define, each also a constant of this module (nat.GS_TILE,
+# nat.GS_FLAG_ROWS, nat.GS_INFO_FLAGS, nat.GS_WS_REC, ...).
+SIGNATURES, PARAMS, DEFINES = parse_header(_read_header())
+globals().update(DEFINES)
 
 
 def build(verbose: bool = False, clean: bool = False) -> str:
@@ -139,13 +74,12 @@ def build_variant(name: str, extra_flags: str) -> str:
     os.makedirs(VARIANT_DIR, exist_ok=True)
     out = os.path.join(VARIANT_DIR, f"libgsraster_{name}.so")
     srcs = [f for pat in ("*.hip", "*.h", "*.inc", "Makefile") for f in glob.glob(os.path.join(CSRC_DIR, pat))]
-    if os.path.exists(out) and all(os.path.getmtime(out) >= os.path.getmtime(f) for f in srcs + [os.path.join(_HERE, "..", "include", "gs_raster.h")]):
+    if os.path.exists(out) and all(os.path.getmtime(out) >= os.path.getmtime(f) for f in srcs + [HEADER_PATH]):
         return out
     d = tempfile.mkdtemp(prefix=f"gsvar_{name}_")
     try:
-        header = os.path.abspath(os.path.join(_HERE, "..", "include", "gs_raster.h"))
         for f in srcs:
-            text = open(f).read().replace("../../include/gs_raster.h", header)
+            text = open(f).read().replace("../../include/gs_raster.h", HEADER_PATH)
             open(os.path.join(d, os.path.basename(f)), "w").write(text)
         proc = subprocess.run(["make", "-C", d, "-j4", f"EXTRA={extra_flags}", f"LIB={out}"], capture_output=True, text=True)
         if proc.returncode != 0:
@@ -153,6 +87,14 @@ def build_variant(name: str, extra_flags: str) -> str:
     finally:
         shutil.rmtree(d, ignore_errors=True)
     return out
+
+
+def bind(cdll, names=None):
+    """Types the entry points `names` (default: all the header declares) of a loaded library as the header declares them."""
+    for name in SIGNATURES if names is None else names:
+        fn = getattr(cdll, name)  # AttributeError => header/library mismatch
+        fn.restype, fn.argtypes = SIGNATURES[name]
+    return cdll
 
 
 def lib() -> ct.CDLL:
@@ -166,11 +108,7 @@ def lib() -> ct.CDLL:
                         f"{LIB_PATH} is missing: the HIP rasterizer has not been built. Run "
                         "`python -c 'import __graft_entry__ as g; g.build()'` or "
                         f"`make -C {CSRC_DIR}`. There is no CPU fallback.")
-                L = ct.CDLL(LIB_PATH)
-                for name, (res, args) in SIGNATURES.items():
-                    fn = getattr(L, name)  # AttributeError => header/library mismatch
-                    fn.restype = res
-                    fn.argtypes = args
+                L = bind(ct.CDLL(LIB_PATH))
                 flags = L.gs_build_flags().decode("utf-8", "replace")
                 if flags and os.environ.get("GS_ALLOW_VARIANT") != "1":
                     raise NativeLibraryError(

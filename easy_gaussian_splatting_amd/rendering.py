@@ -207,7 +207,7 @@ def _pinned_info(device: torch.device) -> Tensor:
     key = device.index if device.index is not None else torch.cuda.current_device()
     ring = cache.get(key)
     if ring is None:
-        ring = cache[key] = [torch.empty((_INFO_RING, 8), dtype=torch.int64, pin_memory=True), 0]
+        ring = cache[key] = [torch.empty((_INFO_RING, nat.GS_INFO_WORDS), dtype=torch.int64, pin_memory=True), 0]
     ring[1] = (ring[1] + 1) % _INFO_RING
     return ring[0][ring[1]]
 
@@ -389,7 +389,7 @@ class _ReferenceLists:
             to_i32 = lambda v: torch.where(v >= (1 << 31), v - (1 << 32), v).to(torch.int32)   # (uint32 bit patterns)
             bbox = torch.stack([to_i32(r[:, 0] & 0xFFFFFFFF), to_i32(r[:, 1] & 0xFFFFFFFF), to_i32(mask), cnt.to(torch.int32)], dim=1).contiguous()
             tiles_per_gauss = cnt.to(torch.int32).view(C, N)
-            info_dev = torch.zeros((8,), dtype=torch.int64, device=dev)
+            info_dev = torch.zeros((nat.GS_INFO_WORDS,), dtype=torch.int64, device=dev)
             isect_offsets = torch.empty((C * tiles + 1,), **i32)
             bucket_offsets = torch.empty((C * tiles + 1,), **i32)
             cum_tiles = torch.empty((C * N,), **i32)
@@ -405,11 +405,11 @@ class _ReferenceLists:
                                               0, _ptr(cum_tiles), _ptr(isect_offsets), _ptr(bucket_offsets), None, _ptr(info_dev), None),
                               "gs_bins_count")
                     info = info_dev.tolist()
-                    if not int(info[3]) & 12:
+                    if not int(info[nat.GS_INFO_FLAGS]) & (nat.GS_FLAG_COARSE | nat.GS_FLAG_COARSE_LIST):
                         break
-                    coarse_cap = int(info[4]) + (int(info[4]) >> 2) + 1024
+                    coarse_cap = int(info[nat.GS_INFO_COARSE]) + (int(info[nat.GS_INFO_COARSE]) >> 2) + 1024
                     info_dev.zero_()
-                n_isects = int(info[0])
+                n_isects = int(info[nat.GS_INFO_ISECTS])
                 flatten_ids = torch.empty((max(n_isects, 1),), **i32)
                 isect_ids = torch.empty((max(n_isects, 1),), dtype=torch.int64, device=dev) if self.eager_ids else None
                 nat.check(L.gs_bins_lists(st, C, N, tw, th, shift, _ptr(bbox), _ptr(ws), ws.numel(), _ptr(keys), coarse_cap, _ptr(cum_tiles),
@@ -419,7 +419,7 @@ class _ReferenceLists:
                 nat.check(L.gs_bin_count(st, C, N, tw, th, _ptr(bbox), _ptr(ws), ws.numel(), _ptr(isect_offsets), _ptr(bucket_offsets), None,
                                          _ptr(info_dev), None), "gs_bin_count")
                 info = info_dev.tolist()
-                n_isects, max_tile = int(info[0]), int(info[2])
+                n_isects, max_tile = int(info[nat.GS_INFO_ISECTS]), int(info[nat.GS_INFO_MAX_TILE])
                 flatten_ids = torch.empty((max(n_isects, 1),), **i32)
                 isect_ids = torch.empty((max(n_isects, 1),), dtype=torch.int64, device=dev) if self.eager_ids else None
                 keys_tmp = torch.empty((max(n_isects, 1),), dtype=torch.int64, device=dev)
@@ -459,12 +459,12 @@ class _OneRoundLists:
             i32 = dict(dtype=torch.int32, device=dev)
             ws_bytes = int(L.gs_bin_workspace_bytes(C, N, tw, th))
             ws = torch.empty((ws_bytes,), dtype=torch.uint8, device=dev)
-            offs, bko, info = torch.empty((C * tiles + 1,), **i32), torch.empty((C * tiles + 1,), **i32), torch.zeros((8,), dtype=torch.int64, device=dev)
+            offs, bko, info = torch.empty((C * tiles + 1,), **i32), torch.empty((C * tiles + 1,), **i32), torch.zeros((nat.GS_INFO_WORDS,), dtype=torch.int64, device=dev)
             host = torch.zeros((4,), dtype=torch.int64)
             bbox = self.lease.ptr(WS.BBOX)
             nat.check(L.gs_bin_count(st, C, N, tw, th, bbox, ws.data_ptr(), ws_bytes, offs.data_ptr(), bko.data_ptr(), None, info.data_ptr(),
                                      host.data_ptr()), "gs_bin_count")
-            n_isects, max_tile = int(host[0]), int(host[2])
+            n_isects, max_tile = int(host[nat.GS_INFO_ISECTS]), int(host[nat.GS_INFO_MAX_TILE])
             keys = torch.empty((max(n_isects, 1),), dtype=torch.int64, device=dev)
             flat, cum = torch.empty((max(n_isects, 1),), **i32), torch.empty((C * N,), **i32)
             nat.check(L.gs_bin_emit_sort(st, C, N, tw, th, bbox, self.depths.data_ptr(), ws.data_ptr(), ws_bytes, offs.data_ptr(), n_isects,
@@ -557,7 +557,7 @@ def _forward_stages(means, quats, scales, opacities, colors, colors_rest, viewma
     lease = WS.pool.acquire(dev, st)
     lease.bind(WS.Layout(C, N, W, H, cap, coarse_cap, shift, flags, max(cap_units, 256), cap_rows), st)
     P = lease.ptr
-    info_dev = lease.view(WS.INFO, 8)
+    info_dev = lease.view(WS.INFO, nat.GS_INFO_WORDS)
     info_host = _pinned_info(dev)
     bin_bytes = lambda: int(L.gs_bins_workspace_bytes(C, N, tw, th, shift, coarse_cap) if two_level else L.gs_bin_workspace_bytes(C, N, tw, th))
 
@@ -665,7 +665,7 @@ def _forward_stages(means, quats, scales, opacities, colors, colors_rest, viewma
                         t_wait = time.perf_counter_ns()
                         ev.synchronize()
                         sizes["waited"] += time.perf_counter_ns() - t_wait
-                        if int(info_host[3]) != 0 or int(rb["host"][nat.GS_ROUND_LIVE]) == 0:
+                        if int(info_host[nat.GS_INFO_FLAGS]) != 0 or int(rb["host"][nat.GS_ROUND_LIVE]) == 0:
                             break   # (the front round did not fit: `settle` re-sizes and the attempt is repeated; or it finished the frame)
                 return ev
             _stage("gs_bin_count", dev, count)
@@ -692,36 +692,36 @@ def _forward_stages(means, quats, scales, opacities, colors, colors_rest, viewma
             ev.synchronize()
         sizes["waited"] += time.perf_counter_ns() - t_wait
         info = sizes["info"] = [int(v) for v in info_host.tolist()]
-        n_isects, max_tile, fl = info[0], info[2], info[3]
+        n_isects, max_tile, fl = info[nat.GS_INFO_ISECTS], info[nat.GS_INFO_MAX_TILE], info[nat.GS_INFO_FLAGS]
         if fl == 0:
             return True
         sizes["attempt"] += 1
         if sizes["attempt"] > 6:
             raise nat.NativeLibraryError(f"rasterization: list capacities did not settle (info {info})")
-        if two_level and fl & 12:
+        if two_level and fl & (nat.GS_FLAG_COARSE | nat.GS_FLAG_COARSE_LIST):
             # the coarse stage did not fit: the tile counts (I, longest list) were never formed -- only its own
             # sizes {I', longest bin list} are meaningful; the tile-list capacity is checked by the repeat
-            if fl & 4:
-                coarse_cap = info[4] + (info[4] >> 2) + 1024
+            if fl & nat.GS_FLAG_COARSE:
+                coarse_cap = info[nat.GS_INFO_COARSE] + (info[nat.GS_INFO_COARSE] >> 2) + 1024
             coarse_list_cap = 0
             with _state_lock:
                 stats["coarse_retries"] += 1
         else:
-            if fl & 1:
+            if fl & nat.GS_FLAG_ISECTS:
                 cap = n_isects + (n_isects >> 3) + 1024
-            if fl & 2:
+            if fl & nat.GS_FLAG_TILE:
                 cap_tile = _sort_class(max_tile)
         with _state_lock:
             stats["overflow_reruns"] += 1
         lease.grow_lists(WS.Layout(C, N, W, H, cap, coarse_cap, shift, flags, max(cap_units, 256), cap_rows), st)
-        info_dev = lease.view(WS.INFO, 8)
+        info_dev = lease.view(WS.INFO, nat.GS_INFO_WORDS)
         info_dev.zero_()
         return False
 
     def learn():
         """The capacity hints follow what this call needed."""
         info = sizes["info"]
-        n_isects, max_tile = info[0], info[2]
+        n_isects, max_tile = info[nat.GS_INFO_ISECTS], info[nat.GS_INFO_MAX_TILE]
         with _state_lock:
             stats["sync_wait_ns"] += sizes["waited"]
             stats["calls"] += 1
@@ -731,17 +731,18 @@ def _forward_stages(means, quats, scales, opacities, colors, colors_rest, viewma
             new = dict(cap=max(n_isects + (n_isects >> 2) + 1024, int(old.get("cap", 0) * 0.995)),
                        cap_tile=max(_sort_class(max_tile + (max_tile >> 2)), int(old.get("cap_tile", 1024))), footprint=n_isects / max(1, C * N),
                        mode="bins" if two_level else "tiles", n=N, listed_one_round=n_isects)
-            if rounds:   # (what one round would have listed, info[7]: the pipeline choice and the rounds decision follow the frame, not the rounds)
-                new["footprint"], new["listed_one_round"] = info[7] / max(1, C * N), info[7]
-                # ... and "auto" gives rounds up for a call shape whose front slab keeps leaving tiles to the back round (info[6]: a
+            if rounds:   # (what one round would have listed: the pipeline choice and the rounds decision follow the frame, not the rounds)
+                new["footprint"], new["listed_one_round"] = info[nat.GS_INFO_ONE_ROUND] / max(1, C * N), info[nat.GS_INFO_ONE_ROUND]
+                # ... and "auto" gives rounds up for a call shape whose front slab keeps leaving tiles to the back round (GS_INFO_LIVE: a
                 # back round that has work pays the fixed costs of the list stages twice -- train_graph.TrainStepGraph.ROUNDS_MAX_LIVE)
-                strikes = int(old.get("live_strikes", 0)) + 1 if info[6] > ROUNDS_MAX_LIVE * C * tiles else 0
+                strikes = int(old.get("live_strikes", 0)) + 1 if info[nat.GS_INFO_LIVE] > ROUNDS_MAX_LIVE * C * tiles else 0
                 new["live_strikes"], new["rounds_off"] = strikes, strikes >= 3
             elif old.get("rounds_off") and int(old.get("n", -1)) == N:
                 new["rounds_off"] = True
             if two_level:
-                new.update(entries=max(info[4] + (info[4] >> 2) + 1024, int(old.get("entries", 0) * 0.995)),
-                           longest=max(info[5] + (info[5] >> 2) + 64, int(old.get("longest", 0) * 0.995)))
+                coarse, max_bin = info[nat.GS_INFO_COARSE], info[nat.GS_INFO_MAX_BIN]
+                new.update(entries=max(coarse + (coarse >> 2) + 1024, int(old.get("entries", 0) * 0.995)),
+                           longest=max(max_bin + (max_bin >> 2) + 64, int(old.get("longest", 0) * 0.995)))
             _hints[hint_key] = new
             _coarse_hint[dev_index] = dict(mode=new["mode"], footprint=new["footprint"])
 
@@ -767,7 +768,7 @@ def _forward_stages(means, quats, scales, opacities, colors, colors_rest, viewma
                     late = True
                     ev, whole = enqueue_attempt(), True
             learn()
-            state_late["n_isects"], state_late["n_buckets"] = sizes["info"][0], sizes["info"][1]
+            state_late["n_isects"], state_late["n_buckets"] = sizes["info"][nat.GS_INFO_ISECTS], sizes["info"][nat.GS_INFO_BUCKETS]
             if late:
                 with _state_lock:
                     stats["late_overflows"] += 1
@@ -784,7 +785,7 @@ def _forward_stages(means, quats, scales, opacities, colors, colors_rest, viewma
         while not settle(ev, whole):
             ev, whole = enqueue_attempt(), True
         learn()
-        n_isects, n_buckets, max_tile = sizes["info"][0], sizes["info"][1], sizes["info"][2]
+        n_isects, n_buckets, max_tile = (sizes["info"][w] for w in (nat.GS_INFO_ISECTS, nat.GS_INFO_BUCKETS, nat.GS_INFO_MAX_TILE))
 
     def isects() -> int:
         if pending is not None:

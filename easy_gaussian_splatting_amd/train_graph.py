@@ -203,7 +203,7 @@ class TrainStepGraph:
         b["isect_offsets"] = torch.empty((tiles + 1,), **i32)
         b["bucket_offsets"] = torch.empty((tiles + 1,), **i32)
         b["tile_order"] = torch.empty((tiles,), **i32)
-        b["info"] = torch.zeros((8,), dtype=torch.int64, device=dev)
+        b["info"] = torch.zeros((nat.GS_INFO_WORDS,), dtype=torch.int64, device=dev)
         b["applied"] = torch.zeros((1,), dtype=torch.int64, device=dev)
         b["render_colors"] = torch.empty((1, H, W, 3), **f32)
         b["render_alphas"] = torch.empty((1, H, W, 1), **f32)
@@ -399,9 +399,10 @@ class TrainStepGraph:
         info = b["info"].tolist()
         w = b["walk_state"][:8].tolist()
         b["info"].zero_()
-        if int(info[3]) & ~48:
+        walk_flags = nat.GS_FLAG_UNITS | nat.GS_FLAG_ROWS
+        if int(info[nat.GS_INFO_FLAGS]) & ~walk_flags:
             raise RuntimeError(f"TrainStepGraph: the probed list capacities do not hold their own view {info}")
-        return int(w[1]), int(w[3]), int(info[3]) & 48
+        return int(w[nat.GS_WALK_STORAGE]), int(w[nat.GS_WALK_ROWS]), int(info[nat.GS_INFO_FLAGS]) & walk_flags
 
     def _protect_pending(self, static: Tensor):
         """`static` (one of the runner's input buffers) is about to be overwritten: steps still pending that were issued
@@ -568,7 +569,7 @@ class TrainStepGraph:
                 self._project()
                 self._count()
             info = b["info"].tolist()
-            n_isects, max_tile = int(info[0]), int(info[2])
+            n_isects, max_tile = int(info[nat.GS_INFO_ISECTS]), int(info[nat.GS_INFO_MAX_TILE])
             footprint = n_isects / max(1, self.N)
         else:
             with torch.cuda.device(dev), self._on_stream():
@@ -582,13 +583,13 @@ class TrainStepGraph:
                 with torch.cuda.device(dev), self._on_stream():
                     self._count()
                 info = b["info"].tolist()
-                if not int(info[3]) & 12:
+                if not int(info[nat.GS_INFO_FLAGS]) & (nat.GS_FLAG_COARSE | nat.GS_FLAG_COARSE_LIST):
                     break
-                self.cap_coarse = int(int(info[4]) * self.margin) + 4096
-            self.cap_coarse = int(int(info[4]) * self.margin) + 4096
-            self.cap_coarse_list = int(int(info[5]) * 1.5) + 64
-            self.probed_coarse = (int(info[4]), int(info[5]))   # coarse-bin entries I', longest bin list
-            n_isects, max_tile = int(info[0]), int(info[2])
+                self.cap_coarse = int(int(info[nat.GS_INFO_COARSE]) * self.margin) + 4096
+            self.cap_coarse = int(int(info[nat.GS_INFO_COARSE]) * self.margin) + 4096
+            self.cap_coarse_list = int(int(info[nat.GS_INFO_MAX_BIN]) * 1.5) + 64
+            self.probed_coarse = (int(info[nat.GS_INFO_COARSE]), int(info[nat.GS_INFO_MAX_BIN]))   # coarse-bin entries I', longest bin list
+            n_isects, max_tile = int(info[nat.GS_INFO_ISECTS]), int(info[nat.GS_INFO_MAX_TILE])
         b["info"].zero_()
         return n_isects, max_tile
 
@@ -727,7 +728,7 @@ class TrainStepGraph:
                     for n, s in zip(names, saved[3:]):
                         getattr(m, n).copy_(s)
                 self.buf["applied"].zero_()
-                if info[3] != 0:   # the capacities learnt from the probe do not hold (cannot happen unless inputs changed in between)
+                if info[nat.GS_INFO_FLAGS] != 0:   # the capacities learnt from the probe do not hold (cannot happen unless inputs changed in between)
                     self.buf["info"].zero_()
                     raise RuntimeError(f"TrainStepGraph: warm-up step overflowed its own capacities {info}")
             self.graph = None
@@ -893,7 +894,7 @@ class TrainStepGraph:
             self.pending.popleft()
         self.confirmed += max(done, 0)
         if flags != 0:
-            self._recover(n_isects, max_tile, (units, rows) if flags & 48 else (0, 0))
+            self._recover(n_isects, max_tile, (units, rows) if flags & (nat.GS_FLAG_UNITS | nat.GS_FLAG_ROWS) else (0, 0))
 
     def _recover(self, n_isects: int, max_tile: int, walk=(0, 0)):
         """A step did not fit: everything issued after the last applied step was skipped on the device.  Grow, re-capture,
@@ -910,11 +911,11 @@ class TrainStepGraph:
         self.stats["overflows"] += 1
         self.stats["replayed_steps"] += len(redo)
         # (what did not fit, and into what: flags 1 = listed intersections, 2 = longest tile list, 4 / 8 = coarse bins, 16 = work units, 32 = rows)
-        if int(self.status[3]) & 64:   # GS_FLAG_BACK: a frame needed the back round the captured step does not hold
+        if int(self.status[nat.GS_INFO_FLAGS]) & nat.GS_FLAG_BACK:   # a frame needed the back round the captured step does not hold
             self._back_needed = True
             self.stats["back_round_needed"] = self.stats.get("back_round_needed", 0) + 1
         self.stats.setdefault("overflow_log", []).append({
-            "step": self.confirmed + 1, "flags": int(self.status[3]), "isects": n_isects, "longest_list": max_tile, "work_units": walk[0], "rows": walk[1],
+            "step": self.confirmed + 1, "flags": int(self.status[nat.GS_INFO_FLAGS]), "isects": n_isects, "longest_list": max_tile, "work_units": walk[0], "rows": walk[1],
             "capacities": [self.cap, self.cap_tile, self.cap_units, self.cap_rows]})
         for e in redo:   # steps fed from recycled device slots (HostFeed): upload their own inputs again
             src = e[9] if len(e) > 9 else None

@@ -28,16 +28,17 @@ import torch
 
 from . import _native as nat
 
-# slot indices / flags of include/gs_raster.h
-INFO, REC, BBOX, TILES_PER_GAUSS, CUM_TILES, COLORS_POST, ISECT_OFFSETS, BUCKET_OFFSETS, TILE_ORDER, QCNT, SH_JAC = range(11)
-LIST_FIRST = 11
-BIN, COARSE_KEYS, KEYS_TMP, SLOT_GID, FLATTEN_IDS, SLOTS, ISECT_IDS, QMASK, ROW_BASE, WALK_STATE = range(11, 21)
-WALK_FIRST = 21
-CKPT, QLIST, UNIT_DESC, ROWS = range(21, 25)
-N_SLOTS = 25
-WALK_UNITS, WALK_STORAGE, _, WALK_ROWS, WALK_FLAGS = range(5)   # words of the walk state (GS_WALK_*)
-FLAG_UNITS, FLAG_ROWS = 16, 32
-F_TRAIN, F_TWO_LEVEL, F_ISECT_IDS = 1, 2, 4
+# Slot indices, walk-state words and flags of include/gs_raster.h under this module's short names: GS_WS_<NAME> is <NAME>, except
+# where the header gives the short name to something else -- GS_WS_SLOTS is the COUNT of slots (the slot is GS_WS_SLOTS_BUF), and
+# GS_WS_ISECT_IDS, like GS_WS_TRAIN and GS_WS_TWO_LEVEL, is a layout FLAG (the slot is GS_WS_ISECT_IDS_BUF).
+for _name in ("INFO", "REC", "BBOX", "TILES_PER_GAUSS", "CUM_TILES", "COLORS_POST", "ISECT_OFFSETS", "BUCKET_OFFSETS", "TILE_ORDER", "QCNT",
+              "SH_JAC", "LIST_FIRST", "BIN", "COARSE_KEYS", "KEYS_TMP", "SLOT_GID", "FLATTEN_IDS", "QMASK", "ROW_BASE", "WALK_STATE",
+              "WALK_FIRST", "CKPT", "QLIST", "UNIT_DESC", "ROWS"):
+    globals()[_name] = nat.DEFINES["GS_WS_" + _name]
+SLOTS, ISECT_IDS, N_SLOTS = nat.GS_WS_SLOTS_BUF, nat.GS_WS_ISECT_IDS_BUF, nat.GS_WS_SLOTS
+F_TRAIN, F_TWO_LEVEL, F_ISECT_IDS = nat.GS_WS_TRAIN, nat.GS_WS_TWO_LEVEL, nat.GS_WS_ISECT_IDS
+WALK_UNITS, WALK_STORAGE, WALK_ROWS, WALK_FLAGS = nat.GS_WALK_UNITS, nat.GS_WALK_STORAGE, nat.GS_WALK_ROWS, nat.GS_WALK_FLAGS
+FLAG_UNITS, FLAG_ROWS = nat.GS_FLAG_UNITS, nat.GS_FLAG_ROWS
 
 _DTYPES = {INFO: torch.int64, REC: torch.float32, BBOX: torch.int32, TILES_PER_GAUSS: torch.int32, CUM_TILES: torch.int32,
            COLORS_POST: torch.float32, ISECT_OFFSETS: torch.int32, BUCKET_OFFSETS: torch.int32, TILE_ORDER: torch.int32,

@@ -49,7 +49,18 @@ extern "C" {
 #define GS_WALK_RANGES 32    /* the storage units are handed out from 32 counters, each over its own 1/32 of [0, cap_units) and in */
 #define GS_WALK_RANGE0 32    /* a cache line of its own: word GS_WALK_RANGE0 + 32 * r (one counter took 30 k same-address atomics per frame) */
 #define GS_WALK_WORDS (GS_WALK_RANGE0 + 32 * GS_WALK_RANGES)
-/* Flag bits of an info block (info_dev[3], gs_guard_set) */
+/* Size record ("info block") of the list stages: int64[GS_INFO_WORDS], written by gs_bin_count (the first four words) and
+ * gs_bins_count (all of them); the GS_WS_INFO slot of a workspace, info_dev / info_host below. */
+#define GS_INFO_ISECTS 0     /* I: (tile, Gaussian) intersections listed */
+#define GS_INFO_BUCKETS 1    /* n_buckets */
+#define GS_INFO_MAX_TILE 2   /* longest tile list */
+#define GS_INFO_FLAGS 3      /* GS_FLAG_* */
+#define GS_INFO_COARSE 4     /* two-level binning: I', the coarse-bin entries */
+#define GS_INFO_MAX_BIN 5    /* two-level binning: longest bin list */
+#define GS_INFO_LIVE 6       /* chunks (depth rounds: tiles the front round left live) */
+#define GS_INFO_ONE_ROUND 7  /* one-round I of a call in depth rounds */
+#define GS_INFO_WORDS 8
+/* Flag bits of an info block (info_dev[GS_INFO_FLAGS], gs_guard_set) */
 #define GS_FLAG_ISECTS 1     /* I > cap_isects */
 #define GS_FLAG_TILE 2       /* a tile list longer than cap_tile */
 #define GS_FLAG_COARSE 4     /* two-level binning: coarse entries > coarse_cap */
@@ -191,7 +202,7 @@ int gs_step_status(void* stream, const int64_t* info_dev, const int64_t* applied
  * below; a call whose lists outgrow the capacity (info flags, see gs_guard_set) replaces the list arena only and repeats
  * gs_bin_count .. gs_blend_fwd; a training call whose walk outgrows cap_units / cap_rows replaces the walk arena only and repeats
  * gs_blend_fwd. */
-#define GS_WS_INFO 0            /* int64[8]   {I, n_buckets, longest tile list, flags, I', longest bin list, chunks (depth rounds: tiles the front round left live), one-round I of a call in depth rounds} */
+#define GS_WS_INFO 0            /* int64[GS_INFO_WORDS]: the size record, see GS_INFO_* */
 #define GS_WS_REC 1             /* f32 [C*N][12] */
 #define GS_WS_BBOX 2            /* u32 [C*N][4] */
 #define GS_WS_TILES_PER_GAUSS 3 /* i32 [C*N] */
@@ -305,7 +316,7 @@ int gs_bin_emit_sort(void* stream, int C, int64_t N, int tile_w, int tile_h, con
  * I entries, this one I'; it pays from ~6 tile-list entries per Gaussian upwards (real captures: tens to hundreds).
  *   coarse_keys[coarse_cap] u64   scratch for the bin lists (kept between the two calls)
  *   coarse_list_cap               longest bin list the sort classes launched must take (<= 0: launch every class)
- *   info_dev[8]                   {I, n_buckets, longest tile list, flags, I', longest bin list, chunks, -}
+ *   info_dev[GS_INFO_WORDS]       the size record (GS_INFO_*)
  *                                 flags: 1 I > guard capacity | 4 I' > coarse_cap | 8 a bin list > coarse_list_cap;
  *                                 with flags != 0 nothing was emitted: repeat gs_bins_count with the sizes reported
  *   cum_tiles[C*N]                exclusive scan of tiles_per_gauss (first gradient-row slot of each flatten id)

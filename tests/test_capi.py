@@ -25,7 +25,36 @@ def test_header_symbols_all_exported(native):
     lib = native.lib()
     for n in names:
         assert hasattr(lib, n), f"{n} declared in include/gs_raster.h but not exported"
-    assert names == set(native.SIGNATURES), "ctypes signature table out of sync with the header"
+    assert names == set(native.SIGNATURES)   # (the binding is parsed from the same header: tests/test_native_header.py)
+
+
+def _dynamic_symbols(path):
+    """Names of the symbols a shared object defines in its dynamic symbol table: `llvm-nm -D` of the ROCm tree, or -- a ROCm
+    tree that ships no llvm-nm -- the same table through its llvm-readelf.  None when neither tool is there."""
+    import shutil
+    import subprocess
+    rocm = os.environ.get("ROCM_PATH", "/opt/rocm")
+    dirs = os.pathsep.join([os.path.join(rocm, "llvm", "bin"), os.path.join(rocm, "lib", "llvm", "bin")])
+    nm, readelf = shutil.which("llvm-nm", path=dirs), shutil.which("llvm-readelf", path=dirs)
+    if nm:
+        out = subprocess.run([nm, "-D", "--defined-only", path], check=True, capture_output=True, text=True).stdout
+        return {ln.split()[-1] for ln in out.splitlines() if len(ln.split()) >= 3}
+    if readelf:
+        out = subprocess.run([readelf, "--dyn-syms", "-W", path], check=True, capture_output=True, text=True).stdout
+        rows = [ln.split() for ln in out.splitlines()]   # Num: Value Size Type Bind Vis Ndx Name
+        return {r[7].split("@")[0] for r in rows if len(r) >= 8 and r[0].rstrip(":").isdigit() and r[6] != "UND"}
+    return None
+
+
+def test_exported_entry_points_are_all_declared(native):
+    """The reverse of test_header_symbols_all_exported: every gs_* symbol the shared object exports dynamically is declared in
+    include/gs_raster.h -- an entry point defined in a .hip file and left out of the header has no binding and no contract."""
+    syms = _dynamic_symbols(native.LIB_PATH)
+    if syms is None:
+        pytest.skip("neither llvm-nm nor llvm-readelf in the ROCm tree: the dynamic symbol table cannot be read")
+    exported = {s for s in syms if s.startswith("gs_")}
+    assert len(exported) >= 61 and "gs_project_fwd" in exported, sorted(exported)[:5]
+    assert exported <= set(native.SIGNATURES), f"exported but not declared in include/gs_raster.h: {sorted(exported - set(native.SIGNATURES))}"
 
 
 def test_no_kernel_needs_scratch_memory(native):

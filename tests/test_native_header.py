@@ -1,0 +1,192 @@
+"""The Python binding is derived from include/gs_raster.h (easy_gaussian_splatting_amd/_header.py): the parser on short header
+snippets, the constants the package exports against the header's defines, and every Python call of an entry point against the
+header's parameter count.  Host only: nothing here loads the library or needs a GPU."""
+import ast
+import ctypes as ct
+import glob
+import os
+
+import pytest
+
+from easy_gaussian_splatting_amd import _header as H
+from easy_gaussian_splatting_amd import _native as nat
+
+ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
+P = ct.c_void_p
+
+
+# ---- the parser ----
+
+def test_pointers_and_arrays_are_void_pointers_and_values_keep_their_width():
+    sig, params, _ = H.parse("int gs_f(void* stream, const float* a, float* b, int32_t rec[6], const float* const* pp, const float** qq,\n"
+                             "         int n, int64_t big, size_t bytes, float x, double d, int32_t i, uint32_t u, const int k);")
+    assert sig == {"gs_f": (ct.c_int, [P, P, P, P, P, P, ct.c_int, ct.c_int64, ct.c_size_t, ct.c_float, ct.c_double, ct.c_int32, ct.c_uint32,
+                                       ct.c_int])}
+    assert params == {"gs_f": ["stream", "a", "b", "rec", "pp", "qq", "n", "big", "bytes", "x", "d", "i", "u", "k"]}
+
+
+def test_return_types_and_empty_parameter_lists():
+    sig, params, _ = H.parse("size_t gs_bytes(int n);\nconst char* gs_name(void);\nconst char *gs_name2();\nint gs_v( void );\nvoid gs_nothing(int a);")
+    assert sig == {"gs_bytes": (ct.c_size_t, [ct.c_int]), "gs_name": (ct.c_char_p, []), "gs_name2": (ct.c_char_p, []), "gs_v": (ct.c_int, []),
+                   "gs_nothing": (None, [ct.c_int])}
+    assert params["gs_name"] == [] and params["gs_bytes"] == ["n"]
+    assert list(sig) == ["gs_bytes", "gs_name", "gs_name2", "gs_v", "gs_nothing"]   # (the header's order)
+
+
+def test_a_prototype_over_several_lines_is_one_declaration():
+    sig, params, _ = H.parse("#ifdef __cplusplus\nextern \"C\" {\n#endif\nint gs_long(void* stream,\n            int64_t N,   /* how many */\n"
+                             "            const float*\n                means,\n            float eps);\n#ifdef __cplusplus\n}\n#endif\n")
+    assert sig == {"gs_long": (ct.c_int, [P, ct.c_int64, P, ct.c_float])} and params["gs_long"] == ["stream", "N", "means", "eps"]
+
+
+def test_comments_are_not_declarations():
+    text = ("/* call gs_ghost(a, b); then int gs_ghost2(int x); (see above) */\n"
+            "int gs_real(int a); /* gs_trailing(void); */\n"
+            "// int gs_line(int a);\n"
+            "#define GS_N 3 /* not (4); a comment\n   that goes on; int gs_in_define(void); */\n"
+            "int gs_after(float* p /* float gs_inner(int); */, int n);\n")
+    sig, params, defines = H.parse(text)
+    assert list(sig) == ["gs_real", "gs_after"] and sig["gs_after"] == (ct.c_int, [P, ct.c_int]) and defines == {"GS_N": 3}
+
+
+@pytest.mark.parametrize("decl, named", [
+    ("int gs_bad(void* s, long n);", "gs_bad"),                 # a type outside the map
+    ("int gs_bad(void* s, unsigned int n);", "gs_bad"),
+    ("int gs_bad(void* s, int);", "gs_bad"),                    # no parameter name: the names are part of what is derived
+    ("int gs_bad(float*);", "gs_bad"),
+    ("long gs_bad(int n);", "gs_bad"),                          # a return type outside the map
+    ("int gs_bad(int n)", "gs_bad"),                            # runs into the next declaration
+    ("int gs_bad(int n) int gs_next(void);", "gs_bad"),
+    ("typedef struct gs_thing gs_thing;", "gs_thing"),          # not a prototype at all
+    ("int gs_twice(int a); int gs_twice(int a);", "gs_twice"),
+])
+def test_what_the_parser_cannot_read_raises_and_names_the_function(decl, named):
+    with pytest.raises(H.HeaderError, match=named):
+        H.parse("int gs_ok(int a);\n" + decl + "\nint gs_ok2(int a);")
+
+
+def test_integer_defines():
+    _, _, d = H.parse("#ifndef GS_GUARD_H_\n#define GS_GUARD_H_\n#define GS_A 16\n#define GS_ERR (-1)\n# define GS_B GS_A\n"
+                      "#define GS_C (GS_A + 32 * GS_B)   /* words */\n#define GS_D ((GS_C - 8) * 2 + -GS_ERR)\n#define GS_HEX 0x10\n"
+                      "#ifndef GS_E\n#define GS_E 12\n#endif\n#endif\n")
+    assert d == {"GS_A": 16, "GS_ERR": -1, "GS_B": 16, "GS_C": 528, "GS_D": 1041, "GS_HEX": 16, "GS_E": 12}
+    assert list(d) == ["GS_A", "GS_ERR", "GS_B", "GS_C", "GS_D", "GS_HEX", "GS_E"]   # in order; the guard has no value and is no entry
+
+
+@pytest.mark.parametrize("line, named", [
+    ("#define GS_NAME \"gfx950\"", "GS_NAME"),                  # not an integer
+    ("#define GS_HALF 0.5", "GS_HALF"),
+    ("#define GS_LATER GS_UNDEFINED_SO_FAR", "GS_LATER"),       # only EARLIER defines
+    ("#define GS_DIV (8 / 2)", "GS_DIV"),                       # outside + - *
+    ("#define GS_SHIFT (1 << 4)", "GS_SHIFT"),
+    ("#define GS_CALL __import__(\"os\").getpid()", "GS_CALL"),  # never evaluated as Python
+    ("#define GS_ATTR GS_A.real", "GS_ATTR"),
+    ("#define GS_MAX(a, b) ((a) > (b) ? (a) : (b))", "GS_MAX"),  # a function-like macro
+    ("#define GS_SUFFIX 16u", "GS_SUFFIX"),
+    ("#if GS_A > 4", "#if"),                                    # a conditional the parser would have to evaluate
+    ("#undef GS_A", "#undef"),
+])
+def test_a_define_that_is_no_integer_expression_is_rejected(line, named):
+    with pytest.raises(H.HeaderError, match=named):
+        H.parse("#define GS_A 16\n" + line + "\n")
+
+
+def test_a_missing_header_is_a_native_library_error(monkeypatch, tmp_path):
+    monkeypatch.setattr(nat, "HEADER_PATH", str(tmp_path / "gs_raster.h"))
+    with pytest.raises(nat.NativeLibraryError, match="gs_raster.h"):
+        nat._read_header()
+
+
+# ---- the real header ----
+
+def test_the_header_parses_into_the_binding():
+    assert set(nat.SIGNATURES) == set(nat.PARAMS) and len(nat.SIGNATURES) >= 61
+    for name, (res, args) in nat.SIGNATURES.items():
+        assert name.startswith("gs_") and len(args) == len(nat.PARAMS[name]) == len(set(nat.PARAMS[name])), name
+    assert nat.PARAMS["gs_project_bwd"][-7:-4] == ["v_colors_pre", "opacities", "activations"] and len(nat.PARAMS["gs_project_bwd"]) == 42
+    assert len(nat.PARAMS["gs_project_bwd_cam"]) == 45 and nat.PARAMS["gs_project_bwd_cam"][:42] == nat.PARAMS["gs_project_bwd"]
+    assert nat.SIGNATURES["gs_bin_workspace_bytes"] == (ct.c_size_t, [ct.c_int, ct.c_int64, ct.c_int, ct.c_int])
+    assert nat.SIGNATURES["gs_last_error"] == (ct.c_char_p, []) and "GS_RASTER_H_" not in nat.DEFINES
+
+
+def test_exported_constants_are_the_headers_defines():
+    """Every constant the package re-exports under a name of its own equals the header's define; the aliases that are not
+    GS_WS_<NAME> -> <NAME> are written out (the header gives SLOTS and ISECT_IDS to the slot COUNT and to a FLAG)."""
+    from easy_gaussian_splatting_amd import workspace as WS
+    D = nat.DEFINES
+    for name in ("GS_TILE", "GS_BUCKET", "GS_UNIT", "GS_REC_FLOATS", "GS_ROW_FLOATS", "GS_ROUND_BASE", "GS_ROUND_SPLIT", "GS_ROUND_LIVE",
+                 "GS_ROUND_FRONT_N", "GS_ROUND_LISTED_ALL", "GS_ROUND_WORDS", "GS_FLAG_COARSE", "GS_FLAG_BACK", "GS_INFO_FLAGS", "GS_INFO_WORDS"):
+        assert getattr(nat, name) == D[name], name
+    assert (nat.GS_TILE, nat.GS_BUCKET, nat.GS_UNIT, nat.GS_REC_FLOATS, nat.GS_ROW_FLOATS, nat.GS_ROUND_WORDS, nat.GS_INFO_WORDS) == (16, 64, 32, 12, 12, 8, 8)
+    irregular = {"SLOTS": "GS_WS_SLOTS_BUF", "N_SLOTS": "GS_WS_SLOTS", "ISECT_IDS": "GS_WS_ISECT_IDS_BUF", "F_ISECT_IDS": "GS_WS_ISECT_IDS",
+                 "F_TRAIN": "GS_WS_TRAIN", "F_TWO_LEVEL": "GS_WS_TWO_LEVEL", "WALK_UNITS": "GS_WALK_UNITS", "WALK_STORAGE": "GS_WALK_STORAGE",
+                 "WALK_ROWS": "GS_WALK_ROWS", "WALK_FLAGS": "GS_WALK_FLAGS", "FLAG_UNITS": "GS_FLAG_UNITS", "FLAG_ROWS": "GS_FLAG_ROWS"}
+    regular = ("INFO", "REC", "BBOX", "TILES_PER_GAUSS", "CUM_TILES", "COLORS_POST", "ISECT_OFFSETS", "BUCKET_OFFSETS", "TILE_ORDER", "QCNT",
+               "SH_JAC", "LIST_FIRST", "BIN", "COARSE_KEYS", "KEYS_TMP", "SLOT_GID", "FLATTEN_IDS", "QMASK", "ROW_BASE", "WALK_STATE", "WALK_FIRST",
+               "CKPT", "QLIST", "UNIT_DESC", "ROWS")
+    for name in regular:
+        assert getattr(WS, name) == D["GS_WS_" + name], name
+    for name, define in irregular.items():
+        assert getattr(WS, name) == D[define], name
+    assert (WS.SLOTS, WS.N_SLOTS, WS.ISECT_IDS, WS.F_ISECT_IDS, WS.F_TRAIN, WS.F_TWO_LEVEL) == (16, 25, 17, 4, 1, 2)
+    # the slots are 0 .. N_SLOTS-1, each once (LIST_FIRST / WALK_FIRST name the first slot of an arena, not slots of their own)
+    slots = [getattr(WS, n) for n in regular if n not in ("LIST_FIRST", "WALK_FIRST")] + [WS.SLOTS, WS.ISECT_IDS]
+    assert sorted(slots) == list(range(WS.N_SLOTS))
+    assert 0 < WS.LIST_FIRST < WS.WALK_FIRST < WS.N_SLOTS
+    assert set(WS._DTYPES) <= set(slots)
+    # the size record: eight words, the flags where the guard writes them
+    assert [D["GS_INFO_" + n] for n in ("ISECTS", "BUCKETS", "MAX_TILE", "FLAGS", "COARSE", "MAX_BIN", "LIVE", "ONE_ROUND")] == list(range(D["GS_INFO_WORDS"]))
+
+
+# ---- the call sites ----
+
+def _python_sources():
+    files = sorted(glob.glob(os.path.join(ROOT, "easy_gaussian_splatting_amd", "*.py")) + glob.glob(os.path.join(ROOT, "tests", "*.py"))
+                   + glob.glob(os.path.join(ROOT, "tools", "*.py")) + [os.path.join(ROOT, "bench.py")])
+    assert len(files) > 40
+    return files
+
+
+def _tuple_literal(tree: ast.AST, name: str, before_line: int):
+    """The tuple literal last assigned to `name` (`name = (...)` or `name = lambda: (...)`) above `before_line`, or None."""
+    best = None
+    for node in ast.walk(tree):
+        if isinstance(node, ast.Assign) and node.lineno < before_line and any(isinstance(t, ast.Name) and t.id == name for t in node.targets):
+            value = node.value.body if isinstance(node.value, ast.Lambda) else node.value
+            if best is None or node.lineno > best[0]:
+                best = (node.lineno, value if isinstance(value, ast.Tuple) and not any(isinstance(e, ast.Starred) for e in value.elts) else None)
+    return best[1] if best else None
+
+
+def test_every_python_call_site_passes_the_headers_parameter_count():
+    """ctypes checks the count of a call against argtypes only when the call runs, and most of these calls run only on a GPU:
+    count the positional arguments of every `<lib>.gs_*(...)` call in the package, the tests, the tools and bench.py against the
+    header.  A call with a starred argument cannot be counted as it stands; where the starred name is a tuple literal of the same
+    file (the package's `args` / `bwd_args()`) its length is added, otherwise the call is left out -- and only a few may be."""
+    checked, left_out, wrong, starred_package = 0, [], [], 0
+    for path in _python_sources():
+        tree = ast.parse(open(path).read(), filename=path)
+        rel = os.path.relpath(path, ROOT)
+        for call in ast.walk(tree):
+            if not (isinstance(call, ast.Call) and isinstance(call.func, ast.Attribute) and call.func.attr in nat.SIGNATURES):
+                continue
+            name, where = call.func.attr, f"{rel}:{call.lineno}"
+            n, stars = len(call.args), [a.value for a in call.args if isinstance(a, ast.Starred)]
+            if call.keywords or len(stars) > 1:
+                left_out.append(where)
+                continue
+            if stars:
+                star = stars[0].func if isinstance(stars[0], ast.Call) and not stars[0].args else stars[0]
+                lit = _tuple_literal(tree, star.id, call.lineno) if isinstance(star, ast.Name) else None
+                if lit is None:
+                    left_out.append(where)
+                    continue
+                n += len(lit.elts) - 1
+                starred_package += rel.startswith("easy_gaussian_splatting_amd")
+            checked += 1
+            if n != len(nat.PARAMS[name]):
+                wrong.append(f"{where}: {name} called with {n} arguments, the header declares {len(nat.PARAMS[name])}: {', '.join(nat.PARAMS[name])}")
+    print(f"call sites: {checked} checked, {len(left_out)} left out {left_out}; starred package calls resolved: {starred_package}")
+    assert not wrong, "\n".join(wrong)
+    assert checked >= 200 and len(left_out) <= 10, (checked, left_out)
+    assert starred_package >= 4   # rendering.py: gs_project_bwd[_cam](*bwd_args(), ...); train_graph.py: gs_project_bwd_adam[_reg](*args, ...)

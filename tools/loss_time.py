@@ -26,10 +26,7 @@ mask = (torch.rand((H, W), device=dev, generator=g) < 0.05).float() if os.enviro
 mp = None if mask is None else mask.data_ptr()
 def load(name):
     path = nat.LIB_PATH if name == "product" else os.path.join(nat.VARIANT_DIR, f"libgsraster_{name}.so")
-    L = ct.CDLL(path)
-    for fn in ("gs_loss_workspace_floats", "gs_l1_ssim_fwd", "gs_l1_ssim_bwd"):
-        f = getattr(L, fn); f.restype, f.argtypes = nat.SIGNATURES[fn]
-    return L
+    return nat.bind(ct.CDLL(path), ("gs_loss_workspace_floats", "gs_l1_ssim_fwd", "gs_l1_ssim_bwd"))
 ref = None
 for name in names:
     L = load(name)

@@ -44,7 +44,7 @@ def rowsums(st):
 def geo(st):
     nat.check(L.gs_project_bwd(st, 1, N, K, int(m.active_sh_degree), _p(m.means), _p(m.quats), _p(m.log_scales), _p(m.sh_0), _p(m.sh_rest), 0,
               _p(b["viewmats"]), _p(b["Ks"]), W, H, 0.3, 0.01, 1e10, _p(b["radii"]), _p(b["colors_post"]), _p(b["tiles_per_gauss"]), _p(b["cum_tiles"]),
-              None, None, _p(gm), _p(gq), _p(gs_), _p(go), None, None, _p(b["v_abs"]), None, None, None, None, _p(m.logit_opacities), 1,
+              None, None, None, _p(gm), _p(gq), _p(gs_), _p(go), None, None, _p(b["v_abs"]), None, None, None, None, _p(m.logit_opacities), 1,
               _p(b["sh_jac"]), _p(row_sums), _p(gn), _p(cn)), "project_bwd(sums)")
     names = [grp["name"] for grp, _ in opt._plist]
     ns = len(names)
