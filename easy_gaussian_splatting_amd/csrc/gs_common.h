@@ -169,6 +169,60 @@ __device__ __forceinline__ float wave_reduce_add_dpp(float v) {
     return __builtin_bit_cast(float, __builtin_amdgcn_readlane(__builtin_bit_cast(int, v), 63));
 }
 
+// Sums of the colour quads (float4 2 of a 12-float gradient row: gs_blend_bwd / gs_blend_bwd_ch) of each lane's rows [r0, r0 + nr):
+// gs_channel_grads' channel gradients and gs_depth_grads' depth gradient.  The rows of consecutive Gaussians are contiguous (gs_blend_fwd's
+// row-base scan), so the wave's rows are ONE range, read 64 rows (an item) at a time, a row per lane.  An item that lies inside one
+// Gaussian's range -- and the run of such items behind it -- is summed per lane and closed by one DPP reduction; otherwise the item
+// is staged in LDS and every Gaussian adds its own rows of it in row order.  Fixed order: reproducible sums.
+__device__ __forceinline__ float4 quad_sums_wave(const float4* __restrict__ rows, int nr, int r0, float4* item) {
+    const int lane = lane_id();
+    const int incl = wave_incl_scan_add(nr);
+    const int o = incl - nr;
+    const int T = __builtin_amdgcn_readlane(incl, 63);
+    float4 s = make_float4(0.f, 0.f, 0.f, 0.f);
+    if (T == 0) return s;   // wave-uniform
+    const unsigned long long fb = __ballot(nr > 0);
+    const int R0 = __shfl(r0, __builtin_ctzll(fb), 64);
+    auto fetch = [&](int it) {
+        const int j = 64 * it + lane;
+        return j < T ? rows[3 * (int64_t)(R0 + j) + 2] : make_float4(0.f, 0.f, 0.f, 0.f);
+    };
+    const int n_items = (T + 63) >> 6;
+    float4 cur = fetch(0);
+    int it = 0;
+    while (it < n_items) {
+        const int jb = 64 * it;
+        const int lo = max(o, jb) - jb, hi = min(o + nr, jb + 64) - jb;   // this Gaussian's rows inside the item
+        const unsigned long long whole = __ballot(nr > 0 && lo == 0 && hi == 64);
+        if (whole) {   // wave-uniform
+            const int owner = __builtin_ctzll(whole);
+            const int last = (__shfl(o + nr, owner, 64) >> 6) - 1;   // the last item that is all this Gaussian's
+            float4 p = cur;
+#pragma unroll 4
+            for (int k = it + 1; k <= last; ++k) {
+                const float4 b = fetch(k);
+                p.x += b.x; p.y += b.y; p.z += b.z; p.w += b.w;
+            }
+            const float tx = wave_reduce_add_dpp(p.x), ty = wave_reduce_add_dpp(p.y), tz = wave_reduce_add_dpp(p.z),
+                        tw = wave_reduce_add_dpp(p.w);
+            if (lane == owner) { s.x += tx; s.y += ty; s.z += tz; s.w += tw; }
+            it = last + 1;
+            if (it < n_items) cur = fetch(it);
+            continue;
+        }
+        item[lane] = cur;
+        __builtin_amdgcn_wave_barrier();   // (LDS operations of one wave complete in issue order)
+        for (int r = max(lo, 0); r < hi; ++r) {
+            const float4 b = item[r];
+            s.x += b.x; s.y += b.y; s.z += b.z; s.w += b.w;
+        }
+        __builtin_amdgcn_wave_barrier();
+        ++it;
+        if (it < n_items) cur = fetch(it);
+    }
+    return s;
+}
+
 // Block-wide exclusive scan for blockDim.x <= 1024 (16 waves).  `scratch` >= 17 entries of T.
 template <typename T>
 __device__ __forceinline__ T block_excl_scan_add(T v, T* scratch, T* total) {

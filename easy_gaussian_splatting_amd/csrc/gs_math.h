@@ -566,4 +566,33 @@ GS_HD void make_camera(const float* V, const float* K, int W, int H, Camera& cam
     cam.half_h = 0.5f * (float)H;
 }
 
+// ---- depth render modes (gs_depth.hip) ----
+// The depth of a (camera, Gaussian) is the projection's camera-space z = A[2,:] . mean + t[2] (row 2 of the view matrix
+// [[A, t], [0, 1]]).  Its VJP for an upstream v_z: v_mean += v_z A[2,:] (fp32, accumulated in camera order on top of what the
+// projection backward left) ...
+GS_HD void depth_vjp_mean(float v_z, const float* view_row2, float* v_mean) {
+    v_mean[0] += v_z * view_row2[0];
+    v_mean[1] += v_z * view_row2[1];
+    v_mean[2] += v_z * view_row2[2];
+}
+// ... and, on request, the row-2 terms of v_viewmat: {v_A[2,0:3], v_t[2]} += {v_z mean, v_z} -- in fp64, like the other camera
+// terms: the sum over a camera's Gaussians is rounded once, at its end.
+GS_HD void depth_vjp_cam(float v_z, const float* mean, double* acc4) {
+    acc4[0] += (double)v_z * (double)mean[0];
+    acc4[1] += (double)v_z * (double)mean[1];
+    acc4[2] += (double)v_z * (double)mean[2];
+    acc4[3] += (double)v_z;
+}
+
+// Expected depth (gsplat's "ED" / "RGB+ED"): accumulated depth / clamp(alpha, min = 1e-10), torch's float32 arithmetic.
+constexpr float kEdAlphaFloor = 1e-10f;
+GS_HD float expected_depth(float acc, float alpha) { return acc / fmaxf(alpha, kEdAlphaFloor); }
+// Its VJP for an upstream v_out: v_acc = v_out / clamp(alpha); the clamp passes the gradient where alpha >= 1e-10 (equality
+// included, as torch's clamp backward does): v_alpha = -v_out acc / alpha^2 there, 0 below.
+GS_HD void expected_depth_vjp(float v_out, float acc, float alpha, float& v_acc, float& v_alpha) {
+    const float a = fmaxf(alpha, kEdAlphaFloor);
+    v_acc = v_out / a;
+    v_alpha = alpha >= kEdAlphaFloor ? -(v_out * ((acc / a) / a)) : 0.f;
+}
+
 }  // namespace gs

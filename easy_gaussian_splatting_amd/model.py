@@ -387,13 +387,18 @@ class GaussianModel(nn.Module):
         #  sizes what the walk leaves from a fresh probe instead of from the steps before, train_graph.TrainStepGraph.step)
         self.opacity_resets = getattr(self, "opacity_resets", 0) + 1
 
-    def forward(self, data: Dict[str, Any], clamp: bool = True) -> Dict[str, Optional[Tensor]]:
+    def forward(self, data: Dict[str, Any], clamp: bool = True, depth: Optional[str] = None) -> Dict[str, Optional[Tensor]]:
         """`clamp=False` returns the un-clamped image for `LossComputer(clamp_input=True)` (the clamp of
         /root/reference/model/gaussian.py:368 then happens inside the loss kernels).
+        `depth="D"` / `"ED"` renders `render_mode="RGB+D"` / `"RGB+ED"` and adds `"render_depth"` ([H, W, 1]: the accumulated /
+        the expected camera-space depth, differentiable; never clamped) to the returned dict.  GPU and eager loop only, not with
+        `sh_grads = "colors_pre"` (`rasterization()` refuses that); the default is the call as it was.
         A `data["w2c"]` that requires grad (e.g. from `pose.CameraDeltas`) receives its gradient: the render is then asked for
         camera gradients (`rasterization(_camera_grads=True)`).  Eager loop only: `TrainStepGraph` refuses such a `w2c`, and a
         model with `sh_grads = "colors_pre"` (`ViewParallelStep` with its exchange on) is refused by `rasterization()`."""
         w2c = data["w2c"]
+        if depth not in (None, "D", "ED"):
+            raise ValueError(f"depth: None, 'D' or 'ED', got {depth!r}")
         # on the GPU the raw parameters go in and exp / sigmoid happen inside the projection kernels
         raw = self.means.is_cuda and getattr(self, "fuse_activations", True)
         batch_render_imgs, _, meta = rasterization(
@@ -420,15 +425,22 @@ class GaussianModel(nn.Module):
             _grad_out=self.grad_out() if callable(getattr(self, "grad_out", None)) else None,
             _view_payload=self.view_payload() if callable(getattr(self, "view_payload", None)) else None,
             _camera_grads=bool(w2c.requires_grad),
+            **({} if depth is None else {"render_mode": "RGB+" + depth}),
         )
         render_img = batch_render_imgs.squeeze(0)   # (a view both ways: `[0]` would cost a zero-fill + copy in backward)
+        render_depth = None
+        if depth is not None:
+            render_img, render_depth = render_img[..., :3], render_img[..., 3:]
         if clamp:
             render_img = clamp01(render_img)
-        return {
+        out = {
             "render_img": render_img,  # [H, W, 3]
             "batch_xys": meta["means2d"],  # [1, N, 2]
             "batch_radii": meta["radii"],  # [1, N]
         }
+        if depth is not None:
+            out["render_depth"] = render_depth  # [H, W, 1]
+        return out
 
     @torch.no_grad()
     def update_statistics(self, data: Dict[str, Any], model_output: Dict[str, Tensor]):

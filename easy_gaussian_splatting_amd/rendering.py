@@ -509,6 +509,15 @@ def _forward_stages(means, quats, scales, opacities, colors, colors_rest, viewma
     # colour channels: 3 (SH colours, and RGB features) is the RGB path as it stands; 1, 2 or 4 feature channels go through the
     # channel entry points (gs_rec_colors, gs_blend_fwd_ch / gs_blend_bwd_ch, gs_channel_grads), always in one depth round
     ch = 3 if sh_degree is not None else int(colors.shape[-1])
+    # depth render modes (gs_raster.h "Depth render modes"): the projection's depths as one more channel behind the dc colour
+    # channels ("append": RGB+D / RGB+ED), or alone ("only": D / ED -- geometry-only projection, no SH colour); one depth round
+    dmode = cfg.get("depth")
+    dc = ch
+    if dmode == "only":
+        deg, K, per_cam, dc = -1, 0, 0, 0
+    if dmode:
+        ch = dc + 1
+    split_project = _SPLIT_PROJECT and not dmode
 
     # what escapes to the caller through `meta` is allocated per call; everything else is workspace
     radii = torch.empty((C, N), **i32)
@@ -531,7 +540,7 @@ def _forward_stages(means, quats, scales, opacities, colors, colors_rest, viewma
     # depth rounds: inference, one camera, long lists (see ROUNDS_MIN_LISTED above); the decision of a call shape is taken from
     # what its one-round calls listed and kept (a two-round call reports the short total of its two rounds)
     rmode = cfg.get("rounds") or rounds_mode()
-    rounds = (not need_grad) and C == 1 and N > 0 and ch == 3 and rmode != "off" and (rmode == "on" or (
+    rounds = (not need_grad) and C == 1 and N > 0 and ch == 3 and not dmode and rmode != "off" and (rmode == "on" or (
         two_level and int(hint.get("n", -1)) == N and int(hint.get("listed_one_round", 0)) >= ROUNDS_MIN_LISTED and not hint.get("rounds_off")))
     rb = _round_buffers(dev, st, N, tiles) if rounds else None
     eager_ids = os.environ.get("GS_EAGER_ISECT_IDS") == "1"   # (default: meta builds isect_ids on first access, _LazyMeta)
@@ -620,12 +629,15 @@ def _forward_stages(means, quats, scales, opacities, colors, colors_rest, viewma
     # 3. SH colours; 4. lists + blend, speculatively; 5. only now the host looks at the sizes.
     # (one launch for geometry + colour: since the list stages no longer wait for the host, a colour pass of its own behind
     #  the tile count hides nothing, and the fused launch is 25 us shorter than the two -- GS_FWD_SPLIT=1 keeps the split)
-    if ch == 3:
-        project(1 if _SPLIT_PROJECT else 0, "gs_project_fwd")
+    if dc == 3:
+        project(1 if split_project else 0, "gs_project_fwd")
     else:   # geometry, then the colour quad of the records from the D-channel features
         project(1, "gs_project_fwd")
-        _stage("gs_rec_colors", dev, lambda: nat.check(L.gs_rec_colors(st, C, N, ch, _ptr(colors), per_cam, _ptr(radii), P(WS.REC)),
-                                                       "gs_rec_colors"))
+        if dc > 0:
+            _stage("gs_rec_colors", dev, lambda: nat.check(L.gs_rec_colors(st, C, N, dc, _ptr(colors), per_cam, _ptr(radii), P(WS.REC)),
+                                                           "gs_rec_colors"))
+    if dmode:   # lane dc of the colour quad: the depth
+        _stage("gs_rec_depth", dev, lambda: nat.check(L.gs_rec_depth(st, C, N, dc, _ptr(depths), _ptr(radii), P(WS.REC)), "gs_rec_depth"))
     sizes = {"attempt": 0, "waited": 0, "info": None}   # (mutable: the deferred check finishes this call after it returned)
     tstream = torch.cuda.current_stream(dev)            # (the stream `st` belongs to: a late repair runs on it, whoever calls)
 
@@ -642,7 +654,7 @@ def _forward_stages(means, quats, scales, opacities, colors, colors_rest, viewma
                 # enqueue the back round at all when there are none (18 launches that would return at once: 0.1 ms per frame).
                 # Deferred check: both rounds are enqueued, the size record is the back round's (the total of both; a back round
                 # with no live tile leaves the front round's record standing).
-                if sizes["attempt"] == 0 and _SPLIT_PROJECT:
+                if sizes["attempt"] == 0 and split_project:
                     project(2, "gs_project_fwd_color")
                 nat.check(L.gs_round_split(st, N, _ptr(depths), P(WS.TILES_PER_GAUSS), ROUND_FRACTION, rb["hist"].data_ptr(), rb["blk"].data_ptr()),
                           "gs_round_split")
@@ -672,7 +684,7 @@ def _forward_stages(means, quats, scales, opacities, colors, colors_rest, viewma
             nat.check(L.gs_info_mirror_set(None), "gs_info_mirror_set")
             ev = torch.cuda.Event()
             ev.record(tstream)
-            if sizes["attempt"] == 0 and _SPLIT_PROJECT and ch == 3:
+            if sizes["attempt"] == 0 and split_project and ch == 3:
                 project(2, "gs_project_fwd_color")
             lists_and_blend()
         finally:
@@ -824,7 +836,7 @@ def _forward_stages(means, quats, scales, opacities, colors, colors_rest, viewma
     })
     if not lazy_ref:
         meta._lease = ref   # (the list lazies above read the arenas; in the "gsplat" mode nothing in meta does)
-    state = dict(C=C, N=N, K=K, deg=deg, per_cam=per_cam, ch=ch, sh_jac=use_jac, n_isects=n_isects, n_buckets=n_buckets, radii=radii, lease=lease,
+    state = dict(C=C, N=N, K=K, deg=deg, per_cam=per_cam, ch=ch, dc=dc, dmode=dmode, sh_jac=use_jac, n_isects=n_isects, n_buckets=n_buckets, radii=radii, lease=lease,
                  lease_ref=WS.LeaseRef(lease) if need_grad else None, factorised=factorised, pending=pending, late=state_late,
                  walk=walk, hint_key=hint_key, backgrounds=backgrounds)
     if pending is not None:
@@ -915,13 +927,21 @@ class _Rasterize(torch.autograd.Function):
         # would pin two full workspaces -- but by the saved tensors (`rasterization()` installs a pack hook that
         # attaches it): the engine drops those when a backward without retain_graph has finished, or when the graph dies.
         holder.lease_ref = state.pop("lease_ref")
-        holder.out_ptrs = (render_colors.data_ptr(), render_alphas.data_ptr())
+        out_colors = render_colors
+        if cfg.get("expected_depth"):
+            # ED: the node hands out the image with its last channel normalised by the alphas and keeps the accumulated one --
+            # the blend backward forms "total - prefix" from it
+            out_colors = torch.empty_like(render_colors)
+            _stage("gs_expected_depth_fwd", means.device, lambda: nat.check(nat.lib().gs_expected_depth_fwd(
+                _stream(means.device), render_alphas.numel(), state["ch"], _ptr(render_colors), _ptr(render_alphas), _ptr(out_colors)),
+                "gs_expected_depth_fwd"))
+        holder.out_ptrs = (out_colors.data_ptr(), render_alphas.data_ptr())
         ctx.cfg, ctx.holder, ctx.state = cfg, holder, state
         ctx.split = colors_rest is not None
         if need_grad:
             extra = (colors_rest,) if ctx.split else ()
             ctx.save_for_backward(means, quats, scales, colors, viewmats, Ks, render_colors, render_alphas, opacities, *extra)
-        return render_colors, render_alphas
+        return out_colors, render_alphas
 
     @staticmethod
     def backward(ctx, v_render_colors, v_render_alphas):
@@ -948,7 +968,14 @@ class _Rasterize(torch.autograd.Function):
         n_rows = _settle_walk(s, cfg, render_colors, render_alphas)
         # scratch for the backward's fill classes (gs_raster.h; a caching-allocator block, re-used stream-ordered)
         ucls = torch.empty((int(L.gs_unit_classes_ints(lease.layout.cap_units, C, W, H)),), dtype=torch.int32, device=dev) if _BWD_CLASSES else None
-        ch = s["ch"]
+        ch, dc, dmode = s["ch"], s["dc"], s["dmode"]
+        if cfg.get("expected_depth"):
+            # (v_out, v_alphas) -> the gradients of the accumulated image and the alphas the blend backward takes
+            v_out, v_ra_in = v_rc, v_ra
+            v_rc, v_ra = torch.empty_like(render_colors), torch.empty_like(render_alphas)
+            _stage("gs_expected_depth_bwd", dev, lambda: nat.check(L.gs_expected_depth_bwd(
+                st, render_alphas.numel(), ch, _ptr(render_colors), _ptr(render_alphas), _ptr(v_out), _ptr(v_ra_in), _ptr(v_rc), _ptr(v_ra)),
+                "gs_expected_depth_bwd"))
         if ch == 3:
             _stage("gs_blend_bwd", dev, lambda: nat.check(L.gs_blend_bwd(st, C, W, H, P(WS.REC), P(WS.QLIST), P(WS.QCNT),
                                      P(WS.UNIT_DESC), lease.layout.cap_units, P(WS.CKPT), P(WS.QMASK), P(WS.ROW_BASE), P(WS.WALK_STATE),
@@ -968,11 +995,12 @@ class _Rasterize(torch.autograd.Function):
         v_quats = go["quats"] if "quats" in go else torch.empty((N, 4), **f32)
         v_scales = go["scales"] if "scales" in go else torch.empty((N, 3), **f32)
         v_opac = go["opacities"] if "opacities" in go else torch.empty((N,), **f32)
-        v_colors = None if factorised else torch.empty(colors.shape, **f32)
+        v_colors = None if (factorised or dmode == "only") else torch.empty(colors.shape, **f32)
         # D != 3 feature channels: gs_project_bwd gives the geometry gradients (its colour output, [C,N,3] scratch, is not used) and
-        # gs_channel_grads the channel gradients from the rows' colour quads
-        v_pc, pc_cam = (v_colors, s["per_cam"]) if ch == 3 else (torch.empty((C, N, 3), **f32), 1)
-        v_rest = torch.empty(colors_rest.shape, **f32) if (ctx.split and not factorised) else None
+        # gs_channel_grads the channel gradients from the rows' colour quads.  (A depth mode's depth lane sits behind the dc colour
+        # channels: three colours keep gs_project_bwd as their source, "D" / "ED" have none.)
+        v_pc, pc_cam = (v_colors, s["per_cam"]) if dc == 3 else (torch.empty((C, N, 3), **f32), 1)
+        v_rest = torch.empty(colors_rest.shape, **f32) if (ctx.split and not factorised and dmode != "only") else None
         v_pre = row_sums = None
         if factorised:
             # Row sums as a pass of their own (gs_row_sums): they yield the colour gradient other ranks need -- and, with
@@ -1026,10 +1054,20 @@ class _Rasterize(torch.autograd.Function):
                                                             "gs_project_bwd_cam"))
         else:
             _stage("gs_project_bwd", dev, lambda: nat.check(L.gs_project_bwd(*bwd_args()), "gs_project_bwd"))
-        if ch != 3:
+        if dc != 3 and dc > 0:
             _stage("gs_channel_grads", dev, lambda: nat.check(L.gs_channel_grads(
-                st, C, N, ch, s["per_cam"], _ptr(s["radii"]), P(WS.TILES_PER_GAUSS), P(WS.CUM_TILES), P(WS.ROWS), P(WS.ROW_BASE),
+                st, C, N, dc, s["per_cam"], _ptr(s["radii"]), P(WS.TILES_PER_GAUSS), P(WS.CUM_TILES), P(WS.ROWS), P(WS.ROW_BASE),
                 P(WS.QMASK), _ptr(v_colors)), "gs_channel_grads"))
+        if dmode:
+            # the depth lane's gradient: to v_means (on top of the projection's, in camera order) and -- camera gradients -- to row 2
+            # of v_viewmats (fp64 partials: scratch of this backward alone)
+            v_dep = torch.empty((C, N), **f32) if dbg is not None else None
+            dpart = torch.empty((int(L.gs_depth_partials_doubles(C, N)),), dtype=torch.float64, device=dev) if (ctx.camera_grads and N > 0) else None
+            _stage("gs_depth_grads", dev, lambda: nat.check(L.gs_depth_grads(
+                st, C, N, dc, _ptr(means), _ptr(viewmats), _ptr(s["radii"]), P(WS.TILES_PER_GAUSS), P(WS.CUM_TILES), P(WS.ROWS), P(WS.ROW_BASE),
+                P(WS.QMASK), _ptr(v_means), _ptr(v_dep), _ptr(dpart), _ptr(v_viewmats) if dpart is not None else None), "gs_depth_grads"))
+            if dbg is not None:
+                dbg["v_depths"] = v_dep
         if holder.grad_out is not None:
             holder.grad_out["_written"] = True   # (the caller's own dict: it can tell that its tensors were filled by THIS backward)
         if dbg is not None:
@@ -1046,8 +1084,8 @@ class _Rasterize(torch.autograd.Function):
         ni = ctx.needs_input_grad
         return (v_means if (ni[0] and "means" not in go) else None, v_quats if (ni[1] and "quats" not in go) else None,
                 v_scales if (ni[2] and "scales" not in go) else None,
-                v_opac if (ni[3] and "opacities" not in go) else None, v_colors if (ni[4] and not factorised) else None,
-                v_rest if (ctx.split and ni[5] and not factorised) else None,
+                v_opac if (ni[3] and "opacities" not in go) else None, v_colors if (ni[4] and v_colors is not None) else None,
+                v_rest if (ctx.split and ni[5] and v_rest is not None) else None,
                 v_viewmats, None, None, None, None, v_campos if (len(ni) > 11 and ni[11]) else None)
 
 
@@ -1143,8 +1181,16 @@ def rasterization(
     Colour features (`sh_degree=None`): `colors` [N,D] or [C,N,D] with D in 1..4, `backgrounds` [C,D]; gsplat's semantics -- no
     clamp, background added as (1 - alpha) * bg per channel, gradients to means, quats, scales, opacities, colours and `.absgrad`.
     D = 3 is the RGB path; D = 1, 2, 4 go through the channel entry points (include/gs_raster.h), always in ONE depth round
-    whatever `_rounds` / GS_ROUNDS say.  D > 4 raises `NotImplementedError` (no `channel_chunk` splitting).  A depth map is a
-    channel: INTEGRATION.md "Depth as a channel".  `meta["means2d"]`
+    whatever `_rounds` / GS_ROUNDS say.  D > 4 raises `NotImplementedError` (no `channel_chunk` splitting).
+
+    `render_mode` (gsplat's): "RGB+D" / "RGB+ED" append the projection's camera-space depth (`meta["depths"]`) as one last channel
+    to the colours -- SH colours after the clamp, or Dc <= 3 feature channels -- and return [C,H,W,Dc+1]; `backgrounds` stays
+    [C,Dc], the depth's background is 0.  "D" / "ED" render the depth alone, [C,H,W,1]: colours are not evaluated and receive no
+    gradient, a given `backgrounds` is replaced by zero.  "ED" modes divide that channel by `render_alphas.clamp(min=1e-10)` (an
+    uncovered pixel yields 0; the gradient goes to the accumulated depth and to the alphas).  The depth is differentiable w.r.t.
+    `means` and, with `_camera_grads=True`, `viewmats`.  One depth round, the immediate size check, HIP tensors only; not together
+    with `_sh_grads="colors_pre"`, `_grad_out` or `_view_payload` (`ValueError`).  INTEGRATION.md "Depth as a channel".
+    `meta["means2d"]`
     receives the attribute `.absgrad` ([C,N,2]) during backward when `absgrad=True`, and -- a leaf that requires grad whenever
     the render does -- `.grad` = dL/d means2d ([C,N,2]; gsplat: after `meta["means2d"].retain_grad()`, a no-op here);
     `meta["radii"]` is int32 [C,N] with `> 0` marking visible Gaussians.
@@ -1239,8 +1285,13 @@ def rasterization(
         assert backgrounds.shape == (C, 3 if sh_degree is not None else colors.shape[-1]), backgrounds.shape
     if packed:
         raise NotImplementedError("packed=True is not implemented (the reference passes packed=False)")
-    if render_mode != "RGB":
-        raise NotImplementedError("only render_mode='RGB' is implemented")
+    depth = {"RGB": None, "D": "only", "ED": "only", "RGB+D": "append", "RGB+ED": "append"}[render_mode]
+    if depth == "append" and sh_degree is None and colors.shape[-1] + 1 > 4:
+        raise NotImplementedError(f"colour features of at most 4 channels are implemented on the HIP path (got {colors.shape[-1]} plus "
+                                  f"the depth channel of render_mode={render_mode!r}; channel_chunk splitting is not implemented)")
+    if depth and (_sh_grads == "colors_pre" or _grad_out is not None or _view_payload is not None):
+        raise ValueError(f"render_mode={render_mode!r} cannot be combined with _sh_grads='colors_pre', _grad_out or _view_payload "
+                         "(the view-parallel record has no place for a depth gradient)")
     if rasterize_mode != "classic":
         raise NotImplementedError("only rasterize_mode='classic' is implemented")
     if tile_size != _TILE:
@@ -1258,6 +1309,9 @@ def rasterization(
         raise ValueError("_camera_grads cannot be combined with _sh_grads='colors_pre', _grad_out or _view_payload "
                          "(the view-parallel step has no place for a camera gradient)")
     if not means.is_cuda:
+        if depth:   # (a NotImplementedError, which is a RuntimeError: callers that probed for the depth modes keep their handler)
+            raise NotImplementedError(f"render_mode={render_mode!r} runs on the GPU only: tensors must live on a HIP device "
+                                      "(there is no CPU fallback in this package)")
         raise RuntimeError("rasterization() runs on the GPU only: tensors must live on a HIP device "
                            "(there is no CPU fallback in this package)")
     nat.lib()  # fail loudly here if the extension is missing
@@ -1279,12 +1333,17 @@ def rasterization(
     rest_c = None if colors_rest is None else prep(colors_rest)
     viewmats_c, Ks_c = prep(viewmats), prep(Ks)
     bg_c = None if backgrounds is None else prep(backgrounds)
+    if depth == "only":
+        bg_c = None   # (gsplat: the depth alone has no background)
+    elif depth and bg_c is not None:
+        bg_c = torch.cat([bg_c, bg_c.new_zeros((C, 1))], dim=1)   # (the depth channel's background is 0)
+    expected = render_mode in ("ED", "RGB+ED")
     cfg = dict(width=int(width), height=int(height), near_plane=float(near_plane),
                far_plane=float(far_plane), radius_clip=float(radius_clip), eps2d=float(eps2d),
                sh_degree=sh_degree, tile_culling={"gsplat": 1, "tight": 1, "gsplat_eager": 0}[_tile_culling],
                lazy_ref_lists=_tile_culling == "gsplat", sh_grads=_sh_grads,
                activations={"none": 0, "exp_sigmoid": 1}[_activations], grad_enabled=torch.is_grad_enabled(),
-               defer_size_check=size_check == "deferred", rounds=_rounds,
+               defer_size_check=size_check == "deferred" and not expected, rounds=_rounds, depth=depth, expected_depth=expected,
                camera_grads=bool(_camera_grads and viewmats.requires_grad and torch.is_grad_enabled()))
     if _sh_grads not in ("dense", "colors_pre") or (_sh_grads == "colors_pre" and sh_degree is None):
         raise ValueError("_sh_grads: 'dense', or 'colors_pre' together with sh_degree")
@@ -1297,7 +1356,7 @@ def rasterization(
         raise ValueError("_view_payload needs _sh_grads='colors_pre'")
     # camera gradients with direction-dependent colours: the camera centre as a graph tensor (see _Rasterize.forward)
     campos = None
-    if cfg["camera_grads"] and sh_degree is not None and sh_degree >= 1:
+    if cfg["camera_grads"] and sh_degree is not None and sh_degree >= 1 and depth != "only":
         campos = torch.linalg.inv(viewmats_c)[:, :3, 3].contiguous()
     # (pack hook: every tensor the node saves for backward carries the workspace lease -- see _Rasterize.forward)
     with torch.cuda.device(means.device), torch.autograd.graph.saved_tensors_hooks(_lease_pack_hook(holder), lambda p: p[0]):

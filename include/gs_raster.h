@@ -479,6 +479,40 @@ int gs_project_bwd_cam(void* stream, int C, int64_t N, int K, int sh_degree, con
                        float* stat_grad_norm, float* stat_count, double* cam_partials, float* v_viewmats,
                        float* v_campos);
 
+/* Depth render modes (gsplat's render_mode "D", "ED", "RGB+D", "RGB+ED").  The depth of a (camera, Gaussian)
+ * is gs_project_fwd's depths[C,N] (camera-space z); it is blended as ONE MORE colour channel, lane j = Dc of the record's colour
+ * quad behind Dc = 0 .. 3 colour channels, by gs_blend_fwd (Dc + 1 == 3) or gs_blend_fwd_ch, whose background for that channel is
+ * 0.  A call sequence ("RGB+D" with SH colours: j = 3; "D": j = 0 behind gs_project_fwd(stage = 1)):
+ *   forward   gs_project_fwd [, gs_rec_colors], gs_rec_depth, the list stages, the blend at Dc + 1 channels [, gs_expected_depth_fwd]
+ *   backward  [gs_expected_depth_bwd,] the blend backward, gs_project_bwd / gs_project_bwd_cam [, gs_channel_grads(channels = Dc)],
+ *             gs_depth_grads
+ * One depth round only: gs_rec_depth and gs_depth_grads refuse gs_rounds_set phases other than 0.  Every entry point checks its
+ * lane / channel range, its pointers and their alignment before it launches anything.
+ * gs_rec_depth: rec[C*N*12] float 8 + lane = depths[f] for the Gaussians with radii > 0; lane = 0 writes the whole quad (z, 0, 0, 0)
+ *   -- the geometry-only projection leaves it unwritten --, lanes 1..3 that float alone.  rec 16-byte aligned.
+ * gs_depth_grads (behind gs_project_bwd / gs_project_bwd_cam): v_z of each (camera, Gaussian) = the sum of float 8 + lane of its
+ *   gradient rows (gathered as gs_channel_grads gathers them: fixed order, no atomics); v_means[N,3] += v_z * viewmats[c][2][0:3] in
+ *   camera order; v_depths[C,N] (optional, may be NULL) = v_z, 0 for culled Gaussians.  With v_viewmats[C,4,4] and cam_partials
+ *   (both or neither; cam_partials: gs_depth_partials_doubles(C, N) doubles of scratch, 8-byte aligned, contents undefined before and
+ *   after) the depth's dependence on the view matrix is ADDED to what gs_project_bwd_cam wrote: v_viewmats[c][2][0:3] += sum_n v_z
+ *   means[n], v_viewmats[c][2][3] += sum_n v_z -- fp64 partials per block, one block per camera adding them in a fixed order, only
+ *   the final sums rounded to fp32: two calls give the same bits.  rows / qmask 16-byte aligned.  Honours the step guard.
+ * gs_expected_depth_fwd: out_colors[n_pixels][channels] = acc_colors with its LAST channel divided by max(alphas[p], 1e-10) (torch's
+ *   clamp(min = 1e-10); an uncovered pixel yields 0); the other channels are copied.
+ * gs_expected_depth_bwd: the VJP of that: v_colors = v_out with its last channel divided by max(alpha, 1e-10); v_alphas[p] =
+ *   v_alphas_in[p] (may be NULL: 0) - v_out[last] * acc[last] / alpha^2 where alpha >= 1e-10 (equality included, as torch's clamp
+ *   backward), + 0 below.  (v_colors, v_alphas) are what the blend backward takes, acc_colors what the blend forward wrote.
+ *   Images of 2 / 4 channels are read as 8- / 16-byte pixels and must be aligned so. */
+int gs_rec_depth(void* stream, int C, int64_t N, int lane, const float* depths, const int32_t* radii, float* rec);
+size_t gs_depth_partials_doubles(int C, int64_t N);
+int gs_depth_grads(void* stream, int C, int64_t N, int lane, const float* means, const float* viewmats, const int32_t* radii,
+                   const int32_t* tiles_per_gauss, const int32_t* cum_tiles, const float* rows, const int32_t* row_base,
+                   const uint8_t* qmask, float* v_means, float* v_depths, double* cam_partials, float* v_viewmats);
+int gs_expected_depth_fwd(void* stream, int64_t n_pixels, int channels, const float* acc_colors, const float* alphas,
+                          float* out_colors);
+int gs_expected_depth_bwd(void* stream, int64_t n_pixels, int channels, const float* acc_colors, const float* alphas,
+                          const float* v_out, const float* v_alphas_in, float* v_colors, float* v_alphas);
+
 /* Row e (view sharding): the row sums of every Gaussian as a pass of its own, and from them everything another rank needs of
  * this view before the long projection backward runs.  row_sums[C*N][12] = the 11 sums gs_project_bwd forms first (same
  * function, same bits; 12th float 0; rows of culled Gaussians are left unwritten) -> gs_project_bwd(..., row_sums);
