@@ -7,8 +7,10 @@ Public surface (mirrors the reference's names for this path):
   model.GaussianModel       -- the reference's `forward(data)` / `update_statistics` harness
   loss.LossComputer         -- L1 + (1 - SSIM) as the reference's train step uses
   distributed               -- one-view-per-GPU gradient all-reduce over RCCL
+  evaluate.Evaluator        -- the reference's held-out evaluation (eval.py): PSNR / SSIM from one fused kernel per view
 """
+from .evaluate import Evaluator, evaluate_output, image_metrics  # noqa: F401
 from .rendering import rasterization  # noqa: F401
 
-__all__ = ["rasterization"]
+__all__ = ["rasterization", "Evaluator", "image_metrics", "evaluate_output"]
 __version__ = "0.1.0"

@@ -18,26 +18,11 @@
 // LDS instead of 71 / 38 KB, block-uniform bases with 32-bit byte offsets instead of 64-bit index arithmetic per element, the
 // window taps as literal operands, whole-pixel global accesses and four moment maps instead of five in the forward.
 // Pure HBM-streaming + LDS stencil work; no atomics.
-#include "gs_common.h"
+#include "gs_loss_tile.h"
 
 namespace gs {
 
-constexpr int kLT = 32;               // tile edge (outputs)
-constexpr int kHalo = 5;
-constexpr int kLR = kLT + 2 * kHalo;  // 42 staged rows / cols
-constexpr int kLRP = kLR + 1;         // padded row stride of the staged tiles
-constexpr int kHP = kLT + 1;          // row stride of the horizontal-pass buffers
-static_assert(kLT * (kLT / 4) == 256 && kLR * 6 <= 256 && kLR % 6 == 0, "thread mapping of the staging and the separable passes");
-static_assert(kLR % 2 == 0 && kLR * 3 <= 128, "backward staging: two 128-thread halves, one staged row each");
-constexpr int64_t kLossMaxPixels = (int64_t)1 << 28;   // 12 bytes per pixel and plane under 2^32
-constexpr int kLossMaxWidth = 1 << 20;                 // a row's 12 W bytes under 2^24; the row INDEX is held under 2^24 by the entry points (24-bit multiplies)
 constexpr float kC1 = 0.01f * 0.01f, kC2 = 0.03f * 0.03f;
-
-// The window as compile-time constants: every tap is a LITERAL operand of its FMA.  From __constant__ memory the taps sat in
-// scalar registers, and a VALU instruction with a scalar-register source issues every 4.4 cycles on gfx950 against 3.0 with
-// vector-register or literal sources (tools/micro/valu_enc.hip) -- two thirds of these kernels' instructions.
-#define GS_WIN_TAPS {1.0283800845e-03f, 7.5987581352e-03f, 3.6000772128e-02f, 1.0936068951e-01f, 2.1300553771e-01f, \
-                     2.6601172486e-01f, 2.1300553771e-01f, 1.0936068951e-01f, 3.6000772128e-02f, 7.5987581352e-03f, 1.0283800845e-03f}
 
 struct LossArgs {
     int H, W;
@@ -51,32 +36,12 @@ struct LossArgs {
     float* v_render;                   // [H,W,3]
 };
 
-__device__ __forceinline__ int clampi(int v, int lo, int hi) { return v < lo ? lo : (v > hi ? hi : v); }
-// base + 32-bit BYTE offset: with a block-uniform base this is one global_load with a scalar base and a vector offset
-__device__ __forceinline__ float ld_off(const float* base, unsigned byte_off) {
-    return *reinterpret_cast<const float*>(reinterpret_cast<const char*>(base) + byte_off);
-}
 __device__ __forceinline__ void st_off(float* base, unsigned byte_off, float v) {
     *reinterpret_cast<float*>(reinterpret_cast<char*>(base) + byte_off) = v;
 }
 
-struct F3 { float x, y, z; };   // one pixel of a channel-last image / one pixel's three derivative maps: a 12-byte access
-__device__ __forceinline__ F3 ld3_off(const float* base, unsigned byte_off) {
-    return *reinterpret_cast<const F3*>(reinterpret_cast<const char*>(base) + byte_off);
-}
 __device__ __forceinline__ void st3_off(float* base, unsigned byte_off, float x, float y, float z) {
     *reinterpret_cast<F3*>(reinterpret_cast<char*>(base) + byte_off) = F3{x, y, z};
-}
-
-// Block -> tile.  Consecutive block ids go round-robin over the eight XCDs, each with its own L2: XCD x takes the contiguous
-// row-major run of tiles [x * per, (x + 1) * per) -- the halos neighbouring tiles share are met in that L2.
-__device__ __forceinline__ bool loss_tile(const LossArgs& a, int& x0, int& y0) {
-    const int ntx = (a.W + kLT - 1) / kLT, nt = ntx * ((a.H + kLT - 1) / kLT), per = (nt + 7) >> 3;
-    const int id = blockIdx.x, t = (id & 7) * per + (id >> 3);
-    if ((id >> 3) >= per || t >= nt) return false;
-    const int ty = t / ntx;
-    x0 = (t - ty * ntx) * kLT; y0 = ty * kLT;
-    return true;
 }
 
 // Block -> (tile, channel) for the backward kernel: the same XCD runs, the three channels of a tile one after the other on the
@@ -90,10 +55,6 @@ __device__ __forceinline__ bool loss_tile_channel(const LossArgs& a, int& x0, in
     x0 = (t - ty * ntx) * kLT; y0 = ty * kLT;
     return true;
 }
-
-// the separable window's horizontal pass over one staged row: thread = row x 6 output columns, register sliding window
-// (42 rows x 6 column groups; the last group starts at column 26 and recomputes two: 252 of the 256 threads work)
-constexpr int kHOut = 6, kHWin = kHOut + 10;
 
 // One block per tile.  The tile + halo of both images is requested ONCE, a whole pixel (12 bytes, three channels) per lane
 // and row: 7 + 7 (+ 7 mask) fully coalesced loads per thread; the three channels then take turns in the same 37 KB of LDS
@@ -425,9 +386,6 @@ extern "C" int gs_clamp01(void* stream, int64_t n, const float* x, const float* 
     GS_LAUNCH_CHECK("clamp01_kernel");
     return GS_OK;
 }
-
-static int loss_tile_count(int height, int width) { return ((width + kLT - 1) / kLT) * ((height + kLT - 1) / kLT); }
-static dim3 loss_grid(int nt) { return dim3((unsigned)(8 * ((nt + 7) / 8))); }   // see loss_tile()
 
 extern "C" size_t gs_loss_workspace_floats(int height, int width) {
     const size_t nb = (size_t)((width + kLT - 1) / kLT) * ((height + kLT - 1) / kLT);

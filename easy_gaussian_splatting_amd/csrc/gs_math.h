@@ -595,4 +595,38 @@ GS_HD void expected_depth_vjp(float v_out, float acc, float alpha, float& v_acc,
     v_alpha = alpha >= kEdAlphaFloor ? -(v_out * ((acc / a) / a)) : 0.f;
 }
 
+// ---- evaluation metrics (gs_metrics.hip) ----
+// SSIM of one window from its four moments: mu_x, mu_y, ess = E[xx] + E[yy] (SSIM sees the two only through their sum) and
+// exy = E[xy]; K1 = 0.01, K2 = 0.03, data_range 1 (torchmetrics' defaults, the statement of gs_loss.hip's forward).  The
+// denominators d1 >= C1, d2 >= C2 > 0 are far from any range a division's refinement steps guard: on the device the two
+// hardware reciprocals (1 ulp each), on the host plain division.
+// The three products of the means are rounded ON THEIR OWN (ssim_rounded: the library is built with -ffp-contract=fast, which
+// fuses a product into the sum that reads it whatever a pragma says).  Two identical images (mu_x == mu_y, ess == 2 exy, which the
+// window passes keep exact) then give n1 == d1 and n2 == d2 bit for bit -- the doublings and the differences of equal terms are
+// exact -- and the result is 1 to the reciprocals' rounding.  With the products fused, n2 and d2 differ by the rounding of mu^2
+// (6e-8), which a flat bright window divides by C2 = 9e-4: up to 7e-5 per window.  A host build (g++, no FMA contraction on its
+// default target) rounds every product anyway: the same arithmetic.
+constexpr float kSsimC1 = 0.01f * 0.01f, kSsimC2 = 0.03f * 0.03f;
+GS_HD float ssim_rcp(float d) {
+#if defined(__HIP_DEVICE_COMPILE__)
+    return __builtin_amdgcn_rcpf(d);
+#else
+    return 1.0f / d;
+#endif
+}
+// x as it is, hidden from the optimizer on the device (gs_common.h: fp_opaque): the product behind it is not fused into a sum
+GS_HD float ssim_rounded(float x) {
+#if defined(__HIP_DEVICE_COMPILE__)
+    asm volatile("" : "+v"(x));
+#endif
+    return x;
+}
+GS_HD float ssim_from_moments(float mu_x, float mu_y, float ess, float exy) {
+    const float pxy = ssim_rounded(mu_x * mu_y), pxx = ssim_rounded(mu_x * mu_x), pyy = ssim_rounded(mu_y * mu_y);
+    const float mm = pxx + pyy, sxy = exy - pxy;
+    const float n1 = 2.f * pxy + kSsimC1, n2 = 2.f * sxy + kSsimC2;   // (2 p is exact: fused or not, one rounding of the sum)
+    const float d1 = mm + kSsimC1, d2 = (ess - mm) + kSsimC2;
+    return (n1 * n2) * (ssim_rcp(d1) * ssim_rcp(d2));
+}
+
 }  // namespace gs

@@ -573,6 +573,17 @@ int gs_l1_ssim_bwd_slots(void* stream, int height, int width, float lambda_ssim,
                          const float* const* slots_dev, int clamp_input, const float* workspace,
                          const float* v_total, float* v_render);
 
+/* ---- evaluation metrics: what the reference's eval.py:45-55 takes from torchmetrics per held-out view ----
+ * render / gt are [H,W,3]; mask [H,W] may be NULL.  c = mask*gt + (1-mask)*render, with render clamped to [0,1] first when
+ * clamp_input != 0.  out2 = {mse, ssim}: mse = the mean of (c - gt)^2 over all H*W*3 elements (PeakSignalNoiseRatio(data_range=1.0)
+ * is 10 log10(1 / mse); a float data_range does not clamp), ssim = the mean SSIM over the (H-10) x (W-10) interior of the three
+ * channels, the statement gs_l1_ssim_fwd uses (the mean itself, not 1 - ssim).  Forward only and without atomics: the same inputs
+ * give the same bits (a NaN in a clamped render becomes 0, as in gs_l1_ssim_fwd).  workspace holds gs_metrics_workspace_floats(H,W) floats (two per launched block); every word of it that is
+ * read is written by the same call.  Sizes as for gs_l1_ssim_fwd: anything else is refused with GS_ERR_ARG before a launch. */
+size_t gs_metrics_workspace_floats(int height, int width);
+int gs_image_metrics(void* stream, int height, int width, const float* render, const float* gt, const float* mask,
+                     int clamp_input, float* workspace, float* out2);
+
 /* Row a-2: `torch.clamp(render, 0, 1)` of /root/reference/model/gaussian.py:368 as one pass.
  * v_out == NULL: out = clamp(x, 0, 1).  v_out != NULL: out = v_out where 0 <= x <= 1, else 0 (the
  * backward of that clamp).  n floats, 16-byte aligned buffers. */

@@ -1,12 +1,16 @@
 #!/usr/bin/env python3
 """Times gs_l1_ssim_fwd / gs_l1_ssim_bwd alone (HIP events, the bench resolution) for the product library and any variants:
-   tools/loss_time.py [H W] -- lib names after `--` are libgsraster_<name>.so files in build/variants/ (GS_ALLOW_VARIANT=1).
-Each variant's outputs are compared with the first library's (largest absolute difference of loss3 / maps-derived gradient)."""
+   tools/loss_time.py [--metrics] [H W] -- lib names after `--` are libgsraster_<name>.so files in build/variants/ (GS_ALLOW_VARIANT=1).
+Each variant's outputs are compared with the first library's (largest absolute difference of loss3 / maps-derived gradient).
+--metrics: also times gs_image_metrics (the evaluation's {mse, ssim}: the forward without its derivative maps) beside the forward,
+on the same cold inputs in the same run (`metrics_us`), and prints its two values next to the forward's 1 - ssim."""
 import ctypes as ct, json, os, sys
 ROOT = os.environ.get("GRAFT_REPO_ROOT", os.path.dirname(os.path.dirname(os.path.abspath(__file__)))); sys.path.insert(0, ROOT)
 import torch
 from easy_gaussian_splatting_amd import _native as nat
 args = sys.argv[1:]
+METRICS = "--metrics" in args
+args = [a for a in args if a != "--metrics"]
 names = ["product"]
 if "--" in args:
     i = args.index("--"); names += args[i + 1:]; args = args[:i]
@@ -26,7 +30,7 @@ mask = (torch.rand((H, W), device=dev, generator=g) < 0.05).float() if os.enviro
 mp = None if mask is None else mask.data_ptr()
 def load(name):
     path = nat.LIB_PATH if name == "product" else os.path.join(nat.VARIANT_DIR, f"libgsraster_{name}.so")
-    return nat.bind(ct.CDLL(path), ("gs_loss_workspace_floats", "gs_l1_ssim_fwd", "gs_l1_ssim_bwd"))
+    return nat.bind(ct.CDLL(path), ("gs_loss_workspace_floats", "gs_l1_ssim_fwd", "gs_l1_ssim_bwd") + (("gs_metrics_workspace_floats", "gs_image_metrics") if METRICS else ()))
 ref = None
 for name in names:
     L = load(name)
@@ -36,7 +40,12 @@ for name in names:
     fwd = lambda i=0: L.gs_l1_ssim_fwd(st, H, W, 0.2, renders[i].data_ptr(), gts[i].data_ptr(), mp, 1, ws.data_ptr(), out3.data_ptr())
     bwd = lambda i=0: L.gs_l1_ssim_bwd(st, H, W, 0.2, renders[i].data_ptr(), gts[i].data_ptr(), mp, 1, ws.data_ptr(), one.data_ptr(), v.data_ptr())
     res = {"lib": name}
-    for tag, fn in (("fwd_us", fwd), ("bwd_us", bwd)):
+    timed = [("fwd_us", fwd), ("bwd_us", bwd)]
+    if METRICS:
+        mws = torch.zeros((int(L.gs_metrics_workspace_floats(H, W)),), device=dev); out2 = torch.zeros((2,), device=dev)
+        met = lambda i=0: L.gs_image_metrics(st, H, W, renders[i].data_ptr(), gts[i].data_ptr(), mp, 1, mws.data_ptr(), out2.data_ptr())
+        timed += [("metrics_us", met), ("fwd_again_us", fwd)]   # (the forward on both sides of the metrics: the run's own spread)
+    for tag, fn in timed:
         for i in range(20): fn(i % NSETS)
         e0, e1 = torch.cuda.Event(enable_timing=True), torch.cuda.Event(enable_timing=True)
         e0.record()
@@ -49,4 +58,7 @@ for name in names:
     res["loss3"] = [float(x) for x in cur[0]]
     res["max_abs_diff_vs_first"] = [float((cur[0] - ref[0]).abs().max()), float((cur[1] - ref[1]).abs().max())]
     res["v_absmax"] = float(cur[1].abs().max())
+    if METRICS:
+        assert met() == 0
+        res["mask"] = mask is not None; res["metrics2"] = [float(x) for x in out2]
     print(json.dumps(res), flush=True)
