@@ -8,9 +8,12 @@ Public surface (mirrors the reference's names for this path):
   loss.LossComputer         -- L1 + (1 - SSIM) as the reference's train step uses
   distributed               -- one-view-per-GPU gradient all-reduce over RCCL
   evaluate.Evaluator        -- the reference's held-out evaluation (eval.py): PSNR / SSIM from one fused kernel per view
+  viewer.FrameRenderer      -- the viewer's render_func (launch_viewer.py) and the camera-path video export, finished on the device
 """
 from .evaluate import Evaluator, evaluate_output, image_metrics  # noqa: F401
 from .rendering import rasterization  # noqa: F401
+from .viewer import FrameRenderer, camera_interpolation, export_video, finish_frame, viewer_render_func  # noqa: F401
 
-__all__ = ["rasterization", "Evaluator", "image_metrics", "evaluate_output"]
+__all__ = ["rasterization", "Evaluator", "image_metrics", "evaluate_output", "FrameRenderer", "finish_frame", "camera_interpolation",
+           "export_video", "viewer_render_func"]
 __version__ = "0.1.0"

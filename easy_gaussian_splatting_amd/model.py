@@ -387,12 +387,15 @@ class GaussianModel(nn.Module):
         #  sizes what the walk leaves from a fresh probe instead of from the steps before, train_graph.TrainStepGraph.step)
         self.opacity_resets = getattr(self, "opacity_resets", 0) + 1
 
-    def forward(self, data: Dict[str, Any], clamp: bool = True, depth: Optional[str] = None) -> Dict[str, Optional[Tensor]]:
+    def forward(self, data: Dict[str, Any], clamp: bool = True, depth: Optional[str] = None,
+                alphas: bool = False) -> Dict[str, Optional[Tensor]]:
         """`clamp=False` returns the un-clamped image for `LossComputer(clamp_input=True)` (the clamp of
         /root/reference/model/gaussian.py:368 then happens inside the loss kernels).
         `depth="D"` / `"ED"` renders `render_mode="RGB+D"` / `"RGB+ED"` and adds `"render_depth"` ([H, W, 1]: the accumulated /
         the expected camera-space depth, differentiable; never clamped) to the returned dict.  GPU and eager loop only, not with
         `sh_grads = "colors_pre"` (`rasterization()` refuses that); the default is the call as it was.
+        `alphas=True` adds `"render_alpha"` ([H, W, 1]: the accumulated opacity `rasterization()` returns beside the image, which
+        the reference drops) -- what `viewer.FrameRenderer` masks a depth frame with.
         A `data["w2c"]` that requires grad (e.g. from `pose.CameraDeltas`) receives its gradient: the render is then asked for
         camera gradients (`rasterization(_camera_grads=True)`).  Eager loop only: `TrainStepGraph` refuses such a `w2c`, and a
         model with `sh_grads = "colors_pre"` (`ViewParallelStep` with its exchange on) is refused by `rasterization()`."""
@@ -401,7 +404,7 @@ class GaussianModel(nn.Module):
             raise ValueError(f"depth: None, 'D' or 'ED', got {depth!r}")
         # on the GPU the raw parameters go in and exp / sigmoid happen inside the projection kernels
         raw = self.means.is_cuda and getattr(self, "fuse_activations", True)
-        batch_render_imgs, _, meta = rasterization(
+        batch_render_imgs, batch_render_alphas, meta = rasterization(
             means=self.means,
             quats=self.quats,
             scales=self.log_scales if raw else self.scales,
@@ -440,6 +443,8 @@ class GaussianModel(nn.Module):
         }
         if depth is not None:
             out["render_depth"] = render_depth  # [H, W, 1]
+        if alphas:
+            out["render_alpha"] = batch_render_alphas.squeeze(0)  # [H, W, 1]
         return out
 
     @torch.no_grad()

@@ -584,6 +584,34 @@ size_t gs_metrics_workspace_floats(int height, int width);
 int gs_image_metrics(void* stream, int height, int width, const float* render, const float* gt, const float* mask,
                      int clamp_input, float* workspace, float* out2);
 
+/* ---- frame finishing: from a render to what a viewer shows or a video file holds, in one pass ----
+ * render is the un-clamped blend output [H,W,cin], contiguous; out is [out_height,out_width,3] with the image top-left and every
+ * other element zero (the reference's adjust_image_aspect, viewer/viewer_runtime.py:104-116).  gs_frame_finish writes EVERY
+ * element of out: nothing has to clear it first.
+ *   format GS_FRAME_F32: float, clamp(x, 0, 1) with torch.clamp's values (a NaN stays a NaN; -0 gives +0).
+ *          GS_FRAME_U8:  packed RGB bytes floor(fl32(clamp(x, 0, 1) * 255)): one rounded float32 product, then floor
+ *                        (RecordManager.export_video, viewer/utils.py:128-129); NaN gives 0, +inf gives 255.
+ *   mode   GS_FRAME_RGB:   channels 0-2 of a render with cin = 3 or 4 (alpha, range2 and alpha_min are not looked at).
+ *          GS_FRAME_DEPTH: channel cin - 1 of a render with cin = 4 (render_mode "RGB+D" / "RGB+ED") or 1 (a depth image), the
+ *                        alpha image [H,W] and the DEVICE pair range2 = {lo, hi}.  A pixel whose alpha is not >= alpha_min is 0;
+ *                        any other is g = 1 - clamp(t, 0, 1) on all three channels, t = (d - lo) / (hi - lo) in float32 and
+ *                        t = 0 where hi == lo (near is bright); the format then applies to g.
+ * gs_frame_range writes {lo, hi} = the min and max of that depth channel over the pixels with alpha >= alpha_min into range2
+ * (device, [2]); NaN depths are skipped; {0, 0} when no pixel is covered.  Two stages over the caller's workspace of
+ * gs_frame_workspace_floats(H, W) floats (every word read is written by the same call), fixed order, no atomics.
+ * Refused with GS_ERR_ARG before a launch: null pointers, non-positive sizes, out smaller than the render, a cin the mode does
+ * not take, an unknown mode or format, buffers that are not 16-byte aligned, and sizes whose byte counts (H*W*cin*4, the
+ * output's) do not fit 31 bits.  Neither entry looks at the step guard. */
+#define GS_FRAME_F32 0
+#define GS_FRAME_U8 1
+#define GS_FRAME_RGB 0
+#define GS_FRAME_DEPTH 1
+size_t gs_frame_workspace_floats(int height, int width);
+int gs_frame_range(void* stream, int height, int width, int cin, const float* render, const float* alpha, float alpha_min,
+                   float* workspace, float* range2);
+int gs_frame_finish(void* stream, int height, int width, int cin, const float* render, int mode, int format,
+                    const float* alpha, const float* range2, float alpha_min, int out_height, int out_width, void* out);
+
 /* Row a-2: `torch.clamp(render, 0, 1)` of /root/reference/model/gaussian.py:368 as one pass.
  * v_out == NULL: out = clamp(x, 0, 1).  v_out != NULL: out = v_out where 0 <= x <= 1, else 0 (the
  * backward of that clamp).  n floats, 16-byte aligned buffers. */
