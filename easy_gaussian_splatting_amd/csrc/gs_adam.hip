@@ -4,8 +4,14 @@
 // Parameters and both moments live in three flat fp32 buffers (segments padded to 16-byte quads);
 // the gradients stay where autograd put them (one tensor per segment, no accumulate-into-bucket
 // pass, no zero-fill pass).  The whole step is a single HBM-streaming kernel: 16 B/lane loads of
-// p, g, m, v and stores of p, m, v -- 28 B per element.  Same arithmetic as torch's
-// `_single_tensor_adam`:  denom = sqrt(v)/sqrt(1-beta2^t) + eps;  p -= (lr/(1-beta1^t)) * m/denom.
+// p, g, m, v and stores of p, m, v -- 28 B per element.  The form of torch's `_single_tensor_adam`:
+// denom = sqrt(v)/sqrt(1-beta2^t) + eps;  p -= (lr/(1-beta1^t)) * m/denom -- as Adam AT THE fp32 BETAS THE ABI RECEIVES:
+// the betas arrive as `float`, 1 - beta is formed in fp32 (exact for beta in [0.5, 1]) and the bias corrections come from
+// (double)beta, so the step is a self-consistent Adam at beta2' = fl32(0.999) = 0.99900001287.  Against that Adam in fp64
+// every path stays within the bounds of tests/adam_ref.py (4 eps32 on exp_avg, 6 eps32 on exp_avg_sq, eps32 |p| + 10 eps32 of
+// the update on the parameter; tests/test_gpu_adam_edges.py).  torch mixes three roundings of beta2 (fl32(0.999) decays,
+// fl32(0.001) increments, the double 0.999 corrects the bias): its exp_avg_sq lies at a relative 1.3e-5 from this one, which
+// is why a state_dict() exchanged with torch.optim.Adam continues the trajectory to 1e-5 and not to the bit.
 // A segment whose gradient pointer is NULL is skipped entirely (torch skips `p.grad is None`);
 // the view-parallel step uses that to update the SH segments and the geometry segments in two
 // launches of the same step (distributed.py).  `grad_scale` folds the 1/world of a mean over ranks in.

@@ -243,8 +243,11 @@ __device__ __forceinline__ T block_excl_scan_add(T v, T* scratch, T* total) {
     return res;
 }
 
-// One Adam update, torch's `_single_tensor_adam` arithmetic (gs_adam.hip; also applied in place by the fused
-// projection-backward + Adam kernel of gs_project.hip):  isbc2 = 1/sqrt(1-beta2^t),  ss = lr/(1-beta1^t).
+// One Adam update (gs_adam.hip; also applied in place by the fused projection-backward + Adam kernel of gs_project.hip and
+// by gs_sh_adam_views):  isbc2 = 1/sqrt(1-beta2^t),  ss = lr/(1-beta1^t), both formed on the host from (double)beta.
+// It is Adam at the fp32 betas the ABI receives: 1.f - b is exact for b in [0.5, 1], so decay and increment belong to one
+// beta.  Within the bounds of tests/adam_ref.py of that Adam in fp64; exp_avg_sq at a relative 1.3e-5 from torch's
+// `_single_tensor_adam`, whose increment is fl32(0.001) and not 1 - fl32(0.999) (gs_adam.hip's header).
 __device__ __forceinline__ void adam1(float& p, float g, float& m, float& v, float b1, float b2, float eps,
                                       float isbc2, float ss) {
     m = fmaf(b1, m, (1.f - b1) * g);

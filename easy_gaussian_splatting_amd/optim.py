@@ -7,6 +7,14 @@ keeps that interface (`param_groups[i]["name"]`, `["lr"]` -- what `update_learni
 buffers, so one step is ONE HBM-streaming HIP kernel (csrc/gs_adam.hip).  Gradients stay exactly
 where autograd put them: with `.grad` left `None` before `backward()` the rasterizer's own output
 tensors become the `.grad`s without an accumulate pass, and `zero_grad()` just drops them.
+
+What it computes: Adam at the fp32 betas the C ABI receives.  `beta1`, `beta2` and `eps` travel as `float`; the kernel forms
+`1 - beta` in fp32, which is exact, and the bias corrections come from `(double)beta` -- a self-consistent Adam at
+beta2' = fl32(0.999) = 0.99900001287.  Against that Adam in float64 one step stays within the bounds of `tests/adam_ref.py`
+(a few units of 2^-24 per quantity; `tests/test_gpu_adam_edges.py` holds every path to them).  `torch.optim.Adam` mixes three
+roundings of beta2 (fl32(0.999) for the decay, fl32(0.001) for the increment, the double 0.999 for the bias correction), so its
+`exp_avg_sq` lies at a relative 1.3e-5 from this one: a `state_dict()` exchanged with `torch.optim.Adam` continues the same
+trajectory to 1e-5, not to the bit.
 """
 from __future__ import annotations
 
