@@ -130,25 +130,52 @@ class GaussianModel(nn.Module):
         self.BACKGROUND = nn.Parameter(torch.full((3,), 1.0 if white_background else 0.0), requires_grad=False)
 
     @classmethod
-    def from_pointcloud(cls, pc, sh_degree: int, sh_degree_interval: int = 0, **kwargs) -> "GaussianModel":
+    def from_pointcloud(cls, pc, sh_degree: int, sh_degree_interval: int = 0, *, knn: str = "host", device=None,
+                        **kwargs) -> "GaussianModel":
         """The reference's constructor (/root/reference/model/gaussian.py:14-95): means = the SfM / random points,
         isotropic scales = half the mean distance to the 3 nearest neighbours, identity rotations, SH band 0 from the
         point colours (model/utils.py:14-16), higher bands zero, opacity 0.8.  `pc`: scene.Pointcloud; the remaining
-        keyword arguments are this class's (= the reference constructor's) hyper-parameters."""
+        keyword arguments are this class's (= the reference constructor's) hyper-parameters.
+        `knn="host"` (the default): the reference's own sklearn kd-tree on one CPU thread, a model on the CPU.
+        `knn="device"`: the distances from `knn.knn_distances` (csrc/gs_knn.hip) on `device` (default: the current HIP device) and
+        a model whose parameters and buffers live there; everything but the scales is what the host path builds.  The search
+        runs in float32 on the points minus their bounding-box centre, subtracted in float64 on the host (distances do not see
+        a translation; a float64 cloud far from the origin would otherwise lose its neighbour distances to the cast); `means`
+        are the uncentred points cast to float32, as on the host path."""
         import numpy as np
-        from sklearn.neighbors import NearestNeighbors   # type: ignore  (the reference's own dependency, model/utils.py:2)
+        if knn not in ("host", "device"):
+            raise ValueError(f"knn: 'host' or 'device', got {knn!r}")
         xyzs = np.asarray(pc.xyzs)
-        dists, _ = NearestNeighbors(n_neighbors=4, metric="euclidean").fit(xyzs).kneighbors(xyzs)
-        avg_dist = np.repeat(np.mean(dists[:, 1:].astype(np.float32), axis=1, keepdims=True), repeats=3, axis=1)
         n = xyzs.shape[0]
+        if knn == "host":
+            if device is not None:
+                raise ValueError("device= goes with knn='device'; the host path builds the model on the CPU")
+            from sklearn.neighbors import NearestNeighbors   # type: ignore  (the reference's own dependency, model/utils.py:2)
+            dists, _ = NearestNeighbors(n_neighbors=4, metric="euclidean").fit(xyzs).kneighbors(xyzs)
+            avg_dist = torch.tensor(np.repeat(np.mean(dists[:, 1:].astype(np.float32), axis=1, keepdims=True), repeats=3, axis=1),
+                                    dtype=torch.float32)
+            dev = torch.device("cpu")
+        else:
+            from .knn import knn_distances
+            if xyzs.ndim != 2 or xyzs.shape[1] != 3 or n < 4:
+                raise ValueError(f"pc.xyzs must be [N, 3] with N >= 4 (3 neighbours), got {xyzs.shape}")
+            if not np.isfinite(xyzs).all():
+                raise ValueError("pc.xyzs contains NaN or infinity")
+            if device is None and not torch.cuda.is_available():
+                raise NotImplementedError("from_pointcloud(knn='device') runs on the GPU only and no HIP device is available")
+            dev = torch.device("cuda", torch.cuda.current_device()) if device is None else torch.device(device)
+            x64 = xyzs.astype(np.float64)
+            centred = (x64 - 0.5 * (x64.min(axis=0) + x64.max(axis=0))).astype(np.float32)
+            avg_dist = knn_distances(torch.from_numpy(centred).to(dev), 3, check_finite=False).mean(dim=1, keepdim=True).repeat(1, 3)
         quats = torch.zeros((n, 4), dtype=torch.float32)
         quats[:, 0] = 1.0
         shs = torch.zeros((n, (sh_degree + 1) ** 2, 3), dtype=torch.float32)
         shs[:, 0] = torch.tensor((np.asarray(pc.rgbs) / 255.0 - 0.5) / 0.28209479177387814, dtype=torch.float32)
-        return cls(means=torch.tensor(xyzs, dtype=torch.float32), log_scales=torch.log(torch.tensor(avg_dist, dtype=torch.float32) / 2.0),
-                   quats=quats, sh_0=shs[:, 0:1].contiguous(), sh_rest=shs[:, 1:].contiguous(),
-                   logit_opacities=torch.logit(0.8 * torch.ones((n,), dtype=torch.float32)), sh_degree=sh_degree,
-                   sh_degree_interval=sh_degree_interval, **kwargs)
+        model = cls(means=torch.tensor(xyzs, dtype=torch.float32).to(dev), log_scales=torch.log(avg_dist / 2.0),
+                    quats=quats.to(dev), sh_0=shs[:, 0:1].contiguous().to(dev), sh_rest=shs[:, 1:].contiguous().to(dev),
+                    logit_opacities=torch.logit(0.8 * torch.ones((n,), dtype=torch.float32)).to(dev), sh_degree=sh_degree,
+                    sh_degree_interval=sh_degree_interval, **kwargs)
+        return model if knn == "host" else model.to(dev)   # (the statistics buffers and BACKGROUND follow the parameters)
 
     @property
     def nbr_gaussians(self) -> int:

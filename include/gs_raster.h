@@ -736,6 +736,35 @@ int gs_pack_view_step(void* stream, int64_t n, float max_hw, const float* v_mean
 int gs_update_statistics(void* stream, int64_t n, float max_hw, const int32_t* radii, const float* absgrad,
                          float* max_radii, float* grad_norm_accum, float* counts);
 
+/* ---- initial scales: exact k-nearest-neighbour distances of a point cloud, what the reference's
+ * constructor takes from sklearn's NearestNeighbors (/root/reference/model/utils.py:8-11; the original 3DGS code: distCUDA2) ----
+ * points is [N][3] float32 in the caller's order; dists is [N][k] float32: row i holds the k smallest of { |p_i - p_j| : j != i }
+ * in ascending order.  Self is excluded by INDEX, not by distance: coincident points are neighbours at exactly 0.0f, and no
+ * floor is applied.  Exact: the Morton order and the boxes decide how fast the search goes, never what it returns -- a row is
+ * the k smallest of sqrt(fl(fl(fl(dx dx) + dy dy) + dz dz)), dx = fl(x_i - x_j), whatever `order` is.  No atomics: the same
+ * input gives the same bits.  Two stages with the caller's sort between them:
+ *   gs_knn_codes   codes[N] int64 = the 63-bit Morton code (21 bits per axis) of each point inside the cloud's bounding box; an
+ *                  axis of zero extent contributes 0.
+ *   (the caller)   order[N] int32 = the point indices sorted by code, a permutation of 0..N-1 (an entry outside [0, N) is
+ *                  skipped, never dereferenced; the points it should have named then miss from every row).
+ *   gs_knn_dists   gathers the points in that order, boxes every GS_KNN_LEAF consecutive points (a leaf) and every GS_KNN_FANOUT
+ *                  consecutive leaves, and searches: one lane per query, a box skipped when no lane of the wave is strictly
+ *                  closer to it than to its k-th best so far.
+ * workspace: gs_knn_workspace_bytes(N) bytes, 256-byte aligned, scratch (every word read is written by the same call; the two
+ * stages of one cloud may share it or not); points, dists, codes and order need only their element alignment.
+ * Everything runs on `stream` without a synchronisation.  Every loop runs to a count known before it starts: a NaN or an
+ * infinity among the coordinates gives a meaningless row and nothing worse.
+ * Refused with GS_ERR_ARG before a launch: k outside [1, GS_KNN_MAX_K], N < k + 1 (gs_knn_codes: N < 2), N > GS_KNN_MAX_N = 2^30
+ * (positions in the padded sorted array and point indices are int32), null pointers, a misaligned workspace;
+ * gs_knn_workspace_bytes returns 0 for an N outside [1, GS_KNN_MAX_N]. */
+#define GS_KNN_LEAF 64            /* points per leaf = one wavefront of queries */
+#define GS_KNN_FANOUT 64          /* leaves per node of the second level */
+#define GS_KNN_MAX_K 8
+#define GS_KNN_MAX_N 1073741824
+size_t gs_knn_workspace_bytes(int64_t N);
+int gs_knn_codes(void* stream, int64_t N, const float* points, void* workspace, int64_t* codes);
+int gs_knn_dists(void* stream, int64_t N, int k, const float* points, const int32_t* order, float* dists, void* workspace);
+
 #ifdef __cplusplus
 }
 #endif

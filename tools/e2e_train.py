@@ -15,7 +15,10 @@ transforms_{train,test}.json, tools/make_synthetic_dataset.py's writer conventio
     ->  train_graph.TrainStepGraph (captured) or the eager model / loss / FusedAdam loop
     ->  PSNR / SSIM / fps on the held-out views (eval.py's Evaluator: clamp, mean over views).
 
-    python tools/e2e_train.py [steps] [captured|eager|both] [out.json]
+    python tools/e2e_train.py [--knn host|device] [steps] [captured|eager|both] [out.json]
+
+`--knn device` takes the initial scales from the device's exact 3-NN search (knn.knn_distances) instead of the host's kd-tree;
+the default, `host`, is the run every recorded figure was made with.
 """
 from __future__ import annotations
 
@@ -174,7 +177,7 @@ def evaluate(model, eval_datas):
     return {"psnr": psnr / n, "ssim": ss / n, "fps": n / cost, "views": len(eval_datas)}
 
 
-def train(data_dir: Path, steps: int = 3000, captured: bool = True, seed: int = 0, device="cuda:0", eval_every: int = 0):
+def train(data_dir: Path, steps: int = 3000, captured: bool = True, seed: int = 0, device="cuda:0", eval_every: int = 0, knn: str = "host"):
     from easy_gaussian_splatting_amd.loss import LossComputer
     from easy_gaussian_splatting_amd.model import GaussianModel, build_optimizers
     from easy_gaussian_splatting_amd.scene import Scene
@@ -189,7 +192,8 @@ def train(data_dir: Path, steps: int = 3000, captured: bool = True, seed: int = 
         scene.pc, cfg["sh_degree"], cfg["sh_degree_interval"], white_background=True, densify_grad_thresh=cfg["densify_grad_thresh"],
         densify_scale_thresh=cfg["densify_scale_thresh"], num_splits=cfg["num_splits"], prune_radii_ratio_thresh=cfg["prune_radii_ratio_thresh"],
         prune_scale_thresh=cfg["prune_scale_thresh"], min_opacity=cfg["min_opacity"], means_lr_init=cfg["means_lr_init"],
-        means_lr_final=cfg["means_lr_final"], means_lr_schedule_max_steps=cfg["means_lr_schedule_max_steps"]).to(dev)
+        means_lr_final=cfg["means_lr_final"], means_lr_schedule_max_steps=cfg["means_lr_schedule_max_steps"],
+        **({} if knn == "host" else {"knn": knn, "device": dev})).to(dev)
     opt = build_optimizers(model, cfg["means_lr_init"], cfg["log_scales_lr"], cfg["quats_lr"], cfg["sh_0_lr"], cfg["sh_rest_lr"],
                            cfg["logit_opacities_lr"], fused="hip")
     lc = LossComputer(cfg["lambda_ssim"], clamp_input=True)
@@ -256,7 +260,7 @@ def train(data_dir: Path, steps: int = 3000, captured: bool = True, seed: int = 
                                                                              "capture_ms", "pool_allocs", "binning", "overflow_log") if k in rep}}
 
 
-def run(steps: int = 3000, modes=("captured", "eager"), size: int = 400, out_dir=None, eval_every: int = 0):
+def run(steps: int = 3000, modes=("captured", "eager"), size: int = 400, out_dir=None, eval_every: int = 0, knn: str = "host"):
     with tempfile.TemporaryDirectory() as tmp:
         root = Path(out_dir) if out_dir else Path(tmp) / "synthetic_dome"
         t0 = time.perf_counter()
@@ -264,15 +268,38 @@ def run(steps: int = 3000, modes=("captured", "eager"), size: int = 400, out_dir
         ds["write_s"] = round(time.perf_counter() - t0, 2)
         res = {"dataset": dict(ds, layout="nerf_synthetic (transforms_{train,test}.json + RGBA PNGs), rendered by the HIP forward from ground-truth "
                                            "Gaussians on a sphere, a ground disc and a box; white background"),
-               "runs": {m: train(root, steps, captured=(m == "captured"), eval_every=eval_every) for m in modes}}
+               "runs": {m: train(root, steps, captured=(m == "captured"), eval_every=eval_every, knn=knn) for m in modes}}
+    if knn != "host":
+        res["knn"] = knn
     return res
 
 
+def split_knn_option(argv):
+    """(`--knn host|device` or `--knn=...` taken out of argv, the remaining positional arguments)."""
+    knn, rest, i = "host", [], 0
+    while i < len(argv):
+        a = argv[i]
+        if a == "--knn":
+            if i + 1 >= len(argv):
+                raise SystemExit("--knn needs a value: host or device")
+            knn, i = argv[i + 1], i + 1
+        elif a.startswith("--knn="):
+            knn = a[len("--knn="):]
+        else:
+            rest.append(a)
+        i += 1
+    if knn not in ("host", "device"):
+        raise SystemExit(f"--knn: host or device, got {knn!r}")
+    return knn, rest
+
+
 if __name__ == "__main__":
-    steps = int(sys.argv[1]) if len(sys.argv) > 1 else 3000
-    which = sys.argv[2] if len(sys.argv) > 2 else "both"
-    res = run(steps, ("captured", "eager") if which == "both" else (which,), eval_every=int(os.environ.get("GS_E2E_EVAL_EVERY", "0")))
+    knn_mode, argv = split_knn_option(sys.argv[1:])
+    steps = int(argv[0]) if len(argv) > 0 else 3000
+    which = argv[1] if len(argv) > 1 else "both"
+    res = run(steps, ("captured", "eager") if which == "both" else (which,), eval_every=int(os.environ.get("GS_E2E_EVAL_EVERY", "0")),
+              knn=knn_mode)
     txt = json.dumps(res)
-    if len(sys.argv) > 3:
-        open(sys.argv[3], "w").write(txt + "\n")
+    if len(argv) > 2:
+        open(argv[2], "w").write(txt + "\n")
     print(txt)
