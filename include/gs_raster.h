@@ -683,6 +683,43 @@ int gs_refine_apply(void* stream, int64_t n_old, int num_splits, int K, const in
                     float* new_exp_avg, float* new_exp_avg_sq, const int64_t* new_offsets_host, int32_t* src_scratch,
                     int8_t* tag_scratch);
 
+/* ---- training under a Gaussian budget: the MCMC densification (Kheradmand et al., 2024) on the flat Adam buffers ----
+ * (csrc/gs_mcmc.hip; easy_gaussian_splatting_amd/mcmc.py; DESIGN.md "Training to a budget").  No entry allocates; n == 0 launches
+ * nothing.
+ * gs_mcmc_weights: o = sigmoid(logit) in fp64; dead[i] = !(o > min_opacity) (0 everywhere when grow = 1);
+ * weights[i] = dead ? 0 : max(1, floor(o 2^24)).
+ * gs_mcmc_cdf: inclusive prefix sum of the uint32 weights into int64 (exact, whatever the block order).
+ * workspace: gs_mcmc_cdf_workspace_longs(n) int64.
+ * gs_mcmc_sample: draw j takes t = mulhi64((uint64) bits[j], total), total = cdf[n-1], and src[j] = min{i : cdf[i] > t};
+ * counts[n] (zeroed here) counts the draws per source.  Relocate (dead / dead_incl given, dead_incl the inclusive scan of dead by
+ * gs_scan_rows_i32, n_slots == n, bits[n]): the number of draws is the dead total, read on the device; dst[rank] = i for the dead
+ * Gaussians in index order.  Grow (dead = dead_incl = NULL): n_draws_host draws, dst[j] = n + j.  No draws when total == 0.
+ * src[n_slots] / dst[n_slots] are -1 beyond what is written; n_draws_dev[1] receives the number of draws.
+ * gs_mcmc_relocation_values: for R = clamp(ratio[i], 1, 51): o' = 1 - (1 - o)^(1/R), s' = s o / D,
+ * D = sum_{i=1..R} sum_{k<i} C(i-1,k) (-1)^k o'^(k+1) / sqrt(k+1), in fp64; opacities[n], scales[n][3], unclamped results.
+ * gs_mcmc_apply: in place on the flat buffers of gs_adam_step (offsets_host[6]: means, log_scales, quats, sh_0, sh_rest,
+ * logit_opacities; floats; rows 0 .. n_rows-1 exist in every segment).  First every Gaussian i < n with counts[i] > 0 gets the
+ * values above for R = min(counts[i] + 1, 51), o' clamped to [min_opacity, 1 - 2^-23], stored as logit(o') and log(s'); then
+ * every draw j < min(n_draws_dev[0], max_draws) copies its six parameter rows src[j] -> dst[j].  The Adam moments of every row
+ * rewritten (sources and destinations, all six segments) restart at zero.
+ * gs_mcmc_noise: means[i] += strength g(o_i) R(q_i) diag(s_i^2) R(q_i)^T z_i in fp64, one rounding at the store;
+ * g(o) = 1 / (1 + exp(-100 ((1 - o) - 0.995))), q normalised (wxyz), s = exp(log_scales), z[n][3] standard normal.
+ * Every pointer 16-byte aligned (the segments of the flat buffers are). */
+int gs_mcmc_weights(void* stream, int64_t n, const float* logit_opacities, double min_opacity, int grow, uint32_t* weights,
+                    int32_t* dead);
+size_t gs_mcmc_cdf_workspace_longs(int64_t n);
+int gs_mcmc_cdf(void* stream, int64_t n, const uint32_t* weights, int64_t* cdf, int64_t* workspace);
+int gs_mcmc_sample(void* stream, int64_t n, int64_t n_slots, const int64_t* cdf, const int64_t* bits, const int32_t* dead,
+                   const int32_t* dead_incl, int64_t n_draws_host, int32_t* src, int32_t* dst, int32_t* counts,
+                   int64_t* n_draws_dev);
+int gs_mcmc_relocation_values(void* stream, int64_t n, const float* opacities, const float* scales, const int32_t* ratio,
+                              float* new_opacities, float* new_scales);
+int gs_mcmc_apply(void* stream, int64_t n, int64_t n_rows, int K, double min_opacity, const int32_t* src, const int32_t* dst,
+                  const int32_t* counts, const int64_t* n_draws_dev, int64_t max_draws, float* params, float* exp_avg,
+                  float* exp_avg_sq, const int64_t* offsets_host);
+int gs_mcmc_noise(void* stream, int64_t n, double strength, const float* log_scales, const float* quats,
+                  const float* logit_opacities, const float* z, float* means);
+
 /* gs_project_bwd + gs_adam_step_dev in one pass, for the reference's own single-camera step with the model's raw
  * parameters (log-scales, logit opacities, split SH: activations as in gs_project_bwd(..., activations = 1)): no
  * gradient is written; each parameter element and its two moments are updated in place where its gradient is
