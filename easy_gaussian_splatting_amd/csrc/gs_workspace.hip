@@ -1,5 +1,6 @@
-// gs_workspace.hip -- the persistent, caller-owned scratch of the eager seam (SURVEY.md section 8b "Ownership": "the native
-// layer ... allocates nothing that outlives [the call] except a per-device, per-stream reusable workspace"; the entry points
+// gs_workspace.hip -- the persistent, caller-owned scratch of the eager seam and of the captured train step (SURVEY.md
+// section 8b "Ownership": "the native layer ... allocates nothing that outlives [the call] except a per-device, per-stream
+// reusable workspace"; the entry points
 // `gs_workspace_query/bind` that row names).  The library owns the LAYOUT -- which intermediates exist for a call shape,
 // their sizes and alignment --, the caller owns the MEMORY: three arenas per call in flight,
 //   fixed arena: everything sized by (C, N, image) -- packed records, footprints, offsets, counters;

@@ -11,13 +11,13 @@ through the C ABI of include/gs_raster.h directly -- the same kernels, in the sa
 inputs as `model(data)` / `LossComputer` / `loss.backward()` / `update_statistics` / `FusedAdam.step` issue
 them, so the two paths agree bit for bit (tests/test_gpu_train_graph.py) -- but
 
-* every buffer lives in a persistent workspace sized by CAPACITY -- of LISTED intersections (keys, sorted lists, quadrant
+* every buffer lives in a persistent workspace -- the intermediates in the three arenas of the library's own layout
+  (`gs_workspace_query`, as the eager seam's: `_SLOTS`) -- sized by CAPACITY -- of LISTED intersections (keys, sorted lists, quadrant
   masks, row bases: 13-25 bytes each) and of what the forward WALKS (work units with their checkpoints and sublists, gradient
   rows; round 6: rounds 1-5 sized those by the list capacity, 355 bytes per listed entry, 25 GB at 2 M Gaussians on a realistic
-  footprint of which 1.6 % was ever walked) -- high-water marks + margin; nothing is allocated per step and the host never
-  reads a size back: the list kernels, the
-  statistics and Adam run under the library's step guard (`gs_guard_set`) -- a step whose lists outgrow the
-  capacity is a device-side no-op, and so is every step queued behind it;
+  footprint of which 1.6 % was ever walked) -- high-water marks + margin; nothing is allocated per step and the host never reads a
+  size back: the list kernels, the statistics and Adam run under the library's step guard (`gs_guard_set`) -- a step whose lists
+  outgrow the capacity is a device-side no-op, and so is every step queued behind it;
 * the whole sequence is captured once into a hipGraph and replayed: per step the host enqueues the input
   copies, one tiny launch that carries Adam's bias corrections / learning rates as kernel arguments, and the
   graph;
@@ -45,11 +45,22 @@ from torch import Tensor
 from . import _native as nat
 from .optim import FusedAdam
 from . import rendering
-from .rendering import _SH_JAC
+from . import workspace as WS
+from .rendering import _SH_JAC, _sort_class
 
 
 _TILE = nat.GS_TILE
-_SORT_CLASSES = (1024, 4096, 8192, 16384)
+
+# Name in `buf` -> (slot of the library's workspace layout, shape of the view; a str: a dimension of the call, see `_lay`).  (-1,) is all the
+# layout gives the slot, 256-byte padding included: lengths only the library knows (scratch, slack words) -- read as a whole, garbage at the end.
+_SLOTS = {
+    "info": (WS.INFO, (nat.GS_INFO_WORDS,)), "rec": (WS.REC, ("N", nat.GS_REC_FLOATS)), "bbox": (WS.BBOX, ("N", 4)), "qcnt": (WS.QCNT, ("quads",)),
+    "tiles_per_gauss": (WS.TILES_PER_GAUSS, (1, "N")), "cum_tiles": (WS.CUM_TILES, ("N",)), "colors_post": (WS.COLORS_POST, (1, "N", 3)),
+    "isect_offsets": (WS.ISECT_OFFSETS, (-1,)), "bucket_offsets": (WS.BUCKET_OFFSETS, (-1,)), "tile_order": (WS.TILE_ORDER, ("tiles",)),
+    "sh_jac": (WS.SH_JAC, (-1,)), "ws": (WS.BIN, (-1,)), "coarse_keys": (WS.COARSE_KEYS, ("cap_coarse",)), "keys_tmp": (WS.KEYS_TMP, ("cap",)),
+    "slot_gid": (WS.SLOT_GID, ("cap",)), "flatten_ids": (WS.FLATTEN_IDS, ("cap",)), "slots": (WS.SLOTS, ("cap",)), "qmask": (WS.QMASK, (-1,)),
+    "row_base": (WS.ROW_BASE, (-1,)), "walk_state": (WS.WALK_STATE, (-1,)), "ckpt": (WS.CKPT, ("cap_units", 64, 4)),
+    "qlist": (WS.QLIST, ("cap_units", nat.GS_UNIT, 2)), "unit_desc": (WS.UNIT_DESC, ("cap_units", 4)), "rows": (WS.ROWS, ("cap_rows", nat.GS_ROW_FLOATS))}
 
 
 def _p(t: Optional[Tensor]):
@@ -142,7 +153,7 @@ class TrainStepGraph:
         self._walk_history_void = False
         self.binning = None
         self.probed = (0, 0)
-        self.cap_tile = _SORT_CLASSES[0]
+        self.cap_tile = _sort_class(0)
         self.pending: deque = deque()     # steps issued but not yet confirmed applied: (t, lrs, w2c, K, gt, mask)
         # {I, n_buckets, max tile, flags, applied} of the latest finished step, written by the device (gs_step_status)
         self.status = torch.zeros((8,), dtype=torch.int64, pin_memory=True)
@@ -150,6 +161,7 @@ class TrainStepGraph:
         self.issued = 0
         self.stats = {"captures": 0, "overflows": 0, "replayed_steps": 0, "rebuilds": 0}
         self._pool: Dict[str, Tensor] = {}
+        self.lease = WS.Lease(None, self.dev)   # private, never in `workspace.pool`: the graph bakes its addresses in
         self._warm = set()     # (binning mode, tile-sort class) pairs that have run EAGERLY in this runner (warm-up steps)
         self._key = None
         self.confirmed_at_build = 0
@@ -171,16 +183,14 @@ class TrainStepGraph:
         `projected` = (I, longest tile list, storage units, gradient rows) carried over from the steps before a refinement (`step()`): no probe, no
         warm-up step -- the re-build is allocation + capture and never touches the device's queue.  (A projection that
         does not hold trips the step guard like any overflow; `_recover` then probes.)"""
-        m, dev = self.model, self.dev
-        L = nat.lib()
+        m, dev, L = self.model, self.dev, nat.lib()
         t_build = time.perf_counter()
         self.N = N = m.means.shape[0]
         self.K = 1 + m.sh_rest.shape[1]
         W, H = self.W, self.H
         self.tw, self.th = math.ceil(W / _TILE), math.ceil(H / _TILE)
-        tiles = self.tw * self.th
+        self.tiles = tiles = self.tw * self.th
         f32 = dict(dtype=torch.float32, device=dev)
-        i32 = dict(dtype=torch.int32, device=dev)
         b = self.buf = {}
         b["viewmats"] = torch.empty((1, 4, 4), **f32)
         b["Ks"] = torch.empty((1, 3, 3), **f32)
@@ -192,18 +202,6 @@ class TrainStepGraph:
         b["means2d"] = self._take("means2d", (1, N, 2), torch.float32)
         b["depths"] = self._take("depths", (1, N), torch.float32)
         b["conics"] = self._take("conics", (1, N, 3), torch.float32)
-        b["colors_post"] = self._take("colors_post", (1, N, 3), torch.float32)
-        # d colour / d view direction of the visible Gaussians (gs_project_fwd -> gs_project_bwd*: no SH coefficient is read
-        # by the backward); GS_SH_JAC=0 keeps the coefficient-staging backward
-        b["sh_jac"] = self._take("sh_jac", (N * 9,), torch.float32) if _SH_JAC else None
-        b["rec"] = self._take("rec", (N, nat.GS_REC_FLOATS), torch.float32)
-        b["bbox"] = self._take("bbox", (N, 4), torch.int32)
-        b["tiles_per_gauss"] = self._take("tiles_per_gauss", (1, N), torch.int32)
-        b["cum_tiles"] = self._take("cum_tiles", (N,), torch.int32)
-        b["isect_offsets"] = torch.empty((tiles + 1,), **i32)
-        b["bucket_offsets"] = torch.empty((tiles + 1,), **i32)
-        b["tile_order"] = torch.empty((tiles,), **i32)
-        b["info"] = torch.zeros((nat.GS_INFO_WORDS,), dtype=torch.int64, device=dev)
         b["applied"] = torch.zeros((1,), dtype=torch.int64, device=dev)
         b["render_colors"] = torch.empty((1, H, W, 3), **f32)
         b["render_alphas"] = torch.empty((1, H, W, 1), **f32)
@@ -212,7 +210,6 @@ class TrainStepGraph:
         b["loss_ring"] = torch.zeros((self.LOSS_RING, 3), **f32)
         b["one"] = torch.ones((), **f32)
         b["v_render"] = torch.empty((H, W, 3), **f32)
-        b["qcnt"] = torch.empty((tiles * 4,), **i32)
         b["v_abs"] = self._take("v_abs", (1, N, 2), torch.float32)
         self.grads = None if self.fuse_adam else {
             "means": torch.empty((N, 3), **f32), "log_scales": torch.empty((N, 3), **f32),
@@ -229,7 +226,7 @@ class TrainStepGraph:
             n_isects, max_tile, units, rows = projected
             self.cap = int(n_isects * self.margin) + 4096
             need_tile = int(max_tile * self.margin)
-            self.cap_tile = next((c for c in _SORT_CLASSES if c >= need_tile), 1 << 30)
+            self.cap_tile = _sort_class(need_tile)
             self.cap_units, self.cap_rows = int(units * self.margin) + 512, int(rows * self.margin) + 4096
             self.stats["projected_rebuilds"] = self.stats.get("projected_rebuilds", 0) + 1
         elif self.cap == 0 or min_cap or min_cap_tile or min_walk[0] or min_walk[1]:
@@ -237,10 +234,9 @@ class TrainStepGraph:
             self.probed = (n_isects, max_tile)
             self.cap = max(int(max(n_isects, min_cap) * self.margin) + 4096, self.cap, self.cap_floor)
             need_tile = max(int(max(max_tile, min_cap_tile) * self.margin), self.cap_tile)   # (same head-room as the lists)
-            self.cap_tile = next((c for c in _SORT_CLASSES if c >= need_tile), 1 << 30)
+            self.cap_tile = _sort_class(need_tile)
             probe_walk = True
-        self._alloc_binning()
-        self._alloc_lists()
+        self._lay(1 if probe_walk else 0)   # (behind a probe the fixed arena stays as it is)
         self._alloc_rounds()
         if probe_walk:
             # what the forward WALKS on this view: one guarded forward on first-guess capacities, repeated with what it reports
@@ -313,42 +309,41 @@ class TrainStepGraph:
             self.stats["pool_allocs"] = self.stats.get("pool_allocs", 0) + 1
         return t[:n].view(*shape)
 
-    def _alloc_binning(self):
-        """Workspace of the binning pipeline the probe chose (rendering.binning_mode): per-tile lists sorted one by one
-        ("tiles") or coarse-bin lists sorted and refined ("bins"; capacities for the coarse entries and the longest bin
-        list learnt from the probe, overflow flagged on the device like the list capacity)."""
-        L, b, dev = nat.lib(), self.buf, self.dev
-        if self.binning == "bins":
-            ws = int(L.gs_bins_workspace_bytes(1, self.N, self.tw, self.th, self.bin_shift, self.cap_coarse))
-            b["coarse_keys"] = self._take("coarse_keys", (self.cap_coarse,), torch.int64)
+    def _lay(self, first: int):
+        """Moves the lease onto the library's layout (gs_workspace_query) for the capacities as they stand, from arena `first` on -- 0: all, a
+        build; 1: lists and walk (the fixed arena, and a projection in it, stay: its offsets depend on no capacity and no binning); 2: walk
+        alone -- and refreshes `buf`'s views of those arenas (None: not in this layout).  The arenas come from `_take`, the runner's memory
+        policy; the walk arena is let go for a smaller one only where the walk capacities are known: a probe lays placeholders first."""
+        bins, st, lease = self.binning == "bins", self.stream.cuda_stream, self.lease
+        lay = WS.Layout(1, self.N, self.W, self.H, self.cap, self.cap_coarse if bins else 0, self.bin_shift if bins else 0,
+                        WS.F_TRAIN | (WS.F_TWO_LEVEL if bins else 0), max(self.cap_units, 256), self.cap_rows)
+        if first == 2 and lay.key == lease.layout.key and self.buf.get("rows") is not None:
+            return   # (laid by this build already)
+        for which, nbytes in list(zip(("fixed", "lists", "walk"), lay.arena_bytes))[first:]:
+            setattr(lease, which, self._take(which, (nbytes,), torch.uint8, shrink=which == "walk" and self.cap_rows > 0))
+        if first == 0:
+            with torch.cuda.device(self.dev):   # (validates, and zeroes the info block on the runner's stream -- unless it has seen these
+                lease.bind(lay, st)             #  arenas and this layout before: the flags are sticky, so zeroed here in any case)
+                lease.view(WS.INFO, nat.GS_INFO_WORDS).zero_()
         else:
-            ws = int(L.gs_bin_workspace_bytes(1, self.N, self.tw, self.th))
-            b["keys_tmp"] = self._take("keys_tmp", (self.cap,), torch.int64)
-            b["slot_gid"] = self._take("slot_gid", (self.cap,), torch.int32)
-        self.ws_bytes = ws
-        b["ws"] = self._take("ws", (ws,), torch.uint8)
-
-    def _alloc_lists(self):
-        """What is sized by the LISTED intersections: the sorted lists, a quadrant-mask byte and a row base per entry."""
-        b, cap = self.buf, self.cap
-        b["flatten_ids"] = self._take("flatten_ids", (cap,), torch.int32)
-        b["slots"] = self._take("slots", (cap,), torch.int32)
-        b["qmask"] = self._take("qmask", (cap + 16,), torch.uint8)
-        b["row_base"] = self._take("row_base", (cap // 16 + 4,), torch.int32)
-        b["walk_state"] = self._take("walk_state", (int(nat.lib().gs_walk_state_ints(cap)),), torch.int32)
+            lease.grow_lists(lay, st) if first == 1 else lease.grow_walk(lay)
+        dims = dict(N=self.N, tiles=self.tiles, quads=4 * self.tiles, cap=self.cap, cap_coarse=lay.key[5], cap_units=self.cap_units, cap_rows=self.cap_rows)
+        for name, (slot, shape) in _SLOTS.items():
+            if WS._arena(slot) >= first:
+                self.buf[name] = None
+                if lay.offsets[slot] >= 0 and (_SH_JAC or slot != WS.SH_JAC):   # (GS_SH_JAC=0 keeps the coefficient-staging backward)
+                    shape, ext = [dims.get(d, d) for d in shape], lay.extent(slot) // WS._DTYPES[slot].itemsize
+                    n = ext if shape == [-1] else math.prod(shape)
+                    assert n <= ext, (name, shape)
+                    self.buf[name] = lease.view(slot, n) if len(shape) == 1 else lease.view(slot, n).view(shape)
+        self.ws_bytes = lay.extent(WS.BIN)   # (rounded up to the alignment: the entry points ask for at least their own figure)
 
     def _alloc_walk(self):
         """What is sized by what the forward WALKS: a checkpoint, a sublist block and a descriptor per work unit, the gradient rows."""
-        b = self.buf
-        cu, cr = max(int(self.cap_units), 256), max(int(self.cap_rows), 1)
-        self.cap_units, self.cap_rows = cu, cr
-        b["ckpt"] = self._take("ckpt", (cu, 64, 4), torch.float32, shrink=True)
-        b["qlist"] = self._take("qlist", (cu, nat.GS_UNIT, 2), torch.int32, shrink=True)
-        b["unit_desc"] = self._take("unit_desc", (cu, 4), torch.int32, shrink=True)
-        # the backward's fill classes (gs_raster.h: gs_blend_bwd groups the units by how full they are); GS_BWD_CLASSES=0: off
-        b["unit_cls"] = (self._take("unit_cls", (int(nat.lib().gs_unit_classes_ints(cu, 1, self.W, self.H)),), torch.int32, shrink=True)
-                         if rendering._BWD_CLASSES else None)
-        b["rows"] = self._take("rows", (cr, nat.GS_ROW_FLOATS), torch.float32, shrink=True)
+        self.cap_units, self.cap_rows = max(int(self.cap_units), 256), max(int(self.cap_rows), 1)
+        self._lay(2)
+        n_cls = int(nat.lib().gs_unit_classes_ints(self.cap_units, 1, self.W, self.H))   # (gs_blend_bwd's fill classes; GS_BWD_CLASSES=0: off)
+        self.buf["unit_cls"] = self._take("unit_cls", (n_cls,), torch.int32, shrink=True) if rendering._BWD_CLASSES else None
 
     ROUNDS_MIN_LISTED = 4_000_000   # "auto": below this the list stages are too short for a second round to pay
     ROUNDS_MIN_RATIO = 4.0          # ... and so they are when the frame lists less than this many entries per gradient row
@@ -557,40 +552,36 @@ class TrainStepGraph:
         """Blocking reads of the list sizes for the current inputs (build time only): {I, longest tile list} from the
         per-tile count, then -- if the footprints call for the two-level binning -- {coarse entries, longest bin list}."""
         from .rendering import MAX_TILES_PER_TILE_PIPELINE, bin_shift_for, binning_choice
-        L, b, dev = nat.lib(), self.buf, self.dev
-        tiles = self.tw * self.th
-        n_isects = max_tile = 0
-        footprint = None
-        if tiles <= MAX_TILES_PER_TILE_PIPELINE:
-            self.binning = "tiles"
-            self.ws_bytes = int(L.gs_bin_workspace_bytes(1, self.N, self.tw, self.th))
-            b["ws"] = torch.empty((self.ws_bytes,), dtype=torch.uint8, device=dev)
-            with torch.cuda.device(dev), self._on_stream():
-                self._project()
+        b, dev, tiles = self.buf, self.dev, self.tiles
+        n_isects, max_tile, footprint, per_tile = 0, 0, None, tiles <= MAX_TILES_PER_TILE_PIPELINE
+        self.binning, self.bin_shift, self.cap_coarse = "tiles" if per_tile else "bins", 2, 0   # (else never counted per tile: the two-level scratch)
+        cap, self.cap = self.cap, 0   # (the counts need nothing that the list capacity sizes: those slots are absent from `buf` here)
+        self._lay(0)
+        with torch.cuda.device(dev), self._on_stream():
+            self._project()
+            if per_tile:
                 self._count()
+        if per_tile:
             info = b["info"].tolist()
             n_isects, max_tile = int(info[nat.GS_INFO_ISECTS]), int(info[nat.GS_INFO_MAX_TILE])
             footprint = n_isects / max(1, self.N)
-        else:
-            with torch.cuda.device(dev), self._on_stream():
-                self._project()
         self.binning = binning_choice(footprint, tiles)
         if self.binning == "bins":
             self.bin_shift = bin_shift_for(footprint) or 2
             self.cap_coarse, self.cap_coarse_list = 2 * self.N + 1024, 0
             while True:
-                self._alloc_binning()
+                self._lay(1)
                 with torch.cuda.device(dev), self._on_stream():
                     self._count()
                 info = b["info"].tolist()
+                self.cap_coarse = int(int(info[nat.GS_INFO_COARSE]) * self.margin) + 4096
                 if not int(info[nat.GS_INFO_FLAGS]) & (nat.GS_FLAG_COARSE | nat.GS_FLAG_COARSE_LIST):
                     break
-                self.cap_coarse = int(int(info[nat.GS_INFO_COARSE]) * self.margin) + 4096
-            self.cap_coarse = int(int(info[nat.GS_INFO_COARSE]) * self.margin) + 4096
             self.cap_coarse_list = int(int(info[nat.GS_INFO_MAX_BIN]) * 1.5) + 64
             self.probed_coarse = (int(info[nat.GS_INFO_COARSE]), int(info[nat.GS_INFO_MAX_BIN]))   # coarse-bin entries I', longest bin list
             n_isects, max_tile = int(info[nat.GS_INFO_ISECTS]), int(info[nat.GS_INFO_MAX_TILE])
         b["info"].zero_()
+        self.cap = cap
         return n_isects, max_tile
 
     def _enqueue_forward(self):
@@ -832,7 +823,7 @@ class TrainStepGraph:
                 # ... but only into a tile-sort class this runner has already run EAGERLY: a class used for the first time is
                 # another kernel / another LDS size, whose attributes `ensure_lds` would raise -- and which would launch for the
                 # first time -- inside the stream capture (gs_binning.hip: the warm-up exists to avoid exactly that)
-                cls = next((c for c in _SORT_CLASSES if c >= int(projected[1] * self.margin)), 1 << 30)
+                cls = _sort_class(int(projected[1] * self.margin))
                 if (self.binning, cls) not in self._warm:
                     # (the probing re-build still takes the projection as a floor: its probe sees ONE view, the history all)
                     carried, projected = projected, None
@@ -983,10 +974,12 @@ class ViewParallelGraphStep(TrainStepGraph):
         kw["fuse_adam"] = False
         super().__init__(model, optimizer, loss_computer, data, gt_img, mask, **kw)
 
-    def _alloc_lists(self):
-        super()._alloc_lists()
-        self.buf["row_sums"] = self._take("row_sums", (self.N, 12), torch.float32)
-        self.vp._records(); self.vp._bucket()   # (the record and the bucket the graph writes into: made before the capture)
+    def _lay(self, first: int):
+        """... and, once per build, what the view-parallel step needs beside the layout: the row sums, the record and the bucket."""
+        super()._lay(first)
+        if first == 0:
+            self.buf["row_sums"] = self._take("row_sums", (self.N, 12), torch.float32)
+            self.vp._records(); self.vp._bucket()   # (the record and the bucket the graph writes into: made before the capture)
 
     def _enqueue_step(self):
         """The captured part: everything up to this rank's all-gather record."""

@@ -17,6 +17,7 @@ Two forwards in flight before a backward (several views accumulated into one los
 whose lists outgrow the capacity replaces the list arena only (`Lease.grow_lists`) and repeats the list stages; a training
 call whose walk outgrows its capacities replaces the walk arena only (`Lease.grow_walk`) and repeats the blend.
 Only tensors that escape to the caller (image, alphas, radii, means2d, depths, conics, gradients) are `torch.empty`.
+The captured train step (`train_graph.TrainStepGraph`) takes the same layout: a private `Lease`, never pooled, on arenas it brings itself.
 """
 from __future__ import annotations
 
@@ -44,7 +45,7 @@ _DTYPES = {INFO: torch.int64, REC: torch.float32, BBOX: torch.int32, TILES_PER_G
            COLORS_POST: torch.float32, ISECT_OFFSETS: torch.int32, BUCKET_OFFSETS: torch.int32, TILE_ORDER: torch.int32,
            QCNT: torch.int32, WALK_STATE: torch.int32, ROW_BASE: torch.int32, SH_JAC: torch.float32, FLATTEN_IDS: torch.int32, SLOTS: torch.int32, ISECT_IDS: torch.int64,
            QMASK: torch.uint8, ROWS: torch.float32, QLIST: torch.int32, UNIT_DESC: torch.int32,
-           CKPT: torch.float32}
+           CKPT: torch.float32, BIN: torch.uint8, COARSE_KEYS: torch.int64, KEYS_TMP: torch.int64, SLOT_GID: torch.int32}
 
 stats = {"leases_created": 0, "acquires": 0, "fixed_allocs": 0, "list_allocs": 0, "walk_allocs": 0, "list_grows": 0, "walk_grows": 0, "binds": 0, "ckpt_ext_allocs": 0}
 
@@ -63,6 +64,15 @@ class Layout:
         self.arena_bytes = (int(self._c_bytes[0]), int(self._c_bytes[1]), int(self._c_bytes[2]))
         self.key = (C, N, W, H, cap, coarse_cap, bin_shift, flags, cap_units, cap_rows)
         self.cap_units, self.cap_rows = int(cap_units), int(cap_rows)
+
+    def extent(self, slot: int) -> int:
+        """Bytes a present slot has to itself (its size, rounded up to the alignment): to the next one of its arena, or the arena's end."""
+        a, off, first = _arena(slot), self.offsets[slot], (0, LIST_FIRST, WALK_FIRST, N_SLOTS)
+        return min([o for o in self.offsets[first[a]:first[a + 1]] if o > off] + [self.arena_bytes[a]]) - off
+
+
+def _arena(slot: int) -> int:
+    return (slot >= LIST_FIRST) + (slot >= WALK_FIRST)
 
 
 class Lease:
@@ -151,18 +161,13 @@ class Lease:
 
     def ptr(self, slot: int) -> Optional[int]:
         off = self.layout.offsets[slot]
-        if off < 0:
-            return None
-        base = self.fixed if slot < LIST_FIRST else (self.lists if slot < WALK_FIRST else self.walk)
-        return base.data_ptr() + off
+        return None if off < 0 else (self.fixed, self.lists, self.walk)[_arena(slot)].data_ptr() + off
 
     def view(self, slot: int, n: int) -> torch.Tensor:
         off = self.layout.offsets[slot]
         assert off >= 0, f"workspace slot {slot} is not part of this layout"
-        base = self.fixed if slot < LIST_FIRST else (self.lists if slot < WALK_FIRST else self.walk)
-        dt = _DTYPES[slot]
-        isz = torch.empty((), dtype=dt).element_size()
-        return base[off:off + n * isz].view(dt)
+        base, dt = (self.fixed, self.lists, self.walk)[_arena(slot)], _DTYPES[slot]
+        return base[off:off + n * dt.itemsize].view(dt)
 
 
 class _Pool:

@@ -188,10 +188,11 @@ int gs_round_status(void* stream, const int64_t* rounds_dev, int64_t* status_hos
 int gs_step_status(void* stream, const int64_t* info_dev, const int64_t* applied_dev, int64_t* status,
                    const float* loss3_dev, float* loss_ring_dev, int ring_len, const int32_t* walk_state);
 
-/* Persistent workspace of the eager seam (SURVEY.md section 8b "Ownership" / "Sync"; replaces the ~25 per-call allocations a
- * binding would otherwise make and lets the list stages be enqueued BEFORE the list sizes have reached the host).
- * gs_workspace_query: layout of every intermediate of one rasterization() call that does not escape to the caller, for a call
- * shape and a CAPACITY of intersections.  offsets[GS_WS_SLOTS]: byte offset of each buffer inside its arena (-1: not needed for
+/* Persistent workspace of both seams, the eager rasterization() and the captured train step (SURVEY.md section 8b "Ownership" /
+ * "Sync"; replaces the ~25 per-call allocations a binding would otherwise make and lets the list stages be enqueued BEFORE the
+ * list sizes have reached the host).  The layout below is the only description of these buffers: no caller sizes one itself.
+ * gs_workspace_query: layout of every intermediate of one rasterization() call (or one train step) that does not escape to the
+ * caller, for a call shape and a CAPACITY of intersections.  offsets[GS_WS_SLOTS]: byte offset of each buffer inside its arena (-1: not needed for
  * these flags); slots below GS_WS_LIST_FIRST live in the fixed arena (sized by C, N, image), those below GS_WS_WALK_FIRST in the
  * list arena (sized by cap_isects / coarse_cap: what is LISTED), the others in the walk arena (sized by cap_units / cap_rows:
  * what a training forward WALKS -- checkpoints, quadrant sublists, work units, gradient rows); arena_bytes[3] = bytes of the

@@ -260,6 +260,23 @@ def test_workspace_layout_query(native):
     assert lib.gs_workspace_bind(None, None, 0, None, 0, None, 0, offs, ab) == -1
 
 
+def test_captured_step_names_every_slot_of_a_training_layout(native):
+    """The captured train step takes its intermediates from the library's layout through `train_graph._SLOTS`: at a ragged tiny
+    shape (300 Gaussians, 72 x 40 = 5 x 3 tiles cut on both edges), under both binnings, every slot the layout holds is in that
+    table, and every slot of the table has a dtype to be viewed with -- a slot added to the library fails here instead of being
+    left out of the runner.  (Host logic only: no GPU.)"""
+    from easy_gaussian_splatting_amd import workspace as WS
+    from easy_gaussian_splatting_amd.train_graph import _SLOTS
+    named = {slot for slot, _ in _SLOTS.values()}
+    assert len(named) == len(_SLOTS)
+    for flags in (WS.F_TRAIN, WS.F_TRAIN | WS.F_TWO_LEVEL):
+        lay = WS.Layout(1, 300, 72, 40, 5000, 1624, 2, flags, 300, 7000)
+        present = {slot for slot, off in enumerate(lay.offsets) if off >= 0}
+        assert len(present) >= 20 and present <= named, (flags, sorted(present - named))
+    for name, (slot, shape) in _SLOTS.items():
+        assert slot in WS._DTYPES, name
+
+
 def test_workspace_pool_leases(native, monkeypatch):
     """workspace.pool: a lease goes back to its (device, stream) pool when the last holder drops it and is re-used by the
     next acquire; two calls in flight get two leases; arenas only grow.  (bind's device memset is stubbed: no GPU.)"""

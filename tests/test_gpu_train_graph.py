@@ -8,7 +8,8 @@ import torch
 
 from easy_gaussian_splatting_amd.loss import LossComputer
 from easy_gaussian_splatting_amd.model import GaussianModel, build_optimizers
-from easy_gaussian_splatting_amd.train_graph import HostFeed, TrainStepGraph
+from easy_gaussian_splatting_amd import rendering, workspace as WS
+from easy_gaussian_splatting_amd.train_graph import _SLOTS, HostFeed, TrainStepGraph
 from scenes import make_scene
 
 pytestmark = pytest.mark.gpu
@@ -55,6 +56,32 @@ def _assert_same(ma, oa, mb, ob, what=""):
     assert oa._step == ob._step
 
 
+def _assert_layout(runner):
+    """The runner's intermediates are the library's layout (gs_workspace_query), not a copy of it: every slot the layout holds is
+    the view `buf` has under its name -- at the slot's offset in its arena, ending at or before the next slot the layout holds
+    there (or the arena's end) -- and the arenas are 256-byte aligned and no smaller than the layout says."""
+    lease, lay = runner.lease, runner.lease.layout
+    arenas = (lease.fixed, lease.lists, lease.walk)
+    arena_of = lambda slot: 0 if slot < WS.LIST_FIRST else (1 if slot < WS.WALK_FIRST else 2)   # noqa: E731
+    for a, nbytes in zip(arenas, lay.arena_bytes):
+        assert a.data_ptr() % 256 == 0 and a.numel() >= nbytes
+    checked = 0
+    for name, (slot, _) in _SLOTS.items():
+        off, k = lay.offsets[slot], arena_of(slot)
+        if off < 0:
+            assert runner.buf.get(name) is None, name
+            continue
+        v = runner.buf[name]
+        if v is None and name == "sh_jac" and not rendering._SH_JAC:   # (GS_SH_JAC=0: the slot is there, the step does not use it)
+            continue
+        end = min([o for s, o in enumerate(lay.offsets) if arena_of(s) == k and o > off] + [lay.arena_bytes[k]])
+        assert v.is_contiguous() and v.data_ptr() == arenas[k].data_ptr() + off, name
+        assert off + v.numel() * v.element_size() <= end, (name, tuple(v.shape))
+        checked += 1
+    assert checked >= 20
+    assert lay.key[:5] == (1, runner.N, runner.W, runner.H, runner.cap) and (lay.cap_units, lay.cap_rows) == (runner.cap_units, runner.cap_rows)
+
+
 @pytest.mark.parametrize("binning", ["tiles", "bins"])
 @pytest.mark.parametrize("fuse_adam", [True, False])
 @pytest.mark.parametrize("use_graph", [True, False])
@@ -73,6 +100,7 @@ def test_graph_step_equals_eager_step(use_graph, with_mask, fuse_adam, binning, 
     # faults.  The runner must therefore replay on a stream of its own; this loop IS the regression
     # test for that -- eager steps on the caller's stream alternate with replays -- and would fault if the workaround went.
     assert runner.stream.cuda_stream != torch.cuda.current_stream(dev).cuda_stream and runner.stream.cuda_stream != 0
+    _assert_layout(runner)
     for it in range(7):
         v = it % 3
         ma.update_learning_rate(it); mb.update_learning_rate(it)
@@ -82,6 +110,7 @@ def test_graph_step_equals_eager_step(use_graph, with_mask, fuse_adam, binning, 
         assert torch.equal(out["loss3"], l_ref), it
         runner.finish()
         _assert_same(ma, oa, mb, ob, f"step {it}")
+    _assert_layout(runner)
     rep = runner.report()
     assert rep["steps"] == 7 and rep["overflows"] == 0 and rep["graph"] == use_graph
     assert rep["captures"] == (1 if use_graph else 0)
@@ -115,6 +144,7 @@ def test_overflow_is_skipped_on_device_detected_lazily_and_replayed(binning, mon
     # the device-side loss log holds the APPLIED steps' losses (skipped launches log nothing)
     hist = runner.loss_history(3)
     assert hist.shape == (min(3, int(runner.buf["applied"].item())), 3) and torch.equal(hist[-1], ref_losses[-1])
+    _assert_layout(runner)
 
 
 def test_walk_overflow_is_skipped_on_device_detected_lazily_and_replayed():
@@ -148,6 +178,7 @@ def test_walk_overflow_is_skipped_on_device_detected_lazily_and_replayed():
         assert last["flags"] == (16 if cut == "units" else 32) and last["work_units"] > 2000 and last["rows"] > 50_000, last
         assert rep["capacity_work_units"] > 2000 and rep["capacity_rows"] > 50_000 and rep["capacity_isects"] <= 1.1 * rep0["capacity_isects"]   # (re-probed on another view)
         _assert_same(ma, oa, mb, ob, f"after a walk overflow ({cut})")
+        _assert_layout(runner)
     assert runner.report()["steps"] == 15
 
 
@@ -165,6 +196,7 @@ def test_refinement_between_graph_steps_rebuilds_the_workspace():
         _eager_step(ma, oa, lc, datas[it % 3], gts[it % 3]); runner.step(datas[it % 3], gts[it % 3])
     runner.finish()
     _assert_same(ma, oa, mb, ob, "before refine")
+    _assert_layout(runner)
     n0 = ma.nbr_gaussians
     for m, seed in ((ma, 5), (mb, 5)):
         m.densify_and_prune(generator=torch.Generator(device=dev).manual_seed(seed))
@@ -174,11 +206,13 @@ def test_refinement_between_graph_steps_rebuilds_the_workspace():
         _eager_step(ma, oa, lc, datas[it % 3], gts[it % 3]); runner.step(datas[it % 3], gts[it % 3])
     runner.finish()
     _assert_same(ma, oa, mb, ob, "after densify")
+    _assert_layout(runner)
     ma.reset_opacities(); mb.reset_opacities()
     for it in range(2):
         _eager_step(ma, oa, lc, datas[it], gts[it]); runner.step(datas[it], gts[it])
     runner.finish()
     _assert_same(ma, oa, mb, ob, "after opacity reset")
+    _assert_layout(runner)
     assert runner.report()["rebuilds"] >= 3
 
 

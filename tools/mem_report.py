@@ -43,10 +43,15 @@ def main():
     torch.cuda.synchronize()
     rep = runner.report()
     listed = max(1, rep["probed_isects"])
-    sizes = {k: int(t.numel() * t.element_size()) for k, t in runner._pool.items()}
+    # the pool holds the three arenas of the library's layout ("fixed", "lists", "walk") whole; `buf`'s views INTO them are listed
+    # on their own (`slots_MiB`) and not counted a second time
+    nbytes = lambda t: int(t.numel() * t.element_size())   # noqa: E731
+    sizes = {k: nbytes(t) for k, t in runner._pool.items()}
+    arenas = {runner._pool[a].untyped_storage().data_ptr() for a in ("fixed", "lists", "walk")}
+    slots = {}
     for k, t in runner.buf.items():
         if isinstance(t, torch.Tensor) and k not in sizes:
-            sizes[k] = int(t.numel() * t.element_size())
+            (slots if t.untyped_storage().data_ptr() in arenas else sizes)[k] = nbytes(t)
     top = sorted(sizes.items(), key=lambda kv: -kv[1])
     print(json.dumps({
         "config": name, "list_mode": mode, "n_gaussians": int(sc["means"].shape[0]), "listed": listed, "capacity": rep["capacity_isects"],
@@ -57,7 +62,9 @@ def main():
         "runner_bytes_per_listed": round((after_build - base) / listed, 1),
         "ms_per_step": round(ev0.elapsed_time(ev1) / steps, 4),
         "status_words": [int(v) for v in runner.status[:8].tolist()],
-        "buffers_MiB": {k: round(v / 2 ** 20, 1) for k, v in top[:24]}}), flush=True)
+        "runner_buffers_GiB": round(sum(sizes.values()) / 2 ** 30, 3),
+        "buffers_MiB": {k: round(v / 2 ** 20, 1) for k, v in top[:24]},
+        "slots_MiB": {k: round(v / 2 ** 20, 1) for k, v in sorted(slots.items(), key=lambda kv: -kv[1])}}), flush=True)
 
 
 if __name__ == "__main__":
