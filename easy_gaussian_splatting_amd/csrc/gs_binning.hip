@@ -18,7 +18,9 @@
 //                       tile_radix_sort_items_kernel: <= 4096 and <= 8192 keys), 8192-key segments + a rank merge up to
 //                       65536 keys (seg_merge_kernel), a bitonic network in place in global memory beyond.
 // Second half of the file: the two-level binning (gs_bins_count / gs_bins_lists) for scenes whose Gaussians cover many
-// tiles -- coarse bins sorted with the same kernels, tiles refined out of them by ordered compaction.
+// tiles -- coarse bins counted, filled and sorted with the same kernels, tiles refined out of them by ordered compaction.
+// Both pipelines read the footprint record of gs_common.h and walk it with ONE walk (walk_cells): bin_hist_kernel and
+// bin_emit_kernel are templates over what a cell is -- a tile (<false>) or a coarse bin (<true>).
 // The "slot" carried in the key's low word is the index of this intersection's gradient row
 // (cum_tiles[f] + k): rows of one Gaussian are contiguous, which lets the backward reduce them
 // with plain coalesced loads instead of float atomics.
@@ -30,15 +32,26 @@ namespace gs {
 #define GS_BIN_PER_GROUP 4096     // Gaussians per binning block (histogram / emit)
 #define GS_BIN_MAX_GROUPS 256     // (bin_colscan_kernel takes up to kColChunks * 16 groups in its batched path)
 constexpr int kBinThreads = 1024;
-constexpr int kCoopTiles = 32;  // footprints above this are spread over the whole wave
 
-BinLayout bin_layout(int C, int64_t N, int tiles) {
-    BinLayout L;
+// Gaussian groups per camera (one histogram / emit block each) and Gaussians per group: both pipelines, and gs_bin_groups
+static int bin_groups(int64_t N, int64_t& per_group) {
     int64_t g = (N + GS_BIN_PER_GROUP - 1) / GS_BIN_PER_GROUP;
     if (g < 1) g = 1;
     if (g > GS_BIN_MAX_GROUPS) g = GS_BIN_MAX_GROUPS;
-    L.groups = (int)g;
-    L.per_group = (N + g - 1) / g;
+    per_group = (N + g - 1) / g;
+    return (int)g;
+}
+
+// bits of the tile index in an intersection id (camera | tile | depth bits)
+static int tile_bits_of(int tiles) {
+    int tb = 0;
+    for (int v = tiles; v > 0; v >>= 1) ++tb;
+    return tb;
+}
+
+BinLayout bin_layout(int C, int64_t N, int tiles) {
+    BinLayout L;
+    L.groups = bin_groups(N, L.per_group);
     auto align = [](size_t x) { return (x + 255) & ~(size_t)255; };
     size_t off = 0;
     L.hist_off = off; off = align(off + sizeof(uint32_t) * (size_t)C * L.groups * tiles);
@@ -50,55 +63,107 @@ BinLayout bin_layout(int C, int64_t N, int tiles) {
     return L;
 }
 
-// footprint word layout written by project_fwd_kernel: x0 | x1<<16, y0 | y1<<16, tile mask, count
-__device__ __forceinline__ void unpack_bbox(uint4 b, int& x0, int& x1, int& y0, int& y1) {
-    x0 = b.x & 0xffff; x1 = b.x >> 16; y0 = b.y & 0xffff; y1 = b.y >> 16;
+// ------------------------------------------------------------------------------------------------ the footprint walk
+// What the histogram and the emit kernels walk: a rectangle of CELLS, `rect` of them from (x0, y0), `w` to a row, and -- up to
+// kMaskTiles cells -- the row-major mask of the cells that count (a larger rectangle counts whole).  A cell is a tile
+// (BINS = false: the footprint record as it stands) or a coarse bin of 1 << shift tiles a side (BINS = true: every bin the
+// tile rectangle touches, mask or not -- a bin none of whose tiles is in the tile mask just yields no entry in the
+// refinement).  A record with count 0 has no cells.
+struct Cells { int x0, y0, w, rect; uint32_t mask; };
+template <bool BINS>
+__device__ __forceinline__ Cells footprint_cells(uint4 fp, int shift) {
+    int x0, x1, y0, y1;
+    fp_unpack(fp, x0, x1, y0, y1);
+    Cells c;
+    if (BINS) {
+        const int r = (1 << shift) - 1;
+        c.x0 = x0 >> shift; c.y0 = y0 >> shift;
+        c.w = ((x1 + r) >> shift) - c.x0;
+        c.rect = c.w * (((y1 + r) >> shift) - c.y0);
+        c.mask = fp_full_mask(c.rect);
+    } else {
+        c.x0 = x0; c.y0 = y0; c.w = x1 - x0; c.rect = c.w * (y1 - y0); c.mask = fp.z;
+    }
+    if (fp.w == 0u) { c.rect = 0; c.mask = 0u; }
+    return c;
+}
+
+// lane `src`'s value in every lane, 32-bit word by word
+template <typename P>
+__device__ __forceinline__ P wave_bcast(const P& v, int src) {
+    static_assert(sizeof(P) % sizeof(int) == 0, "whole 32-bit words");
+    int w[sizeof(P) / sizeof(int)];
+    __builtin_memcpy(w, &v, sizeof(P));
+#pragma unroll
+    for (int k = 0; k < (int)(sizeof(P) / sizeof(int)); ++k) w[k] = __shfl(w[k], src, 64);
+    P r;
+    __builtin_memcpy(&r, w, sizeof(P));
+    return r;
+}
+
+// THE walk over the cells of the wave's 64 footprints (one per lane; wave-uniform call).  body(cell, k, p): cell = index
+// in a grid `stride` cells wide, k = rank of the cell among the footprint's cells, p = the owning lane's payload.  A
+// footprint with a mask is walked by its own lane over the set bits; a larger one is spread over the whole wave, one
+// after the other, its rectangle and payload broadcast from the owning lane (a lane walking 2000 tiles alone held its
+// 63 neighbours).  Rows by div_by_width: cell rectangles lie well inside its exact domain.
+// FULL: the caller knows every mask to be full (coarse bins) -- the lane's own loop then counts through the rectangle,
+// no bit scan and no division per cell.  Measured, not assumed: the bit scan over full masks cost the two-level pipeline
+// up to 7 us where few Gaussians have large footprints (200 k at 106 tiles each: 0.098 against 0.089 ms,
+// profiles/binning_walk_ab.json), the binning blocks being few and the lane loops long.
+template <bool FULL, typename P, typename Body>
+__device__ __forceinline__ void walk_cells(const Cells& c, int stride, const P& mine, Body body) {
+    const float inv_w = 1.0f / (float)max(c.w, 1);
+    if (FULL) {
+        if (c.rect <= kMaskTiles)
+            for (int i = 0, xx = 0, row = c.y0 * stride + c.x0; i < c.rect; ++i) {
+                body(row + xx, (uint32_t)i, mine);
+                if (++xx == c.w) { xx = 0; row += stride; }
+            }
+    } else if (c.rect <= kMaskTiles) {
+        uint32_t k = 0;
+        for (uint32_t mb = c.mask; mb; mb &= mb - 1, ++k) {
+            const int i = __ffs((int)mb) - 1, yy = div_by_width(i, inv_w);
+            body((c.y0 + yy) * stride + c.x0 + (i - yy * c.w), k, mine);
+        }
+    }
+    for (unsigned long long big = __ballot(c.rect > kMaskTiles); big; big &= big - 1) {
+        const int src = __ffsll((long long)big) - 1;
+        const int bx0 = __shfl(c.x0, src, 64), by0 = __shfl(c.y0, src, 64), bw = __shfl(c.w, src, 64), brect = __shfl(c.rect, src, 64);
+        const float binv = __shfl(inv_w, src, 64);
+        const P p = wave_bcast(mine, src);
+        for (int i = lane_id(); i < brect; i += 64) {
+            const int yy = div_by_width(i, binv);
+            body((by0 + yy) * stride + bx0 + (i - yy * bw), (uint32_t)i, p);
+        }
+    }
 }
 
 // ------------------------------------------------------------------------------------------------
-__global__ __launch_bounds__(kBinThreads) void bin_hist_kernel(int64_t N, int tw, int tiles,
-                                                               int64_t per_group,
-                                                               const uint4* __restrict__ bbox,
-                                                               uint32_t* __restrict__ hist_mat,
+// One block per (camera, Gaussian group): LDS histogram over the `cells` cells of a camera (tiles, or coarse bins: a grid
+// `stride` wide) -> the group's row of the matrix; grp_tot = the group's (tile) intersections.
+template <bool BINS>
+__global__ __launch_bounds__(kBinThreads) void bin_hist_kernel(int64_t N, int stride, int cells, int shift, int64_t per_group,
+                                                               const uint4* __restrict__ bbox, uint32_t* __restrict__ hist_mat,
                                                                uint32_t* __restrict__ grp_tot, const int64_t* __restrict__ rblk, int phase) {
     extern __shared__ __attribute__((aligned(16))) uint32_t lds[];
     if (round_idle(rblk, phase)) return;
-    uint32_t* hist = lds;               // [tiles]
-    uint32_t* scratch = lds + tiles;    // [32]
+    uint32_t* hist = lds;               // [cells]
+    uint32_t* scratch = lds + cells;    // [32]
     const int grp = blockIdx.x, c = blockIdx.y, G = gridDim.x;
-    for (int t = threadIdx.x; t < tiles; t += blockDim.x) hist[t] = 0;
+    for (int t = threadIdx.x; t < cells; t += blockDim.x) hist[t] = 0;
     __syncthreads();
     const int64_t g0 = grp * per_group, g1 = min(N, g0 + per_group);
     uint32_t local = 0;
     for (int64_t base = g0; base < g1; base += blockDim.x) {
         const int64_t n = base + threadIdx.x;
-        int x0 = 0, x1 = 0, y0 = 0, y1 = 0;
         uint4 fp = make_uint4(0u, 0u, 0u, 0u);
-        if (n < g1) { fp = bbox[(int64_t)c * N + n]; unpack_bbox(fp, x0, x1, y0, y1); }
-        const int w = x1 - x0, rect = w * (y1 - y0), cnt = (int)fp.w;
-        const float inv_w = 1.0f / (float)max(w, 1);
-        local += cnt;
-        if (rect <= kCoopTiles)   // small footprints: one bit per tile of the rectangle
-            for (uint32_t mb = fp.z; mb; mb &= mb - 1) {
-                const int i = __ffs((int)mb) - 1, yy = div_by_width(i, inv_w);
-                atomicAdd(&hist[(y0 + yy) * tw + x0 + (i - yy * w)], 1u);
-            }
-        unsigned long long big = __ballot(rect > kCoopTiles);
-        while (big) {
-            const int src = __ffsll((long long)big) - 1;
-            big &= big - 1;
-            const int bx0 = __shfl(x0, src, 64), by0 = __shfl(y0, src, 64), bw = __shfl(w, src, 64),
-                      bcnt = __shfl(cnt, src, 64);
-            const float binv = __shfl(inv_w, src, 64);
-            for (int i = lane_id(); i < bcnt; i += 64) {
-                const int yy = div_by_width(i, binv);
-                atomicAdd(&hist[(by0 + yy) * tw + bx0 + (i - yy * bw)], 1u);
-            }
-        }
+        if (n < g1) fp = bbox[(int64_t)c * N + n];
+        local += fp.w;
+        walk_cells<BINS>(footprint_cells<BINS>(fp, shift), stride, 0, [&](int cell, uint32_t, int) { atomicAdd(&hist[cell], 1u); });
     }
     __syncthreads();
-    uint32_t* out = hist_mat + ((size_t)c * G + grp) * tiles;
-    for (int t = threadIdx.x; t < tiles; t += blockDim.x) out[t] = hist[t];
+    uint32_t* out = hist_mat + ((size_t)c * G + grp) * cells;
+    for (int t = threadIdx.x; t < cells; t += blockDim.x) out[t] = hist[t];
     // block total
     uint32_t wsum = wave_reduce_add(local);
     if (lane_id() == 0) scratch[threadIdx.x >> 6] = wsum;
@@ -154,6 +219,32 @@ __global__ __launch_bounds__(kColTiles * kColChunks) void bin_colscan_kernel(int
     }
 }
 
+// group bases: exclusive scan of the groups' intersection totals (few thousand values at most: serial chunks of a block)
+__device__ __forceinline__ void scan_group_bases(int n_groups_total, const uint32_t* __restrict__ grp_tot, uint32_t* __restrict__ grp_base,
+                                                 unsigned long long* scratch) {
+    unsigned long long gcarry = 0;
+    for (int base = 0; base < n_groups_total; base += kBinThreads) {
+        const int i = base + threadIdx.x;
+        unsigned long long v = i < n_groups_total ? grp_tot[i] : 0ull, total;
+        unsigned long long ex = block_excl_scan_add(v, scratch, &total);
+        if (i < n_groups_total) grp_base[i] = (uint32_t)(gcarry + ex);
+        gcarry += total;
+    }
+}
+
+// maximum over a block of kBinThreads; the result is thread 0's
+__device__ __forceinline__ uint32_t block_max(uint32_t m) {
+    __shared__ uint32_t smax[kBinThreads / 64];
+#pragma unroll
+    for (int d = 32; d > 0; d >>= 1) m = max(m, (uint32_t)__shfl_xor((int)m, d, 64));
+    if (lane_id() == 0) smax[threadIdx.x >> 6] = m;
+    __syncthreads();
+    uint32_t mm = 0;
+    if (threadIdx.x == 0)
+        for (int i = 0; i < kBinThreads / 64; ++i) mm = max(mm, smax[i]);
+    return mm;
+}
+
 // Three independent single-block jobs in one launch (they used to run one after the other in a single block, 23 us of
 // barrier and memory latency on the critical path of every forward):
 //   block 0  exclusive scans of the tile counts -> isect_offsets, bucket_offsets; {I, n_buckets, longest list}, flags
@@ -172,16 +263,9 @@ __global__ __launch_bounds__(kBinThreads) void bin_tilescan_kernel(
     // depth rounds: the back round's lists (and slots) continue behind the front round's; a back round with no live tile
     // leaves everything as the front round left it (info[0] = its total)
     if (round_idle(rblk, phase)) return;
-    if (blockIdx.x == 2) {   // group bases (few thousand values at most): serial chunks of kBinThreads
+    if (blockIdx.x == 2) {
         if (sort_counts && threadIdx.x < 64) sort_counts[threadIdx.x] = 0;   // work-list counters of the sort that follows
-        unsigned long long gcarry = 0;
-        for (int base = 0; base < n_groups_total; base += kBinThreads) {
-            const int i = base + threadIdx.x;
-            unsigned long long v = i < n_groups_total ? grp_tot[i] : 0ull, total;
-            unsigned long long ex = block_excl_scan_add(v, scratch, &total);
-            if (i < n_groups_total) grp_base[i] = (uint32_t)(gcarry + ex);
-            gcarry += total;
-        }
+        scan_group_bases(n_groups_total, grp_tot, grp_base, scratch);
         return;
     }
     if (blockIdx.x == 1) {
@@ -257,16 +341,8 @@ __global__ __launch_bounds__(kBinThreads) void bin_tilescan_kernel(
         carry_i += total & ((1ull << 36) - 1);
         carry_b += total >> 36;
     }
-    // max over block
-    uint32_t m = max_cnt;
-#pragma unroll
-    for (int d = 32; d > 0; d >>= 1) m = max(m, (uint32_t)__shfl_xor((int)m, d, 64));
-    __shared__ uint32_t smax[16];
-    if (lane_id() == 0) smax[threadIdx.x >> 6] = m;
-    __syncthreads();
+    uint32_t mm = block_max(max_cnt);
     if (threadIdx.x == 0) {
-        uint32_t mm = 0;
-        for (int i = 0; i < kBinThreads / 64; ++i) mm = max(mm, smax[i]);
         isect_offsets[n_tiles_total] = (int32_t)carry_i;
         bucket_offsets[n_tiles_total] = (int32_t)carry_b;
         if (phase == 1) rblk[GS_ROUND_BASE] = (int64_t)carry_i;
@@ -295,83 +371,82 @@ __global__ __launch_bounds__(kBinThreads) void bin_tilescan_kernel(
 }
 
 // ------------------------------------------------------------------------------------------------
-__global__ __launch_bounds__(kBinThreads) void bin_emit_kernel(
-    int64_t N, int tw, int tiles, int64_t per_group, const uint4* __restrict__ bbox,
-    const float* __restrict__ depths, const uint32_t* __restrict__ hist_mat,
-    const int32_t* __restrict__ isect_offsets, const uint32_t* __restrict__ grp_base,
-    unsigned long long* __restrict__ keys, int32_t* __restrict__ slot_gid,
-    int32_t* __restrict__ cum_tiles, const int64_t* __restrict__ guard, const int64_t* __restrict__ rblk, int phase) {
+struct EmitArgs {
+    int64_t N, per_group;
+    int stride, cells, shift;       // the cell grid of a camera: tiles (tile_w, tiles, 0) or coarse bins (bw, nbins, bin shift)
+    const uint4* bbox;
+    const float* depths;
+    const uint32_t* hist_mat;       // [C*groups][cells]  after the column scan: the group's base inside each cell's list
+    const int32_t* offsets;         // [C*cells]  where each cell's list starts: isect_offsets / the coarse bin offsets
+    const uint32_t* grp_base;
+    unsigned long long* keys;
+    int32_t* slot_gid;              // per-tile training lists: the key's low word is the gradient-row slot, slot_gid[slot] = flatten id;
+                                    //   nullptr (inference lists, coarse lists): the low word is the flatten id itself
+    int32_t* cum_tiles;
+    uint4* rec;                     // coarse lists: [C*N] footprint with the slot base in place of the count, for the refinement
+    const int64_t* stop;            // info block whose flags word voids the call: the step guard's (or none) / the coarse stage's own
+    const int64_t* rblk;
+    int phase;
+};
+
+// Same blocks as the histogram: per-cell write cursors in LDS (returning ds_add), every (Gaussian, cell) pair emits its key
+// (depth bits << 32 | slot or flatten id) into its cell's segment; cum_tiles = the Gaussian's first gradient-row slot.
+template <bool BINS>
+__global__ __launch_bounds__(kBinThreads) void bin_emit_kernel(const EmitArgs a) {
     extern __shared__ __attribute__((aligned(16))) uint32_t lds[];
-    if (guard_tripped(guard) || round_idle(rblk, phase)) return;
-    uint32_t* cursor = lds;                                    // [tiles]
-    uint32_t* scratch = lds + tiles;                           // [32]
+    if (guard_tripped(a.stop) || round_idle(a.rblk, a.phase)) return;
+    const int cells = a.cells;
+    const int64_t N = a.N;
+    uint32_t* cursor = lds;                                    // [cells]
+    uint32_t* scratch = lds + cells;                           // [32]
     const int grp = blockIdx.x, c = blockIdx.y, G = gridDim.x;
-    const uint32_t* mine = hist_mat + ((size_t)c * G + grp) * tiles;
-    const int32_t* toff = isect_offsets + (size_t)c * tiles;
-    // cursor init, loads batched ahead of the LDS stores (8 tiles per thread and round)
-    for (int t0 = 0; t0 < tiles; t0 += 8 * (int)blockDim.x) {
+    const uint32_t* mine = a.hist_mat + ((size_t)c * G + grp) * cells;
+    const int32_t* coff = a.offsets + (size_t)c * cells;
+    // cursor init, loads batched ahead of the LDS stores (8 cells per thread and round)
+    for (int t0 = 0; t0 < cells; t0 += 8 * (int)blockDim.x) {
         uint32_t v[8];
 #pragma unroll
         for (int k = 0; k < 8; ++k) {
             const int t = t0 + k * (int)blockDim.x + (int)threadIdx.x;
-            v[k] = t < tiles ? mine[t] + (uint32_t)toff[t] : 0u;
+            v[k] = t < cells ? mine[t] + (uint32_t)coff[t] : 0u;
         }
 #pragma unroll
         for (int k = 0; k < 8; ++k) {
             const int t = t0 + k * (int)blockDim.x + (int)threadIdx.x;
-            if (t < tiles) cursor[t] = v[k];
+            if (t < cells) cursor[t] = v[k];
         }
     }
     __syncthreads();
     // (depth rounds: the back round's gradient-row slots continue behind the front round's)
-    uint32_t running = grp_base[c * G + grp] + (phase == 2 ? (uint32_t)rblk[GS_ROUND_BASE] : 0u);
-    const int64_t g0 = grp * per_group, g1 = min(N, g0 + per_group);
+    uint32_t running = a.grp_base[c * G + grp] + (a.phase == 2 ? (uint32_t)a.rblk[GS_ROUND_BASE] : 0u);
+    const int64_t g0 = grp * a.per_group, g1 = min(N, g0 + a.per_group);
     // the next round's footprint and depth are requested before this round's scatter
     uint4 fp_next = make_uint4(0u, 0u, 0u, 0u);
     float d_next = 0.f;
-    if (g0 + threadIdx.x < g1) { fp_next = bbox[(int64_t)c * N + g0 + threadIdx.x]; d_next = depths[(int64_t)c * N + g0 + threadIdx.x]; }
+    if (g0 + threadIdx.x < g1) { fp_next = a.bbox[(int64_t)c * N + g0 + threadIdx.x]; d_next = a.depths[(int64_t)c * N + g0 + threadIdx.x]; }
+    struct Owner { uint32_t dbits, slot0, f; };   // what a cell's entry takes from its Gaussian
     for (int64_t base = g0; base < g1; base += blockDim.x) {
         const int64_t n = base + threadIdx.x;
         const int64_t f = (int64_t)c * N + n;
-        int x0 = 0, x1 = 0, y0 = 0, y1 = 0;
-        const uint4 fp = fp_next;
+        const uint4 fp = fp_next;   // (zero words beyond the group's end)
         const float dcur = d_next;
-        if (n < g1) unpack_bbox(fp, x0, x1, y0, y1);
-        const int w = x1 - x0, rect = w * (y1 - y0), cnt = (int)fp.w;
-        const float inv_w = 1.0f / (float)max(w, 1);
         uint32_t total;
-        const uint32_t slot0 = running + block_excl_scan_add((uint32_t)cnt, scratch, &total);
+        const uint32_t slot0 = running + block_excl_scan_add(fp.w, scratch, &total);
         running += total;
         // (after the scan: its barriers drain the vector-memory counter)
         fp_next = make_uint4(0u, 0u, 0u, 0u);
-        if (n + blockDim.x < g1) { fp_next = bbox[f + blockDim.x]; d_next = depths[f + blockDim.x]; }
-        if (n < g1 && (phase != 2 || cnt > 0)) cum_tiles[f] = (int32_t)slot0;   // (a Gaussian of the front round keeps its slots)
-        const uint32_t dbits = cnt > 0 ? __float_as_uint(dcur) : 0u;
-        if (rect <= kCoopTiles) {
-            uint32_t k = 0;
-            for (uint32_t mb = fp.z; mb; mb &= mb - 1, ++k) {
-                const int i = __ffs((int)mb) - 1, yy = div_by_width(i, inv_w);
-                const uint32_t pos = atomicAdd(&cursor[(y0 + yy) * tw + x0 + (i - yy * w)], 1u);
-                keys[pos] = ((unsigned long long)dbits << 32) | (slot_gid ? slot0 + k : (uint32_t)f);
-                if (slot_gid) slot_gid[slot0 + k] = (int32_t)f;
-            }
+        if (n + blockDim.x < g1) { fp_next = a.bbox[f + blockDim.x]; d_next = a.depths[f + blockDim.x]; }
+        if (n < g1) {
+            if (a.phase != 2 || fp.w != 0u) a.cum_tiles[f] = (int32_t)slot0;   // (a Gaussian of the front round keeps its slots)
+            if (BINS) a.rec[f] = make_uint4(fp.x, fp.y, fp.z, slot0);
         }
-        unsigned long long big = __ballot(rect > kCoopTiles);
-        while (big) {
-            const int src = __ffsll((long long)big) - 1;
-            big &= big - 1;
-            const int bx0 = __shfl(x0, src, 64), by0 = __shfl(y0, src, 64), bw = __shfl(w, src, 64),
-                      bcnt = __shfl(cnt, src, 64);
-            const uint32_t bslot = __shfl((int)slot0, src, 64), bd = __shfl((int)dbits, src, 64);
-            const int32_t bf = (int32_t)(c * N + base) + (src + (threadIdx.x & ~63));
-            const float binv = __shfl(inv_w, src, 64);
-            for (int i = lane_id(); i < bcnt; i += 64) {
-                const int yy = div_by_width(i, binv);
-                const uint32_t pos = atomicAdd(&cursor[(by0 + yy) * tw + bx0 + (i - yy * bw)], 1u);
-                keys[pos] = ((unsigned long long)bd << 32) | (slot_gid ? bslot + i : (uint32_t)bf);
-                if (slot_gid) slot_gid[bslot + i] = bf;
-            }
-        }
+        const Owner me = {__float_as_uint(dcur), slot0, (uint32_t)f};
+        walk_cells<BINS>(footprint_cells<BINS>(fp, a.shift), a.stride, me, [&](int cell, uint32_t k, const Owner& o) {
+            const uint32_t pos = atomicAdd(&cursor[cell], 1u);
+            const bool slots = !BINS && a.slot_gid;
+            a.keys[pos] = ((unsigned long long)o.dbits << 32) | (slots ? o.slot0 + k : o.f);
+            if (slots) a.slot_gid[o.slot0 + k] = (int32_t)o.f;
+        });
     }
 }
 
@@ -421,6 +496,19 @@ struct SortArgs {
 };
 __device__ __forceinline__ bool sort_off(const SortArgs& a) { return guard_tripped(a.guard) || round_idle(a.rblk, a.phase); }
 
+// A sorted per-tile list leaves the sort as list entries: (camera | tile) bits of list `list`'s intersection ids, and entry
+// `at` of the intersection-indexed outputs from its sorted key.
+__device__ __forceinline__ long long list_id_bits(const SortArgs& a, int list) {
+    const int cam = list / max(a.tiles, 1), tix = list - cam * a.tiles;
+    return ((long long)cam << (32 + a.tile_bits)) | ((long long)tix << 32);
+}
+__device__ __forceinline__ void write_list_entry(const SortArgs& a, int at, unsigned long long k, long long id_bits) {
+    const uint32_t slot = (uint32_t)k;
+    if (a.slot_gid) { a.slots[at] = (int32_t)slot; a.flatten_ids[at] = a.slot_gid[slot]; }
+    else a.flatten_ids[at] = (int32_t)slot;   // inference lists: the key's low word is the flatten id itself
+    if (a.isect_ids) a.isect_ids[at] = id_bits | (long long)(k >> 32);
+}
+
 constexpr int kSegLen = 8192;   // the largest LDS radix class
 constexpr int kSegMax = 8;      // lists of up to 65536 keys: sorted segment by segment, then rank-merged
 
@@ -446,15 +534,8 @@ __global__ void tile_sort_kernel(const SortArgs a) {
         if (IN_LDS) for (int i = threadIdx.x; i < n; i += blockDim.x) gk[i] = skeys[i];
         return;
     }
-    const int cam = t / a.tiles, tid = t - cam * a.tiles;
-    const long long hi_bits = ((long long)cam << (32 + a.tile_bits)) | ((long long)tid << 32);
-    for (int i = threadIdx.x; i < n; i += blockDim.x) {
-        const unsigned long long k = IN_LDS ? skeys[i] : gk[i];
-        const uint32_t slot = (uint32_t)k;
-        if (a.slot_gid) { a.slots[lo + i] = (int32_t)slot; a.flatten_ids[lo + i] = a.slot_gid[slot]; }
-        else a.flatten_ids[lo + i] = (int32_t)slot;   // inference lists: the key's low word is the flatten id itself
-        if (a.isect_ids) a.isect_ids[lo + i] = hi_bits | (long long)(k >> 32);
-    }
+    const long long id_bits = list_id_bits(a, t);
+    for (int i = threadIdx.x; i < n; i += blockDim.x) write_list_entry(a, lo + i, IN_LDS ? skeys[i] : gk[i], id_bits);
 }
 
 // ------------------------------------------------------------------------------------------------
@@ -584,15 +665,8 @@ __device__ __forceinline__ void radix_sort_list(const SortArgs& a, const int vbl
         for (int i = tid; i < n; i += T) out[i] = src[i];
         return;
     }
-    const int cam = tile / a.tiles, tix = tile - cam * a.tiles;
-    const long long hi_bits = ((long long)cam << (32 + a.tile_bits)) | ((long long)tix << 32);
-    for (int i = tid; i < n; i += T) {
-        const unsigned long long k = src[i];
-        const uint32_t slot = (uint32_t)k;
-        if (a.slot_gid) { a.slots[lo + i] = (int32_t)slot; a.flatten_ids[lo + i] = a.slot_gid[slot]; }
-        else a.flatten_ids[lo + i] = (int32_t)slot;   // inference lists: the key's low word is the flatten id itself
-        if (a.isect_ids) a.isect_ids[lo + i] = hi_bits | (long long)(k >> 32);
-    }
+    const long long id_bits = list_id_bits(a, tile);
+    for (int i = tid; i < n; i += T) write_list_entry(a, lo + i, src[i], id_bits);
 }
 
 template <int T>
@@ -645,10 +719,11 @@ static size_t sort_items_bytes(int64_t n_lists) {   // work lists of launch_list
 // rectangle touches (I' entries, 1.4-17 per Gaussian instead of 3-190), each bin's list is depth-sorted by the same
 // LDS radix kernels on (depth bits << 32 | flatten id) keys, and every tile then takes its own list out of its bin's
 // sorted list by an ORDERED compaction (ballot + popcount: no atomics, no second sort, depth and tie order inherited):
-//   bins_hist_kernel    per (camera, Gaussian group): LDS histogram over bins
+//   bin_hist_kernel<true>  (shared)  per (camera, Gaussian group): LDS histogram over bins
 //   bin_colscan_kernel  (shared)  per bin: exclusive scan down the group axis
 //   bins_scan_kernel    one block: bin offsets, group bases, {I', longest bin list}, coarse overflow flag
-//   bins_emit_kernel    per group: LDS cursors -> keys into the bin segments; cum_tiles (gradient-row slot bases)
+//   bin_emit_kernel<true>  (shared)  per group: LDS cursors -> keys into the bin segments; cum_tiles (gradient-row slot
+//                       bases); rec (footprint + slot base of every Gaussian, for the refinement)
 //   tile_radix_sort_kernel / tile_sort_kernel (shared, coarse mode): bins sorted in place
 //   bins_refine_kernel<false>  one block per bin, one wave per tile: per-tile counts
 //   bin_tilescan_kernel (shared)  isect_offsets, bucket_offsets, tile_order, {I, n_buckets, max list}
@@ -675,11 +750,7 @@ struct BinsLayout {
 
 static BinsLayout bins_layout(int C, int64_t N, int tw, int th, int bin_shift, int64_t coarse_cap) {
     BinsLayout L;
-    int64_t g = (N + GS_BIN_PER_GROUP - 1) / GS_BIN_PER_GROUP;
-    if (g < 1) g = 1;
-    if (g > GS_BIN_MAX_GROUPS) g = GS_BIN_MAX_GROUPS;
-    L.groups = (int)g;
-    L.per_group = (N + g - 1) / g;
+    L.groups = bin_groups(N, L.per_group);
     // 4x4-tile bins unless that puts more than ~2500 Gaussians per bin on average (sort classes above 4096 entries
     // run one block per CU): then 2x2
     const int64_t nb2 = (int64_t)((tw + 3) / 4) * ((th + 3) / 4);
@@ -706,88 +777,6 @@ static BinsLayout bins_layout(int C, int64_t N, int tw, int th, int bin_shift, i
     return L;
 }
 
-// bins touched by a footprint (tile rectangle, possibly with a tile mask: the rectangle is what counts here -- a bin
-// none of whose tiles is in the mask just yields no entry in the refinement)
-__device__ __forceinline__ void coarse_rect(uint4 fp, int shift, int& cx0, int& cw, int& cy0, int& crect) {
-    int x0, x1, y0, y1;
-    unpack_bbox(fp, x0, x1, y0, y1);
-    if (fp.w == 0u) { cx0 = cy0 = cw = crect = 0; return; }
-    const int r = (1 << shift) - 1;
-    cx0 = x0 >> shift; cy0 = y0 >> shift;
-    cw = ((x1 + r) >> shift) - cx0;
-    crect = cw * (((y1 + r) >> shift) - cy0);
-}
-
-__global__ __launch_bounds__(kBinThreads) void bins_hist_kernel(int64_t N, int shift, int bw, int nbins, int64_t per_group,
-                                                                const uint4* __restrict__ bbox,
-                                                                uint32_t* __restrict__ hist_mat,
-                                                                uint32_t* __restrict__ grp_tot, const int64_t* __restrict__ rblk, int phase) {
-    extern __shared__ __attribute__((aligned(16))) uint32_t lds[];
-    if (round_idle(rblk, phase)) return;
-    uint32_t* hist = lds;               // [nbins]
-    uint32_t* scratch = lds + nbins;    // [32]
-    const int grp = blockIdx.x, c = blockIdx.y, G = gridDim.x;
-    for (int t = threadIdx.x; t < nbins; t += blockDim.x) hist[t] = 0;
-    __syncthreads();
-    const int64_t g0 = grp * per_group, g1 = min(N, g0 + per_group);
-    uint32_t local = 0;
-    for (int64_t base = g0; base < g1; base += blockDim.x) {
-        const int64_t n = base + threadIdx.x;
-        uint4 fp = make_uint4(0u, 0u, 0u, 0u);
-        if (n < g1) fp = bbox[(int64_t)c * N + n];
-        int cx0, cw, cy0, crect;
-        coarse_rect(fp, shift, cx0, cw, cy0, crect);
-        local += fp.w;
-        if (crect <= kCoopTiles)
-            for (int i = 0, xx = 0, row = cy0 * bw + cx0; i < crect; ++i) {
-                atomicAdd(&hist[row + xx], 1u);
-                if (++xx == cw) { xx = 0; row += bw; }
-            }
-        unsigned long long big = __ballot(crect > kCoopTiles);
-        while (big) {
-            const int src = __ffsll((long long)big) - 1;
-            big &= big - 1;
-            const int bx0 = __shfl(cx0, src, 64), by0 = __shfl(cy0, src, 64), bcw = __shfl(cw, src, 64), bcnt = __shfl(crect, src, 64);
-            for (int i = lane_id(); i < bcnt; i += 64) {
-                const int yy = i / bcw;
-                atomicAdd(&hist[(by0 + yy) * bw + bx0 + (i - yy * bcw)], 1u);
-            }
-        }
-    }
-    __syncthreads();
-    uint32_t* out = hist_mat + ((size_t)c * G + grp) * nbins;
-    for (int t = threadIdx.x; t < nbins; t += blockDim.x) out[t] = hist[t];
-    uint32_t wsum = wave_reduce_add(local);
-    if (lane_id() == 0) scratch[threadIdx.x >> 6] = wsum;
-    __syncthreads();
-    if (threadIdx.x == 0) {
-        uint32_t s = 0;
-        for (int i = 0; i < (int)(blockDim.x >> 6); ++i) s += scratch[i];
-        grp_tot[c * G + grp] = s;
-    }
-}
-
-// per (camera, bin): exclusive scan over the groups, one wave per bin (G <= 256: four strided elements per lane)
-__global__ __launch_bounds__(256) void bins_colscan_kernel(int C, int G, int nbins, uint32_t* __restrict__ hist_mat,
-                                                          uint32_t* __restrict__ bin_cnt) {
-    const int64_t i = (int64_t)blockIdx.x * 4 + (threadIdx.x >> 6);
-    if (i >= (int64_t)C * nbins) return;
-    const int c = (int)(i / nbins), t = (int)(i % nbins), lane = lane_id();
-    uint32_t* col = hist_mat + (size_t)c * G * nbins + t;
-    uint32_t v[4];
-#pragma unroll
-    for (int k = 0; k < 4; ++k) { const int g = 64 * k + lane; v[k] = g < G ? col[(size_t)g * nbins] : 0u; }
-    uint32_t carry = 0;
-#pragma unroll
-    for (int k = 0; k < 4; ++k) {
-        const uint32_t incl = wave_incl_scan_add(v[k]);
-        const int g = 64 * k + lane;
-        if (g < G) col[(size_t)g * nbins] = carry + incl - v[k];
-        carry += __shfl(incl, 63, 64);
-    }
-    if (lane == 0) bin_cnt[i] = carry;
-}
-
 // block 0: bin offsets (exclusive scan of the bin totals), chunk descriptors, info[4] = I', info[5] = longest bin list,
 // coarse overflow -> flags bit 4 (sticky under a step guard, fresh otherwise); block 1: group bases
 __global__ __launch_bounds__(kBinThreads) void bins_scan_kernel(int n_bins_total, int n_groups_total,
@@ -800,18 +789,10 @@ __global__ __launch_bounds__(kBinThreads) void bins_scan_kernel(int n_bins_total
                                                                 int guarded, int32_t* __restrict__ sort_counts,
                                                                 const int64_t* __restrict__ rblk, int phase) {
     __shared__ unsigned long long scratch[17];
-    __shared__ uint32_t smax[16];
     if (round_idle(rblk, phase)) return;
     if (blockIdx.x == 1) {   // second block of the launch: group bases, beside the bin scan
         if (threadIdx.x < 64) sort_counts[threadIdx.x] = 0;   // work-list counters of the coarse sort
-        unsigned long long gcarry = 0;
-        for (int base = 0; base < n_groups_total; base += kBinThreads) {
-            const int i = base + threadIdx.x;
-            unsigned long long v = i < n_groups_total ? grp_tot[i] : 0ull, total;
-            unsigned long long ex = block_excl_scan_add(v, scratch, &total);
-            if (i < n_groups_total) grp_base[i] = (uint32_t)(gcarry + ex);
-            gcarry += total;
-        }
+        scan_group_bases(n_groups_total, grp_tot, grp_base, scratch);
         return;
     }
     unsigned long long carry = 0, ccarry = 0;
@@ -853,14 +834,8 @@ __global__ __launch_bounds__(kBinThreads) void bins_scan_kernel(int n_bins_total
         carry += total & ((1ull << 36) - 1);
         ccarry += total >> 36;
     }
-    uint32_t m = max_cnt;
-#pragma unroll
-    for (int d = 32; d > 0; d >>= 1) m = max(m, (uint32_t)__shfl_xor((int)m, d, 64));
-    if (lane_id() == 0) smax[threadIdx.x >> 6] = m;
-    __syncthreads();
+    const uint32_t mm = block_max(max_cnt);
     if (threadIdx.x == 0) {
-        uint32_t mm = 0;
-        for (int i = 0; i < kBinThreads / 64; ++i) mm = max(mm, smax[i]);
         coff[n_bins_total] = (int32_t)min(carry, (unsigned long long)0x7fffffff);
         choff[n_bins_total] = (int32_t)ccarry;
         if (phase == 2) {   // (depth rounds: the status words show what the larger of the two rounds needed)
@@ -871,73 +846,6 @@ __global__ __launch_bounds__(kBinThreads) void bins_scan_kernel(int n_bins_total
         const int64_t f = ((int64_t)carry > coarse_cap ? 4 : 0) | ((int64_t)mm > list_cap ? 8 : 0);
         if (guarded || phase == 2) { if (f) info[3] |= f; }   // (the back round of a call adds to the front round's flags)
         else info[3] = f;
-    }
-}
-
-__global__ __launch_bounds__(kBinThreads) void bins_emit_kernel(
-    int64_t N, int shift, int bw, int nbins, int64_t per_group, const uint4* __restrict__ bbox,
-    const float* __restrict__ depths, const uint32_t* __restrict__ hist_mat, const int32_t* __restrict__ coff,
-    const uint32_t* __restrict__ grp_base, unsigned long long* __restrict__ keys, int32_t* __restrict__ cum_tiles,
-    uint4* __restrict__ rec, const int64_t* __restrict__ info, const int64_t* __restrict__ rblk, int phase) {
-    extern __shared__ __attribute__((aligned(16))) uint32_t lds[];
-    if (info[3] != 0 || round_idle(rblk, phase)) return;
-    uint32_t* cursor = lds;             // [nbins]
-    uint32_t* scratch = lds + nbins;    // [32]
-    const int grp = blockIdx.x, c = blockIdx.y, G = gridDim.x;
-    const uint32_t* mine = hist_mat + ((size_t)c * G + grp) * nbins;
-    const int32_t* boff = coff + (size_t)c * nbins;
-    for (int t0 = 0; t0 < nbins; t0 += 8 * (int)blockDim.x) {   // loads batched ahead of the LDS stores
-        uint32_t v[8];
-#pragma unroll
-        for (int k = 0; k < 8; ++k) {
-            const int t = t0 + k * (int)blockDim.x + (int)threadIdx.x;
-            v[k] = t < nbins ? mine[t] + (uint32_t)boff[t] : 0u;
-        }
-#pragma unroll
-        for (int k = 0; k < 8; ++k) {
-            const int t = t0 + k * (int)blockDim.x + (int)threadIdx.x;
-            if (t < nbins) cursor[t] = v[k];
-        }
-    }
-    __syncthreads();
-    uint32_t running = grp_base[c * G + grp] + (phase == 2 ? (uint32_t)rblk[GS_ROUND_BASE] : 0u);   // (the back round's slots continue)
-    const int64_t g0 = grp * per_group, g1 = min(N, g0 + per_group);
-    uint4 fp_next = make_uint4(0u, 0u, 0u, 0u);
-    float d_next = 0.f;
-    if (g0 + threadIdx.x < g1) { fp_next = bbox[(int64_t)c * N + g0 + threadIdx.x]; d_next = depths[(int64_t)c * N + g0 + threadIdx.x]; }
-    for (int64_t base = g0; base < g1; base += blockDim.x) {
-        const int64_t n = base + threadIdx.x;
-        const int64_t f = (int64_t)c * N + n;
-        const uint4 fp = fp_next;
-        const float dcur = d_next;
-        int cx0, cw, cy0, crect;
-        coarse_rect(n < g1 ? fp : make_uint4(0u, 0u, 0u, 0u), shift, cx0, cw, cy0, crect);
-        uint32_t total;
-        const uint32_t slot0 = running + block_excl_scan_add(n < g1 ? fp.w : 0u, scratch, &total);
-        running += total;
-        fp_next = make_uint4(0u, 0u, 0u, 0u);
-        if (n + blockDim.x < g1) { fp_next = bbox[f + blockDim.x]; d_next = depths[f + blockDim.x]; }
-        if (n < g1) {
-            if (phase != 2 || fp.w != 0u) cum_tiles[f] = (int32_t)slot0;   // (a Gaussian of the front round keeps its slots)
-            rec[f] = make_uint4(fp.x, fp.y, fp.z, slot0);
-        }
-        const unsigned long long key = ((unsigned long long)__float_as_uint(dcur) << 32) | (unsigned long long)(uint32_t)f;
-        if (crect <= kCoopTiles)
-            for (int i = 0, xx = 0, row = cy0 * bw + cx0; i < crect; ++i) {
-                keys[atomicAdd(&cursor[row + xx], 1u)] = key;
-                if (++xx == cw) { xx = 0; row += bw; }
-            }
-        unsigned long long big = __ballot(crect > kCoopTiles);
-        while (big) {
-            const int src = __ffsll((long long)big) - 1;
-            big &= big - 1;
-            const int bx0 = __shfl(cx0, src, 64), by0 = __shfl(cy0, src, 64), bcw = __shfl(cw, src, 64), bcnt = __shfl(crect, src, 64);
-            const unsigned long long bkey = __shfl(key, src, 64);
-            for (int i = lane_id(); i < bcnt; i += 64) {
-                const int yy = i / bcw;
-                keys[atomicAdd(&cursor[(by0 + yy) * bw + bx0 + (i - yy * bcw)], 1u)] = bkey;
-            }
-        }
     }
 }
 
@@ -1021,20 +929,14 @@ __global__ __launch_bounds__(64 << (2 * SHIFT)) void bins_refine_kernel(const Re
     uint32_t count = 0;
     for (int j = 0; j < m; j += 64) {
         const int e = j + lane;
-        bool hit = false;
-        int k = 0;
+        int k = -1;   // the rank of this tile inside the entry's footprint
         uint32_t f = 0;
         if (e < m) {
             const uint4 q = s_box[e];
-            int x0, x1, y0, y1;
-            unpack_bbox(q, x0, x1, y0, y1);
             f = q.w;
-            if (tx >= x0 && tx < x1 && ty >= y0 && ty < y1) {
-                const int w = x1 - x0, idx = (ty - y0) * w + (tx - x0);
-                if (w * (y1 - y0) <= kCoopTiles) { hit = (q.z >> idx) & 1u; k = __popc(q.z & ((1u << idx) - 1u)); }
-                else { hit = true; k = idx; }
-            }
+            k = fp_rank(q, tx, ty);
         }
+        const bool hit = k >= 0;
         const unsigned long long bal = __ballot(hit);
         if (WRITE) {
             if (hit) {
@@ -1094,8 +996,7 @@ __global__ __launch_bounds__(1024) void seg_merge_kernel(const SortArgs a, const
     const int s_lo = sg * kSegLen, s_n = min(kSegLen, n - s_lo);
     const int n_seg = (n + kSegLen - 1) / kSegLen;
     const unsigned long long* gk = a.keys + lo;
-    const int cam = list / max(a.tiles, 1), tix = list - cam * a.tiles;
-    const long long hi_bits = ((long long)cam << (32 + a.tile_bits)) | ((long long)tix << 32);
+    const long long id_bits = list_id_bits(a, list);
     for (int i = threadIdx.x; i < s_n; i += blockDim.x) {
         const unsigned long long k = gk[s_lo + i];
         int pos = i;
@@ -1109,14 +1010,8 @@ __global__ __launch_bounds__(1024) void seg_merge_kernel(const SortArgs a, const
             }
             pos += l;
         }
-        if (a.coarse) {
-            a.merged[lo + pos] = k;
-        } else {
-            const uint32_t slot = (uint32_t)k;
-            if (a.slot_gid) { a.slots[lo + pos] = (int32_t)slot; a.flatten_ids[lo + pos] = a.slot_gid[slot]; }
-            else a.flatten_ids[lo + pos] = (int32_t)slot;
-            if (a.isect_ids) a.isect_ids[lo + pos] = hi_bits | (long long)(k >> 32);
-        }
+        if (a.coarse) a.merged[lo + pos] = k;
+        else write_list_entry(a, lo + pos, k, id_bits);
     }
     }
 }
@@ -1140,7 +1035,10 @@ constexpr int kSortLarge = kSegLen * kSegMax;   // beyond: bitonic network in pl
 
 using namespace gs;
 
-extern "C" int gs_bin_groups(int64_t N) { return bin_layout(1, N, 1).groups; }
+extern "C" int gs_bin_groups(int64_t N) {
+    int64_t per_group;
+    return bin_groups(N, per_group);
+}
 
 // the depth round the list stages work for (gs_rounds_set): 1 front, 2 back, 0 none
 static int list_round(int64_t*& rblk) {
@@ -1162,7 +1060,6 @@ extern "C" size_t gs_bin_workspace_bytes(int C, int64_t N, int tile_w, int tile_
 //   work lists (class_items_kernel), a fixed number of blocks striding over the items
 //   beyond: bitonic network in place in global memory
 static int launch_list_sorts(hipStream_t st, SortArgs& a, unsigned grid, int64_t max_tile_count, int32_t* items_ws) {
-    int lo_excl = 0;
     int32_t* counts = items_ws;
     int32_t* items = items_ws + 64;
     const size_t radix_lds = 2 * sizeof(uint32_t) * 256;
@@ -1213,7 +1110,6 @@ static int launch_list_sorts(hipStream_t st, SortArgs& a, unsigned grid, int64_t
         hipLaunchKernelGGL(tile_sort_kernel<false>, dim3(grid), dim3(1024), 0, st, a);
         GS_LAUNCH_CHECK("tile_sort_kernel<global>");
     }
-    (void)lo_excl;
     return GS_OK;
 }
 
@@ -1238,8 +1134,8 @@ extern "C" int gs_bin_count(void* stream, int C, int64_t N, int tile_w, int tile
     uint32_t* grp_tot = (uint32_t*)(ws + L.grp_tot_off);
     uint32_t* grp_base = (uint32_t*)(ws + L.grp_base_off);
     const size_t lds = sizeof(uint32_t) * ((size_t)tiles + 32);
-    if (int rc = ensure_lds((const void*)bin_hist_kernel, lds)) return rc;
-    hipLaunchKernelGGL(bin_hist_kernel, dim3(L.groups, C), dim3(kBinThreads), lds, st, N, tile_w, tiles,
+    if (int rc = ensure_lds((const void*)bin_hist_kernel<false>, lds)) return rc;
+    hipLaunchKernelGGL(bin_hist_kernel<false>, dim3(L.groups, C), dim3(kBinThreads), lds, st, N, tile_w, tiles, 0,
                        L.per_group, (const uint4*)bbox, hist, grp_tot, (const int64_t*)rblk, phase);
     GS_LAUNCH_CHECK("bin_hist_kernel");
     const int64_t ct = (int64_t)C * tiles;
@@ -1281,17 +1177,17 @@ extern "C" int gs_bin_emit_sort(void* stream, int C, int64_t N, int tile_w, int 
     const uint32_t* hist = (const uint32_t*)(ws + L.hist_off);
     const uint32_t* grp_base = (const uint32_t*)(ws + L.grp_base_off);
     const size_t lds = sizeof(uint32_t) * ((size_t)tiles + 32);
-    if (int rc = ensure_lds((const void*)bin_emit_kernel, lds)) return rc;
-    hipLaunchKernelGGL(bin_emit_kernel, dim3(L.groups, C), dim3(kBinThreads), lds, st, N, tile_w, tiles,
-                       L.per_group, (const uint4*)bbox, depths, hist, isect_offsets, grp_base,
-                       (unsigned long long*)keys_tmp, slot_gid, cum_tiles, current_guard().info, (const int64_t*)rblk, phase);
+    EmitArgs e;
+    e.N = N; e.per_group = L.per_group; e.stride = tile_w; e.cells = tiles; e.shift = 0;
+    e.bbox = (const uint4*)bbox; e.depths = depths; e.hist_mat = hist; e.offsets = isect_offsets; e.grp_base = grp_base;
+    e.keys = (unsigned long long*)keys_tmp; e.slot_gid = slot_gid; e.cum_tiles = cum_tiles; e.rec = nullptr;
+    e.stop = current_guard().info; e.rblk = rblk; e.phase = phase;
+    if (int rc = ensure_lds((const void*)bin_emit_kernel<false>, lds)) return rc;
+    hipLaunchKernelGGL(bin_emit_kernel<false>, dim3(L.groups, C), dim3(kBinThreads), lds, st, e);
     GS_LAUNCH_CHECK("bin_emit_kernel");
     if (n_isects == 0) return GS_OK;
     SortArgs a;
-    a.tiles = tiles;
-    int tb = 0;
-    for (int v = tiles; v > 0; v >>= 1) ++tb;
-    a.tile_bits = tb;
+    a.tiles = tiles; a.tile_bits = tile_bits_of(tiles);
     a.isect_offsets = isect_offsets; a.keys = (unsigned long long*)keys_tmp; a.slot_gid = slot_gid;
     a.isect_ids = isect_ids; a.flatten_ids = flatten_ids; a.slots = slots;
     a.guard = current_guard().info;
@@ -1321,9 +1217,7 @@ static void fill_refine_args(RefineArgs& r, const BinsLayout& L, int C, int tile
     r.choff = (const int32_t*)(ws + L.choff_off);
     r.chunk_desc = (const int4*)(ws + L.chunk_bin_off);
     r.cnt_ct = (uint32_t*)(ws + L.cnt_ct_off);
-    int tb = 0;
-    for (int v = r.tiles; v > 0; v >>= 1) ++tb;
-    r.tile_bits = tb; r.bw = L.bw; r.nbins = L.nbins;
+    r.tile_bits = tile_bits_of(r.tiles); r.bw = L.bw; r.nbins = L.nbins;
     r.coff = (const int32_t*)(ws + L.coff_off);
     r.keys = (const unsigned long long*)coarse_keys;
     r.rec = (const uint4*)(ws + L.rec_off);
@@ -1370,24 +1264,28 @@ extern "C" int gs_bins_count(void* stream, int C, int64_t N, int tile_w, int til
     if (coarse_list_cap > 0) list_cap = coarse_list_cap <= 1024 ? 1024 : coarse_list_cap <= 4096 ? 4096 : coarse_list_cap <= kSegLen ? kSegLen
                                         : coarse_list_cap <= kSortLarge ? kSortLarge : 0x7fffffff;
     const size_t lds = sizeof(uint32_t) * ((size_t)L.nbins + 32);
-    if (int rc = ensure_lds((const void*)bins_hist_kernel, lds)) return rc;
-    hipLaunchKernelGGL(bins_hist_kernel, dim3(L.groups, C), dim3(kBinThreads), lds, st, N, L.shift, L.bw, L.nbins, L.per_group,
+    if (int rc = ensure_lds((const void*)bin_hist_kernel<true>, lds)) return rc;
+    hipLaunchKernelGGL(bin_hist_kernel<true>, dim3(L.groups, C), dim3(kBinThreads), lds, st, N, L.bw, L.nbins, L.shift, L.per_group,
                        (const uint4*)bbox, hist, grp_tot, (const int64_t*)rblk, phase);
-    GS_LAUNCH_CHECK("bins_hist_kernel");
+    GS_LAUNCH_CHECK("bin_hist_kernel<bins>");
     const int64_t cb = (int64_t)C * L.nbins;
-    hipLaunchKernelGGL(bins_colscan_kernel, dim3((unsigned)((cb + 3) / 4)), dim3(256), 0, st, C, L.groups, L.nbins, hist, bin_cnt);
-    GS_LAUNCH_CHECK("bins_colscan_kernel");
+    hipLaunchKernelGGL(bin_colscan_kernel, dim3((unsigned)((cb + kColTiles - 1) / kColTiles)), dim3(kColTiles * kColChunks), 0, st, C, L.groups,
+                       L.nbins, hist, bin_cnt);
+    GS_LAUNCH_CHECK("bin_colscan_kernel<bins>");
     hipLaunchKernelGGL(bins_scan_kernel, dim3(2), dim3(kBinThreads), 0, st, (int)cb, C * L.groups, bin_cnt, grp_tot, coff,
                        (int32_t*)(ws + L.choff_off), (int4*)(ws + L.chunk_bin_off), L.max_chunks, L.chunk_shift, grp_base,
                        info_dev, coarse_cap, list_cap,
                        (gd.info != nullptr && !gd.per_call) ? 1 : 0, (int32_t*)(ws + L.items_off), (const int64_t*)rblk, phase);   // (per-call guard: overwrite)
     GS_LAUNCH_CHECK("bins_scan_kernel");
     if (N > 0) {
-        if (int rc = ensure_lds((const void*)bins_emit_kernel, lds)) return rc;
-        hipLaunchKernelGGL(bins_emit_kernel, dim3(L.groups, C), dim3(kBinThreads), lds, st, N, L.shift, L.bw, L.nbins, L.per_group,
-                           (const uint4*)bbox, depths, hist, coff, grp_base, (unsigned long long*)coarse_keys, cum_tiles,
-                           (uint4*)(ws + L.rec_off), (const int64_t*)info_dev, (const int64_t*)rblk, phase);
-        GS_LAUNCH_CHECK("bins_emit_kernel");
+        EmitArgs e;
+        e.N = N; e.per_group = L.per_group; e.stride = L.bw; e.cells = L.nbins; e.shift = L.shift;
+        e.bbox = (const uint4*)bbox; e.depths = depths; e.hist_mat = hist; e.offsets = coff; e.grp_base = grp_base;
+        e.keys = (unsigned long long*)coarse_keys; e.slot_gid = nullptr; e.cum_tiles = cum_tiles; e.rec = (uint4*)(ws + L.rec_off);
+        e.stop = info_dev; e.rblk = rblk; e.phase = phase;   // (the coarse stage's own overflow flags void the emit)
+        if (int rc = ensure_lds((const void*)bin_emit_kernel<true>, lds)) return rc;
+        hipLaunchKernelGGL(bin_emit_kernel<true>, dim3(L.groups, C), dim3(kBinThreads), lds, st, e);
+        GS_LAUNCH_CHECK("bin_emit_kernel<bins>");
         SortArgs a;
         a.tiles = L.nbins; a.tile_bits = 0;
         a.isect_offsets = coff; a.keys = (unsigned long long*)coarse_keys; a.slot_gid = nullptr;

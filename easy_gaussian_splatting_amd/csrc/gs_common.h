@@ -132,6 +132,32 @@ BinLayout bin_layout(int C, int64_t N, int tiles);
 // instead of the ~35 of a run-time integer division -- which was 20 % of the projection kernel's instruction count.
 __device__ __forceinline__ int div_by_width(int i, float inv_w) { return (int)(((float)i + 0.5f) * inv_w); }
 
+// The footprint record of a Gaussian, four u32 words: x0 | x1 << 16, y0 | y1 << 16, tile mask, count -- the tile rectangle
+// [x0, x1) x [y0, y1) and which of its tiles are listed.  A rectangle of at most kMaskTiles tiles carries a row-major bit per
+// tile and count = popcount(mask); a larger one is full: mask all ones, count = its area.  count == 0: not listed (an invisible
+// Gaussian leaves four zero words).  Written by project_fwd_kernel, narrowed by the depth rounds (gs_rounds.hip), read by the
+// list stages (gs_binning.hip).  kMaskTiles is the width of the mask word -- a format constant, not a tuning knob.
+constexpr int kMaskTiles = 32;
+__device__ __forceinline__ uint32_t fp_span(int lo, int hi) { return (uint32_t)lo | ((uint32_t)hi << 16); }
+__device__ __forceinline__ uint4 fp_pack(int x0, int x1, int y0, int y1, uint32_t mask, uint32_t count) {
+    return make_uint4(fp_span(x0, x1), fp_span(y0, y1), mask, count);
+}
+__device__ __forceinline__ void fp_unpack(uint4 fp, int& x0, int& x1, int& y0, int& y1) {
+    x0 = fp.x & 0xffff; x1 = fp.x >> 16; y0 = fp.y & 0xffff; y1 = fp.y >> 16;
+}
+// the mask of a rectangle all of whose tiles are listed
+__device__ __forceinline__ uint32_t fp_full_mask(int rect_tiles) { return rect_tiles >= kMaskTiles ? 0xffffffffu : ((1u << rect_tiles) - 1u); }
+// the rank of tile (tx, ty) among the listed tiles of a footprint (row-major over the rectangle / the set mask bits: the
+// order in which the Gaussian's gradient rows are numbered), or -1 when the footprint does not list the tile
+__device__ __forceinline__ int fp_rank(uint4 fp, int tx, int ty) {
+    int x0, x1, y0, y1;
+    fp_unpack(fp, x0, x1, y0, y1);
+    if (tx < x0 || tx >= x1 || ty < y0 || ty >= y1) return -1;
+    const int w = x1 - x0, idx = (ty - y0) * w + (tx - x0);
+    if (w * (y1 - y0) > kMaskTiles) return idx;
+    return (fp.z >> idx) & 1u ? __popc(fp.z & ((1u << idx) - 1u)) : -1;
+}
+
 // ---- wavefront helpers (wave = 64 lanes on gfx950) ----
 __device__ __forceinline__ int lane_id() { return threadIdx.x & 63; }
 

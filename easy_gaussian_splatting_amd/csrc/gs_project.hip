@@ -280,17 +280,17 @@ __global__ __launch_bounds__(kProjThreads) void project_fwd_kernel(const ProjFwd
         float op = 0.f, ex = -1.f, ey = -1.f;
         if (vis) {
             x0 = s.x0; x1 = s.x1; y0 = s.y0; y1 = s.y1;   // from the unrounded centre (gs_math.h: preal)
-            if (a.rect_ref) a.rect_ref[f] = make_uint2((uint32_t)x0 | ((uint32_t)x1 << 16), (uint32_t)y0 | ((uint32_t)y1 << 16));
+            if (a.rect_ref) a.rect_ref[f] = make_uint2(fp_span(x0, x1), fp_span(y0, y1));
             op = act_opacity(op_raw, a.activations);
             alpha_extent(op, s.cxx, s.cyy, ex, ey);
             // tight mode: keep only the tiles of the 3-sigma rectangle that hold a pixel centre where
             // alpha can reach 1/255 (the blend skips every other pixel anyway: identical image)
             if (a.tight) tile_rect_tight(s.mx, s.my, ex, ey, a.W, a.H, GS_TILE, x0, x1, y0, y1);
         }
-        // tile footprint: rectangle + (for rectangles of <= 32 tiles) a row-major bit per tile
+        // tile footprint (gs_common.h: the footprint record): rectangle + (up to kMaskTiles tiles) a row-major bit per tile
         const int rw = x1 - x0, rect_tiles = rw * (y1 - y0);
-        uint32_t tmask = rect_tiles >= 32 ? 0xffffffffu : ((1u << rect_tiles) - 1u);
-        if (a.tight && rect_tiles > 0 && rect_tiles <= 32) {
+        uint32_t tmask = fp_full_mask(rect_tiles);
+        if (a.tight && rect_tiles > 0 && rect_tiles <= kMaskTiles) {
             // exact test per tile: some pixel centre of the tile must allow alpha >= 1/255
             const float tau = __log2f(255.f * op) + 0.02f, lim = tau + 1e-4f * fabsf(tau);
             const float qa = 0.5f * kLog2e * s.A, qb = kLog2e * s.B, qc = 0.5f * kLog2e * s.C;
@@ -302,13 +302,13 @@ __global__ __launch_bounds__(kProjThreads) void project_fwd_kernel(const ProjFwd
                 if (quad_min_on_rect(qa, qb, qc, dx0, dx0 + (float)(GS_TILE - 1), dy0, dy0 + (float)(GS_TILE - 1)) <= lim) tmask |= 1u << i;
             }
         }
-        const int cnt = rect_tiles <= 32 ? __popc(tmask) : rect_tiles;
+        const int cnt = rect_tiles <= kMaskTiles ? __popc(tmask) : rect_tiles;
         if (in_range) {
             a.radii[f] = s.radius;
             reinterpret_cast<float2*>(a.means2d)[f] = make_float2(s.mx, s.my);
             a.depths[f] = s.depth;
             a.conics[3 * f] = s.A; a.conics[3 * f + 1] = s.B; a.conics[3 * f + 2] = s.C;
-            a.bbox[f] = make_uint4((uint32_t)x0 | ((uint32_t)x1 << 16), (uint32_t)y0 | ((uint32_t)y1 << 16), tmask, (uint32_t)cnt);
+            a.bbox[f] = fp_pack(x0, x1, y0, y1, tmask, (uint32_t)cnt);
             a.tiles_per_gauss[f] = cnt;
             if (vis) {
                 // blend record: conic pre-scaled so the kernels evaluate exp2(-(hA dx^2 + B dx dy + hC dy^2))

@@ -58,22 +58,23 @@ __global__ __launch_bounds__(kRoundThreads) void round_select_kernel(uint32_t* _
     }
 }
 
-// w (<= 32) bits of the live-tile bitmap's row y from column x on
+// w (<= kMaskTiles) bits of the live-tile bitmap's row y from column x on
 __device__ __forceinline__ uint32_t live_row_bits(const unsigned long long* __restrict__ bits, int W64, int x, int y, int w) {
     const int j = x >> 6, sh = x & 63;
     unsigned long long v = bits[y * W64 + j] >> sh;
     if (sh + w > 64 && j + 1 < W64) v |= bits[y * W64 + j + 1] << (64 - sh);   // (sh > 32 here: the shift is in range)
-    return (uint32_t)v & (w >= 32 ? 0xffffffffu : ((1u << w) - 1u));
+    return (uint32_t)v & fp_full_mask(w);
 }
 
-// Footprints of <= 32 tiles carry a bit per tile: dead tiles leave the mask, the rectangle stays (the bits are relative to it).
+// Footprints of <= kMaskTiles tiles carry a bit per tile (gs_common.h: the footprint record): dead tiles leave the mask, the rectangle stays (the bits are relative to it).
 // A ROW of the rectangle at a time -- w bits of the bitmap shifted into place: a bit at a time (an LDS read, a division and a
 // test per tile) made this the back round's footprint pass: 48 of its 70 us at 2 M Gaussians.
 __device__ __forceinline__ uint4 window_small(uint4 fp, const unsigned long long* __restrict__ bits, int W64) {
-    const int x0 = fp.x & 0xffff, x1 = fp.x >> 16, y0 = fp.y & 0xffff, y1 = fp.y >> 16;
+    int x0, x1, y0, y1;
+    fp_unpack(fp, x0, x1, y0, y1);
     const int w = x1 - x0;
     uint32_t lv = 0u;
-    for (int y = y0, sh = 0; y < y1; ++y, sh += w) lv |= live_row_bits(bits, W64, x0, y, w) << sh;   // (sh + w <= 32)
+    for (int y = y0, sh = 0; y < y1; ++y, sh += w) lv |= live_row_bits(bits, W64, x0, y, w) << sh;   // (sh + w <= kMaskTiles)
     const uint32_t m = fp.z & lv;
     return m ? make_uint4(fp.x, fp.y, m, (uint32_t)__popc(m)) : make_uint4(0u, 0u, 0u, 0u);
 }
@@ -104,18 +105,18 @@ __device__ __forceinline__ void live_bounds_wave(int x0, int x1, int y0, int y1,
     }
 }
 
-// the footprint of a bounding rectangle of live tiles [x0, x1] x [y0, y1] (inclusive): a mask when it holds <= 32 tiles
+// the footprint of a bounding rectangle of live tiles [x0, x1] x [y0, y1] (inclusive): a mask when it holds <= kMaskTiles tiles
 __device__ __forceinline__ uint4 box_footprint(int x0, int x1, int y0, int y1, const unsigned long long* __restrict__ bits, int W64) {
     if (y1 < 0) return make_uint4(0u, 0u, 0u, 0u);
     ++x1; ++y1;
     const int w = x1 - x0, rect = w * (y1 - y0);
     uint32_t m = 0xffffffffu, cnt = (uint32_t)rect;
-    if (rect <= 32) {
+    if (rect <= kMaskTiles) {
         m = 0u;
         for (int y = y0, sh = 0; y < y1; ++y, sh += w) m |= live_row_bits(bits, W64, x0, y, w) << sh;
         cnt = (uint32_t)__popc(m);
     }
-    return make_uint4((uint32_t)x0 | ((uint32_t)x1 << 16), (uint32_t)y0 | ((uint32_t)y1 << 16), m, cnt);
+    return fp_pack(x0, x1, y0, y1, m, cnt);
 }
 
 __global__ __launch_bounds__(kRoundThreads) void round_footprints_kernel(int64_t N, int tw, int th, int W64,
@@ -147,8 +148,9 @@ __global__ __launch_bounds__(kRoundThreads) void round_footprints_kernel(int64_t
             if (in) { out[n] = o; tpg[n] = (int32_t)o.w; }
             front_n += o.w != 0u ? 1u : 0u;
         } else {
-            const int x0 = fp.x & 0xffff, x1 = fp.x >> 16, y0 = fp.y & 0xffff, y1 = fp.y >> 16;
-            const bool large = behind && (x1 - x0) * (y1 - y0) > 32;
+            int x0, x1, y0, y1;
+            fp_unpack(fp, x0, x1, y0, y1);
+            const bool large = behind && (x1 - x0) * (y1 - y0) > kMaskTiles;
             if (behind && !large) o = window_small(fp, bits, W64);
             int bx0 = 0, bx1 = -1, by0 = 0, by1 = -1;
             for (unsigned long long todo = __ballot(large); todo; todo &= todo - 1ull) {

@@ -173,7 +173,16 @@ def scene_b_footprints(C, N, tw, th):
     return bbox, kind
 
 
-B_CASES = [(C, N, 13, 7) for N in (1, 4095, 4096, 4097, 8193) for C in (1, 2)] + [(2, 4097, 7, 13)]   # (7 x 13: room for 4 x 8 masks)
+# (7 x 13: room for 4 x 8 masks; 25 x 23: 13 x 12 bins of 2 x 2 tiles, 7 x 6 of 4 x 4 -- ragged at both sizes, and room for
+#  footprints of more than 32 BINS, which the wave-cooperative branch of the coarse walk takes)
+B_CASES = [(C, N, 13, 7) for N in (1, 4095, 4096, 4097, 8193) for C in (1, 2)] + [(2, 4097, 7, 13), (1, 4097, 25, 23), (2, 1025, 25, 23)]
+
+
+def bins_touched(bbox, shift):
+    """Bins of (1 << shift)^2 tiles that the rectangle of every listed footprint touches."""
+    x0, x1, y0, y1, _, cnt = BR.unpack(bbox)
+    r = (1 << shift) - 1
+    return ((((x1 + r) >> shift) - (x0 >> shift)) * (((y1 + r) >> shift) - (y0 >> shift)))[cnt > 0]
 
 
 @pytest.mark.parametrize("pattern", ["k7", "uniform"])
@@ -181,8 +190,8 @@ B_CASES = [(C, N, 13, 7) for N in (1, 4095, 4096, 4097, 8193) for C in (1, 2)] +
 def test_mixed_footprints_hand_off_structures(C, N, tw, th, pattern):
     """Every footprint kind (one tile, sparse masks up to exactly 32 tiles, full rectangles from 33 tiles, the whole grid, 30 % of
     zero-count records with the first and the last Gaussian among them), N at the binning-group edges, tile grids that neither
-    bin size divides, one and two cameras with footprints and depths of their own: each pipeline and list kind against the
-    reference -- offsets, bucket offsets, {I, n_buckets, longest}, cum_tiles, slots, slot_gid, flatten ids, isect ids."""
+    bin size divides (25 x 23: footprints of more than 32 coarse bins at both bin sizes), one and two cameras with footprints and
+    depths of their own: each pipeline and list kind against the reference -- offsets, bucket offsets, {I, n_buckets, longest}, cum_tiles, slots, slot_gid, flatten ids, isect ids."""
     bbox, kind = scene_b_footprints(C, N, tw, th)
     if N > 1:
         kinds = {BR.FOOTPRINT_KINDS[k] for k in kind}
@@ -190,6 +199,10 @@ def test_mixed_footprints_hand_off_structures(C, N, tw, th, pattern):
         cnt = bbox[:, 3].reshape(C, N)
         assert np.all(cnt[:, 0] == 0) and np.all(cnt[:, -1] == 0) and 0.25 < (cnt == 0).mean() < 0.35
         assert (cnt[:, 1:-1] == 0).any() and ((bbox[:, 3] == 32) | (bbox[:, 3] == 33)).any()
+        for shift in (1, 2):   # a grid of more than 32 bins: both branches of the coarse walk (a lane's own loop, the whole wave)
+            if -(-tw >> shift) * -(-th >> shift) > BR.MASK_TILES:
+                nb = bins_touched(bbox, shift)
+                assert (nb > BR.MASK_TILES).any() and ((nb >= 2) & (nb <= BR.MASK_TILES)).any(), (shift, nb.max())
     bits = BR.depth_bits(pattern, C * N, np.random.default_rng(7 * N + C))
     ref = BR.reference(C, N, tw, th, bbox, bits)
     if C == 2 and N > 1:
