@@ -480,6 +480,61 @@ def _sort_class(n: int) -> int:
     return 1 << 30
 
 
+# The list and blend stages, spelled once for the eager seam below and for the captured step (train_graph.py): every workspace buffer
+# is the lease's slot of that name, the binning scratch is as large as its slot, and which pipeline / which channel entry point runs is
+# read off the lease's layout and `ch`.  `check(rc, entry point)` is the caller's wrapper; addresses are plain integers (or None).
+
+def stage_count(L, st, lease, dims, bbox, depths, coarse_list_cap, check=nat.check):
+    """Tile counts, list offsets and the size record of the footprints `bbox`; dims = (C, N, tile columns, tile rows)."""
+    (C, N, tw, th), P, lay = dims, lease.ptr, lease.layout
+    coarse_cap, shift, flags = lay.key[5:8]
+    if flags & WS.F_TWO_LEVEL:
+        check(L.gs_bins_count(st, C, N, tw, th, shift, bbox, depths, P(WS.BIN), lay.extent(WS.BIN), P(WS.COARSE_KEYS), coarse_cap, coarse_list_cap,
+                              P(WS.CUM_TILES), P(WS.ISECT_OFFSETS), P(WS.BUCKET_OFFSETS), P(WS.TILE_ORDER), P(WS.INFO), None), "gs_bins_count")
+    else:
+        check(L.gs_bin_count(st, C, N, tw, th, bbox, P(WS.BIN), lay.extent(WS.BIN), P(WS.ISECT_OFFSETS), P(WS.BUCKET_OFFSETS), P(WS.TILE_ORDER),
+                             P(WS.INFO), None), "gs_bin_count")
+
+
+def stage_lists(L, st, lease, dims, bbox, depths, n_isects, max_tile_count, check=nat.check):
+    """The sorted tile lists behind `stage_count`; n_isects and max_tile_count (the capacities of the per-tile pipeline: listed entries,
+    sort class) are the caller's."""
+    (C, N, tw, th), P, lay = dims, lease.ptr, lease.layout
+    coarse_cap, shift, flags = lay.key[5:8]
+    if flags & WS.F_TWO_LEVEL:
+        check(L.gs_bins_lists(st, C, N, tw, th, shift, bbox, P(WS.BIN), lay.extent(WS.BIN), P(WS.COARSE_KEYS), coarse_cap, P(WS.CUM_TILES),
+                              P(WS.ISECT_OFFSETS), P(WS.ISECT_IDS), P(WS.FLATTEN_IDS), P(WS.SLOTS), P(WS.INFO)), "gs_bins_lists")
+    else:
+        check(L.gs_bin_emit_sort(st, C, N, tw, th, bbox, depths, P(WS.BIN), lay.extent(WS.BIN), P(WS.ISECT_OFFSETS), n_isects, max_tile_count,
+                                 P(WS.KEYS_TMP), P(WS.SLOT_GID), P(WS.CUM_TILES), P(WS.ISECT_IDS), P(WS.FLATTEN_IDS), P(WS.SLOTS)), "gs_bin_emit_sort")
+
+
+def _ckpt_ext(lease, ch: int):   # the fourth channel's checkpoint plane: training layouts only
+    return lease.ckpt_ext() if (ch == 4 and lease.layout.key[7] & WS.F_TRAIN) else None
+
+
+def stage_blend_fwd(L, st, lease, C, W, H, ch, backgrounds, n_isects, colors, alphas, check=nat.check):
+    """The blend of the lists into `colors` / `alphas`; a training layout's walk (checkpoints, sublists, row bases) at its capacities."""
+    P, lay = lease.ptr, lease.layout
+    common = (P(WS.REC), backgrounds, P(WS.ISECT_OFFSETS), P(WS.TILE_ORDER), P(WS.FLATTEN_IDS), P(WS.SLOTS), n_isects, colors, alphas, P(WS.CKPT),
+              P(WS.QLIST), P(WS.QCNT), P(WS.QMASK), P(WS.UNIT_DESC), lay.cap_units, P(WS.ROW_BASE), lay.cap_rows, P(WS.WALK_STATE))
+    if ch == 3:
+        check(L.gs_blend_fwd(st, C, W, H, *common), "gs_blend_fwd")
+    else:
+        check(L.gs_blend_fwd_ch(st, C, W, H, ch, *common, _ckpt_ext(lease, ch)), "gs_blend_fwd_ch")
+
+
+def stage_blend_bwd(L, st, lease, C, W, H, ch, colors, alphas, v_colors, v_alphas, unit_classes, check=nat.check):
+    """The blend backward over the forward's walk: the gradient rows from the image gradients `v_colors` / `v_alphas`."""
+    P = lease.ptr
+    common = (P(WS.REC), P(WS.QLIST), P(WS.QCNT), P(WS.UNIT_DESC), lease.layout.cap_units, P(WS.CKPT), P(WS.QMASK), P(WS.ROW_BASE),
+              P(WS.WALK_STATE), colors, alphas, v_colors, v_alphas, P(WS.ROWS), unit_classes)
+    if ch == 3:
+        check(L.gs_blend_bwd(st, C, W, H, *common), "gs_blend_bwd")
+    else:
+        check(L.gs_blend_bwd_ch(st, C, W, H, ch, *common, _ckpt_ext(lease, ch)), "gs_blend_bwd_ch")
+
+
 def _forward_stages(means, quats, scales, opacities, colors, colors_rest, viewmats, Ks, backgrounds, cfg, need_grad):
     """Runs P/SH-fwd, binning, per-tile sort and B-fwd.  Returns (outputs, meta, saved-state dict).
 
@@ -568,7 +623,6 @@ def _forward_stages(means, quats, scales, opacities, colors, colors_rest, viewma
     P = lease.ptr
     info_dev = lease.view(WS.INFO, nat.GS_INFO_WORDS)
     info_host = _pinned_info(dev)
-    bin_bytes = lambda: int(L.gs_bins_workspace_bytes(C, N, tw, th, shift, coarse_cap) if two_level else L.gs_bin_workspace_bytes(C, N, tw, th))
 
     # training with SH colours: the forward leaves d colour / d view direction per visible Gaussian, and the backward never
     # reads the coefficients (include/gs_raster.h, gs_project_fwd: sh_jac)
@@ -585,40 +639,18 @@ def _forward_stages(means, quats, scales, opacities, colors, colors_rest, viewma
     def bbox_ptr():   # the footprints the list stages read: the projection's, or (depth rounds) those of the round at hand
         return rb["bbox"].data_ptr() if rounds else P(WS.BBOX)
 
+    dims = (C, N, tw, th)
+
     def count():
-        if two_level:
-            nat.check(L.gs_bins_count(st, C, N, tw, th, shift, bbox_ptr(), _ptr(depths), P(WS.BIN), bin_bytes(),
-                                      P(WS.COARSE_KEYS), coarse_cap, coarse_list_cap, P(WS.CUM_TILES), P(WS.ISECT_OFFSETS),
-                                      P(WS.BUCKET_OFFSETS), P(WS.TILE_ORDER), P(WS.INFO), None), "gs_bins_count")
-        else:
-            nat.check(L.gs_bin_count(st, C, N, tw, th, bbox_ptr(), P(WS.BIN), bin_bytes(), P(WS.ISECT_OFFSETS),
-                                     P(WS.BUCKET_OFFSETS), P(WS.TILE_ORDER), P(WS.INFO), None), "gs_bin_count")
+        stage_count(L, st, lease, dims, bbox_ptr(), _ptr(depths), coarse_list_cap)
 
     def lists_and_blend():
-        if two_level:
-            _stage("gs_bin_emit_sort", dev, lambda: nat.check(L.gs_bins_lists(
-                st, C, N, tw, th, shift, bbox_ptr(), P(WS.BIN), bin_bytes(), P(WS.COARSE_KEYS), coarse_cap,
-                P(WS.CUM_TILES), P(WS.ISECT_OFFSETS), P(WS.ISECT_IDS), P(WS.FLATTEN_IDS), P(WS.SLOTS), P(WS.INFO)), "gs_bins_lists"))
-        else:
-            _stage("gs_bin_emit_sort", dev, lambda: nat.check(L.gs_bin_emit_sort(
-                st, C, N, tw, th, bbox_ptr(), _ptr(depths), P(WS.BIN), bin_bytes(), P(WS.ISECT_OFFSETS), cap,
-                min(cap_tile, cap), P(WS.KEYS_TMP), P(WS.SLOT_GID), P(WS.CUM_TILES), P(WS.ISECT_IDS), P(WS.FLATTEN_IDS),
-                P(WS.SLOTS)), "gs_bin_emit_sort"))
+        _stage("gs_bin_emit_sort", dev, lambda: stage_lists(L, st, lease, dims, bbox_ptr(), _ptr(depths), cap, min(cap_tile, cap)))
         if walk is not None:
             nat.check(L.gs_walk_mirror_set(walk.host.data_ptr()), "gs_walk_mirror_set")
         try:
-            if ch == 3:
-                _stage("gs_blend_fwd", dev, lambda: nat.check(L.gs_blend_fwd(
-                    st, C, W, H, P(WS.REC), _ptr(backgrounds), P(WS.ISECT_OFFSETS), P(WS.TILE_ORDER),
-                    P(WS.FLATTEN_IDS), P(WS.SLOTS), cap, _ptr(render_colors), _ptr(render_alphas), P(WS.CKPT), P(WS.QLIST), P(WS.QCNT),
-                    P(WS.QMASK), P(WS.UNIT_DESC), lease.layout.cap_units, P(WS.ROW_BASE), lease.layout.cap_rows, P(WS.WALK_STATE)),
-                    "gs_blend_fwd"))
-            else:
-                _stage("gs_blend_fwd", dev, lambda: nat.check(L.gs_blend_fwd_ch(
-                    st, C, W, H, ch, P(WS.REC), _ptr(backgrounds), P(WS.ISECT_OFFSETS), P(WS.TILE_ORDER),
-                    P(WS.FLATTEN_IDS), P(WS.SLOTS), cap, _ptr(render_colors), _ptr(render_alphas), P(WS.CKPT), P(WS.QLIST), P(WS.QCNT),
-                    P(WS.QMASK), P(WS.UNIT_DESC), lease.layout.cap_units, P(WS.ROW_BASE), lease.layout.cap_rows, P(WS.WALK_STATE),
-                    lease.ckpt_ext() if (need_grad and ch == 4) else None), "gs_blend_fwd_ch"))
+            _stage("gs_blend_fwd", dev, lambda: stage_blend_fwd(L, st, lease, C, W, H, ch, _ptr(backgrounds), cap, _ptr(render_colors),
+                                                                _ptr(render_alphas)))
         finally:
             if walk is not None:
                 L.gs_walk_mirror_set(None)
@@ -870,7 +902,6 @@ def _settle_walk(s: dict, cfg: dict, render_colors: Tensor, render_alphas: Tenso
         cr = _quantize_up(rows + (rows >> 2) + 4096) if fl & WS.FLAG_ROWS else lay.cap_rows
         C, N, W, H, cap, coarse_cap, shift, flags = lay.key[:8]
         lease.grow_walk(WS.Layout(C, N, W, H, cap, coarse_cap, shift, flags, cu, cr))
-        P = lease.ptr
         with _state_lock:
             stats["walk_reruns"] += 1
         with torch.cuda.device(dev):
@@ -878,15 +909,8 @@ def _settle_walk(s: dict, cfg: dict, render_colors: Tensor, render_alphas: Tenso
             sc, sa = torch.empty_like(render_colors), torch.empty_like(render_alphas)
             nat.check(L.gs_walk_mirror_set(walk.host.data_ptr()), "gs_walk_mirror_set")
             try:
-                if s["ch"] == 3:
-                    nat.check(L.gs_blend_fwd(st, C, W, H, P(WS.REC), _ptr(s["backgrounds"]), P(WS.ISECT_OFFSETS), P(WS.TILE_ORDER),
-                                             P(WS.FLATTEN_IDS), P(WS.SLOTS), s["n_isects"], _ptr(sc), _ptr(sa), P(WS.CKPT), P(WS.QLIST),
-                                             P(WS.QCNT), P(WS.QMASK), P(WS.UNIT_DESC), cu, P(WS.ROW_BASE), cr, P(WS.WALK_STATE)), "gs_blend_fwd")
-                else:   # (the fourth channel's checkpoint plane follows the new cap_units)
-                    nat.check(L.gs_blend_fwd_ch(st, C, W, H, s["ch"], P(WS.REC), _ptr(s["backgrounds"]), P(WS.ISECT_OFFSETS),
-                                                P(WS.TILE_ORDER), P(WS.FLATTEN_IDS), P(WS.SLOTS), s["n_isects"], _ptr(sc), _ptr(sa), P(WS.CKPT),
-                                                P(WS.QLIST), P(WS.QCNT), P(WS.QMASK), P(WS.UNIT_DESC), cu, P(WS.ROW_BASE), cr, P(WS.WALK_STATE),
-                                                lease.ckpt_ext() if s["ch"] == 4 else None), "gs_blend_fwd_ch")
+                # (the capacities -- and the fourth channel's checkpoint plane -- are the new layout's)
+                stage_blend_fwd(L, st, lease, C, W, H, s["ch"], _ptr(s["backgrounds"]), s["n_isects"], _ptr(sc), _ptr(sa))
             finally:
                 L.gs_walk_mirror_set(None)
             torch.cuda.current_stream(dev).synchronize()   # (rare: the capacities follow the largest recent frame)
@@ -976,15 +1000,8 @@ class _Rasterize(torch.autograd.Function):
             _stage("gs_expected_depth_bwd", dev, lambda: nat.check(L.gs_expected_depth_bwd(
                 st, render_alphas.numel(), ch, _ptr(render_colors), _ptr(render_alphas), _ptr(v_out), _ptr(v_ra_in), _ptr(v_rc), _ptr(v_ra)),
                 "gs_expected_depth_bwd"))
-        if ch == 3:
-            _stage("gs_blend_bwd", dev, lambda: nat.check(L.gs_blend_bwd(st, C, W, H, P(WS.REC), P(WS.QLIST), P(WS.QCNT),
-                                     P(WS.UNIT_DESC), lease.layout.cap_units, P(WS.CKPT), P(WS.QMASK), P(WS.ROW_BASE), P(WS.WALK_STATE),
-                                     _ptr(render_colors), _ptr(render_alphas), _ptr(v_rc), _ptr(v_ra), P(WS.ROWS), _ptr(ucls)), "gs_blend_bwd"))
-        else:
-            _stage("gs_blend_bwd", dev, lambda: nat.check(L.gs_blend_bwd_ch(st, C, W, H, ch, P(WS.REC), P(WS.QLIST), P(WS.QCNT),
-                                     P(WS.UNIT_DESC), lease.layout.cap_units, P(WS.CKPT), P(WS.QMASK), P(WS.ROW_BASE), P(WS.WALK_STATE),
-                                     _ptr(render_colors), _ptr(render_alphas), _ptr(v_rc), _ptr(v_ra), P(WS.ROWS), _ptr(ucls),
-                                     lease.ckpt_ext() if ch == 4 else None), "gs_blend_bwd_ch"))
+        _stage("gs_blend_bwd", dev, lambda: stage_blend_bwd(L, st, lease, C, W, H, ch, _ptr(render_colors), _ptr(render_alphas), _ptr(v_rc), _ptr(v_ra),
+                                                            _ptr(ucls)))
         go = holder.grad_out or {}   # (`_grad_out`: caller-owned gradient tensors; autograd then receives None for those inputs)
         for k_, shp in (("means", (N, 3)), ("quats", (N, 4)), ("scales", (N, 3)), ("opacities", (N,)), ("grad_norm", (N,)), ("count", (N,))):
             if k_ in go and not (go[k_].shape == shp and go[k_].is_contiguous() and go[k_].dtype == torch.float32 and go[k_].device == dev):

@@ -50,6 +50,8 @@ from .rendering import _SH_JAC, _sort_class
 
 
 _TILE = nat.GS_TILE
+# the projection parameters of the captured step, forward and backward: `rendering.rasterization()`'s defaults
+EPS2D, NEAR_PLANE, FAR_PLANE, RADIUS_CLIP = 0.3, 0.01, 1e10, 0.0
 
 # Name in `buf` -> (slot of the library's workspace layout, shape of the view; a str: a dimension of the call, see `_lay`).  (-1,) is all the
 # layout gives the slot, 256-byte padding included: lengths only the library knows (scratch, slack words) -- read as a whole, garbage at the end.
@@ -336,7 +338,6 @@ class TrainStepGraph:
                     n = ext if shape == [-1] else math.prod(shape)
                     assert n <= ext, (name, shape)
                     self.buf[name] = lease.view(slot, n) if len(shape) == 1 else lease.view(slot, n).view(shape)
-        self.ws_bytes = lay.extent(WS.BIN)   # (rounded up to the alignment: the entry points ask for at least their own figure)
 
     def _alloc_walk(self):
         """What is sized by what the forward WALKS: a checkpoint, a sublist block and a descriptor per work unit, the gradient rows."""
@@ -381,15 +382,7 @@ class TrainStepGraph:
         its walk -- the counters keep counting past the capacities.  Build time only (blocking)."""
         b = self.buf
         with torch.cuda.device(self.dev), self._on_stream():
-            nat.check(nat.lib().gs_guard_set(_p(b["info"]), self.cap, self.cap_tile), "gs_guard_set")
-            try:
-                self._stage_no = 0
-                self._enqueue_forward()
-            except TrainStepGraph._Stop:
-                pass
-            finally:
-                nat.lib().gs_guard_set(None, 0, 0)
-                nat.lib().gs_rounds_set(None, None, None, None, 0)
+            self._guarded(self._enqueue_forward)
         self.stream.synchronize()
         info = b["info"].tolist()
         w = b["walk_state"][:8].tolist()
@@ -532,21 +525,14 @@ class TrainStepGraph:
         culling = {"gsplat": 1, "tight": 1, "gsplat_eager": 0}[getattr(m, "tile_culling", "tight")]
         self._ck(L.gs_project_fwd(self._st(), 1, self.N, self.K, int(m.active_sh_degree), _p(m.means), _p(m.quats), _p(m.log_scales),
                                    _p(m.logit_opacities), _p(m.sh_0), _p(m.sh_rest) if self.K > 1 else None, 0,
-                                   _p(b["viewmats"]), _p(b["Ks"]), self.W, self.H, 0.3, 0.01, 1e10, 0.0, culling, 0, 1,
+                                   _p(b["viewmats"]), _p(b["Ks"]), self.W, self.H, EPS2D, NEAR_PLANE, FAR_PLANE, RADIUS_CLIP, culling, 0, 1,
                                    _p(b["radii"]), _p(b["means2d"]), _p(b["depths"]), _p(b["conics"]), _p(b["colors_post"]),
                                    _p(b["rec"]), _p(b["bbox"]), _p(b["tiles_per_gauss"]), None, _p(b["sh_jac"])), "gs_project_fwd")
 
     def _count(self, bbox: str = "bbox"):
-        L, b = nat.lib(), self.buf
-        if self.binning == "bins":
-            self._ck(L.gs_bins_count(self._st(), 1, self.N, self.tw, self.th, self.bin_shift, _p(b[bbox]), _p(b["depths"]), _p(b["ws"]),
-                                      self.ws_bytes, _p(b["coarse_keys"]), self.cap_coarse, self.cap_coarse_list, _p(b["cum_tiles"]),
-                                      _p(b["isect_offsets"]), _p(b["bucket_offsets"]), _p(b["tile_order"]), _p(b["info"]), None),
-                     "gs_bins_count")
-        else:
-            self._ck(L.gs_bin_count(self._st(), 1, self.N, self.tw, self.th, _p(b[bbox]), _p(b["ws"]), self.ws_bytes,
-                                     _p(b["isect_offsets"]), _p(b["bucket_offsets"]), _p(b["tile_order"]), _p(b["info"]), None),
-                     "gs_bin_count")
+        b = self.buf
+        rendering.stage_count(nat.lib(), self._st(), self.lease, (1, self.N, self.tw, self.th), _p(b[bbox]), _p(b["depths"]), self.cap_coarse_list,
+                              self._ck)
 
     def _probe(self):
         """Blocking reads of the list sizes for the current inputs (build time only): {I, longest tile list} from the
@@ -554,7 +540,7 @@ class TrainStepGraph:
         from .rendering import MAX_TILES_PER_TILE_PIPELINE, bin_shift_for, binning_choice
         b, dev, tiles = self.buf, self.dev, self.tiles
         n_isects, max_tile, footprint, per_tile = 0, 0, None, tiles <= MAX_TILES_PER_TILE_PIPELINE
-        self.binning, self.bin_shift, self.cap_coarse = "tiles" if per_tile else "bins", 2, 0   # (else never counted per tile: the two-level scratch)
+        self.binning, self.bin_shift, self.cap_coarse, self.cap_coarse_list = "tiles" if per_tile else "bins", 2, 0, 0   # (else never counted per tile: the two-level scratch)
         cap, self.cap = self.cap, 0   # (the counts need nothing that the list capacity sizes: those slots are absent from `buf` here)
         self._lay(0)
         with torch.cuda.device(dev), self._on_stream():
@@ -603,83 +589,84 @@ class TrainStepGraph:
         self._rounds_phase(3)
 
     def _lists_and_blend(self, bbox: str):
-        L, b = nat.lib(), self.buf
-        st = self._st()
-        N, W, H = self.N, self.W, self.H
+        L, b, st, lease = nat.lib(), self.buf, self._st(), self.lease
         self._count(bbox)
-        if self.binning == "bins":
-            self._ck(L.gs_bins_lists(st, 1, N, self.tw, self.th, self.bin_shift, _p(b[bbox]), _p(b["ws"]), self.ws_bytes,
-                                      _p(b["coarse_keys"]), self.cap_coarse, _p(b["cum_tiles"]), _p(b["isect_offsets"]),
-                                      None, _p(b["flatten_ids"]), _p(b["slots"]), _p(b["info"])), "gs_bins_lists")
-        else:
-            self._ck(L.gs_bin_emit_sort(st, 1, N, self.tw, self.th, _p(b[bbox]), _p(b["depths"]), _p(b["ws"]), self.ws_bytes,
-                                         _p(b["isect_offsets"]), self.cap, self.cap_tile, _p(b["keys_tmp"]), _p(b["slot_gid"]),
-                                         _p(b["cum_tiles"]), None, _p(b["flatten_ids"]), _p(b["slots"])), "gs_bin_emit_sort")
-        self._ck(L.gs_blend_fwd(st, 1, W, H, _p(b["rec"]), _p(b["bg"]), _p(b["isect_offsets"]),
-                                 _p(b["tile_order"]), _p(b["flatten_ids"]), _p(b["slots"]), self.cap, _p(b["render_colors"]),
-                                 _p(b["render_alphas"]), _p(b["ckpt"]), _p(b["qlist"]), _p(b["qcnt"]), _p(b["qmask"]),
-                                 _p(b["unit_desc"]), self.cap_units, _p(b["row_base"]), self.cap_rows, _p(b["walk_state"])),
-                 "gs_blend_fwd")
+        rendering.stage_lists(L, st, lease, (1, self.N, self.tw, self.th), _p(b[bbox]), _p(b["depths"]), self.cap, self.cap_tile, self._ck)
+        # (the blend, forward and backward, walks at the LAYOUT's capacities: `_alloc_walk` laid it for the runner's as they stand)
+        assert (lease.layout.cap_units, lease.layout.cap_rows) == (self.cap_units, self.cap_rows)
+        rendering.stage_blend_fwd(L, st, lease, 1, self.W, self.H, 3, _p(b["bg"]), self.cap, _p(b["render_colors"]), _p(b["render_alphas"]), self._ck)
 
-    def _enqueue_step(self):
-        """The whole step on the current stream, guarded; nothing here allocates or synchronises."""
-        L, b, m, opt = nat.lib(), self.buf, self.model, self.opt
-        st = self._st()
-        N, W, H = self.N, self.W, self.H
-        nat.check(L.gs_guard_set(_p(b["info"]), self.cap, self.cap_tile), "gs_guard_set")
+    def _guarded(self, enqueue):
+        """`enqueue()` on the current stream under the step guard, its stages counted from one (GS_TG_STOP_AFTER cuts it short); the
+        guard and the rounds context are cleared whatever happens."""
+        L = nat.lib()
+        nat.check(L.gs_guard_set(_p(self.buf["info"]), self.cap, self.cap_tile), "gs_guard_set")
         self._stage_no = 0
         try:
+            enqueue()
+        except TrainStepGraph._Stop:
+            pass
+        finally:
+            L.gs_guard_set(None, 0, 0)
+            L.gs_rounds_set(None, None, None, None, 0)
+
+    def _enqueue_step(self):
+        """The captured step on the current stream, guarded: forward, loss and blend backward, then `_enqueue_rest` -- what the step
+        does with the gradient rows; nothing here allocates or synchronises."""
+        L, b, st, W, H = nat.lib(), self.buf, self._st(), self.W, self.H
+
+        def enqueue():
             self._enqueue_forward()
             lam = float(self.lc.lambda_ssim)
             self._ck(L.gs_l1_ssim_fwd_slots(st, H, W, lam, _p(b["render_colors"]), _p(b["img_slots"]), int(self.has_mask), 1, _p(b["loss_ws"]),
                                              _p(b["loss3"])), "gs_l1_ssim_fwd_slots")
             self._ck(L.gs_l1_ssim_bwd_slots(st, H, W, lam, _p(b["render_colors"]), _p(b["img_slots"]), 1, _p(b["loss_ws"]),
                                              _p(b["one"]), _p(b["v_render"])), "gs_l1_ssim_bwd_slots")
-            if self.scale_reg and self.fuse_adam:   # the value, from the parameters before the in-place update; the gradient: below
+            if self.scale_reg and self.fuse_adam:   # the value, from the parameters before the in-place update; the gradient: `_enqueue_rest`
                 self._scale_reg(None)
-            self._ck(L.gs_blend_bwd(st, 1, W, H, _p(b["rec"]), _p(b["qlist"]), _p(b["qcnt"]), _p(b["unit_desc"]), self.cap_units,
-                                     _p(b["ckpt"]), _p(b["qmask"]), _p(b["row_base"]), _p(b["walk_state"]),
-                                     _p(b["render_colors"]), _p(b["render_alphas"]), _p(b["v_render"]), None, _p(b["rows"]), _p(b["unit_cls"])),
-                      "gs_blend_bwd")
-            b1, b2 = opt.defaults["betas"]
-            if self.fuse_adam:
-                offs = (ct.c_int64 * 6)(*opt._offs)
-                args = (st, N, self.K, int(m.active_sh_degree), _p(opt.flat_param), _p(opt.exp_avg),
-                        _p(opt.exp_avg_sq), offs, _p(b["viewmats"]), _p(b["Ks"]), W, H, 0.3, 0.01, 1e10,
-                        _p(b["radii"]), _p(b["colors_post"]), self._tpg(), _p(b["cum_tiles"]),
-                        _p(b["rows"]), _p(b["row_base"]), _p(b["qmask"]), _p(b["v_abs"]), float(b1), float(b2),
-                        float(opt.defaults["eps"]), _p(b["hyper"]), _p(b["applied"]), _p(m.max_radii),
-                        _p(m.grad_norm_accum), _p(m.collecting_counts), _p(b["sh_jac"]))
-                if self.scale_reg:
-                    self._ck(L.gs_project_bwd_adam_reg(*args, self.max_scale_ratio, self.lambda_scale), "gs_project_bwd_adam_reg")
-                else:
-                    self._ck(L.gs_project_bwd_adam(*args), "gs_project_bwd_adam")
+            rendering.stage_blend_bwd(L, st, self.lease, 1, W, H, 3, _p(b["render_colors"]), _p(b["render_alphas"]), _p(b["v_render"]), None,
+                                      _p(b["unit_cls"]), self._ck)
+            self._enqueue_rest(st)
+        self._guarded(enqueue)
+
+    def _enqueue_rest(self, st: int):
+        """Projection / SH backward, statistics and Adam from the gradient rows, and the step's status words."""
+        L, b, m, opt = nat.lib(), self.buf, self.model, self.opt
+        N, W, H = self.N, self.W, self.H
+        b1, b2 = opt.defaults["betas"]
+        if self.fuse_adam:
+            offs = (ct.c_int64 * 6)(*opt._offs)
+            args = (st, N, self.K, int(m.active_sh_degree), _p(opt.flat_param), _p(opt.exp_avg),
+                    _p(opt.exp_avg_sq), offs, _p(b["viewmats"]), _p(b["Ks"]), W, H, EPS2D, NEAR_PLANE, FAR_PLANE,
+                    _p(b["radii"]), _p(b["colors_post"]), self._tpg(), _p(b["cum_tiles"]),
+                    _p(b["rows"]), _p(b["row_base"]), _p(b["qmask"]), _p(b["v_abs"]), float(b1), float(b2),
+                    float(opt.defaults["eps"]), _p(b["hyper"]), _p(b["applied"]), _p(m.max_radii),
+                    _p(m.grad_norm_accum), _p(m.collecting_counts), _p(b["sh_jac"]))
+            if self.scale_reg:
+                self._ck(L.gs_project_bwd_adam_reg(*args, self.max_scale_ratio, self.lambda_scale), "gs_project_bwd_adam_reg")
             else:
-                g = self.grads
-                self._ck(L.gs_project_bwd(st, 1, N, self.K, int(m.active_sh_degree), _p(m.means), _p(m.quats), _p(m.log_scales),
-                                          _p(m.sh_0), _p(m.sh_rest) if self.K > 1 else None, 0, _p(b["viewmats"]), _p(b["Ks"]), W, H,
-                                          0.3, 0.01, 1e10, _p(b["radii"]), _p(b["colors_post"]), self._tpg(),
-                                          _p(b["cum_tiles"]), _p(b["rows"]), _p(b["row_base"]), _p(b["qmask"]), _p(g["means"]), _p(g["quats"]),
-                                          _p(g["log_scales"]), _p(g["logit_opacities"]), _p(g["sh_0"]), _p(g["sh_rest"]), _p(b["v_abs"]),
-                                          None, None, None, None, _p(m.logit_opacities), 1, _p(b["sh_jac"]), None, None, None), "gs_project_bwd")
-                if self.scale_reg:   # value into the loss total, gradient onto the render's
-                    self._scale_reg(g["log_scales"])
-                self._ck(L.gs_update_statistics(st, N, float(max(H, W)), _p(b["radii"]), _p(b["v_abs"]), _p(m.max_radii),
-                                                _p(m.grad_norm_accum), _p(m.collecting_counts)), "gs_update_statistics")
-                ns = len(opt._plist)
-                ends = (ct.c_int64 * ns)(*opt._ends)
-                lens = (ct.c_int64 * ns)(*opt._lens)
-                gptr = (ct.c_void_p * ns)(*[_p(g[grp["name"]]) for grp, _ in opt._plist])
-                self._ck(L.gs_adam_step_dev(st, opt.flat_param.numel(), _p(opt.flat_param), _p(opt.exp_avg), _p(opt.exp_avg_sq), ns,
-                                            ends, lens, gptr, float(b1), float(b2), float(opt.defaults["eps"]), 1.0, _p(b["hyper"]),
-                                            _p(b["applied"])), "gs_adam_step_dev")
-            self._ck(L.gs_step_status(st, _p(b["info"]), _p(b["applied"]), self.status.data_ptr(), _p(b["loss3"]), _p(b["loss_ring"]),
-                                      self.LOSS_RING, _p(b["walk_state"])), "gs_step_status")
-        except TrainStepGraph._Stop:
-            pass
-        finally:
-            L.gs_guard_set(None, 0, 0)
-            L.gs_rounds_set(None, None, None, None, 0)
+                self._ck(L.gs_project_bwd_adam(*args), "gs_project_bwd_adam")
+        else:
+            g = self.grads
+            self._ck(L.gs_project_bwd(st, 1, N, self.K, int(m.active_sh_degree), _p(m.means), _p(m.quats), _p(m.log_scales),
+                                      _p(m.sh_0), _p(m.sh_rest) if self.K > 1 else None, 0, _p(b["viewmats"]), _p(b["Ks"]), W, H,
+                                      EPS2D, NEAR_PLANE, FAR_PLANE, _p(b["radii"]), _p(b["colors_post"]), self._tpg(),
+                                      _p(b["cum_tiles"]), _p(b["rows"]), _p(b["row_base"]), _p(b["qmask"]), _p(g["means"]), _p(g["quats"]),
+                                      _p(g["log_scales"]), _p(g["logit_opacities"]), _p(g["sh_0"]), _p(g["sh_rest"]), _p(b["v_abs"]),
+                                      None, None, None, None, _p(m.logit_opacities), 1, _p(b["sh_jac"]), None, None, None), "gs_project_bwd")
+            if self.scale_reg:   # value into the loss total, gradient onto the render's
+                self._scale_reg(g["log_scales"])
+            self._ck(L.gs_update_statistics(st, N, float(max(H, W)), _p(b["radii"]), _p(b["v_abs"]), _p(m.max_radii),
+                                            _p(m.grad_norm_accum), _p(m.collecting_counts)), "gs_update_statistics")
+            ns = len(opt._plist)
+            ends = (ct.c_int64 * ns)(*opt._ends)
+            lens = (ct.c_int64 * ns)(*opt._lens)
+            gptr = (ct.c_void_p * ns)(*[_p(g[grp["name"]]) for grp, _ in opt._plist])
+            self._ck(L.gs_adam_step_dev(st, opt.flat_param.numel(), _p(opt.flat_param), _p(opt.exp_avg), _p(opt.exp_avg_sq), ns,
+                                        ends, lens, gptr, float(b1), float(b2), float(opt.defaults["eps"]), 1.0, _p(b["hyper"]),
+                                        _p(b["applied"])), "gs_adam_step_dev")
+        self._ck(L.gs_step_status(st, _p(b["info"]), _p(b["applied"]), self.status.data_ptr(), _p(b["loss3"]), _p(b["loss_ring"]),
+                                  self.LOSS_RING, _p(b["walk_state"])), "gs_step_status")
 
     def _scale_reg(self, v_log_scales: Optional[Any], check=None):
         """The scale-ratio regulariser on the current stream: lambda * reg into loss3[2], reg into buf["scale_reg"][0], and (a gradient
@@ -981,36 +968,15 @@ class ViewParallelGraphStep(TrainStepGraph):
             self.buf["row_sums"] = self._take("row_sums", (self.N, 12), torch.float32)
             self.vp._records(); self.vp._bucket()   # (the record and the bucket the graph writes into: made before the capture)
 
-    def _enqueue_step(self):
-        """The captured part: everything up to this rank's all-gather record."""
-        L, b, m, vp = nat.lib(), self.buf, self.model, self.vp
-        st = self._st()
-        N, W, H = self.N, self.W, self.H
-        send, _ = vp._records()
-        _, offs, flat = vp._bucket()
-        nat.check(L.gs_guard_set(_p(b["info"]), self.cap, self.cap_tile), "gs_guard_set")
-        self._stage_no = 0
-        try:
-            self._enqueue_forward()
-            lam = float(self.lc.lambda_ssim)
-            self._ck(L.gs_l1_ssim_fwd_slots(st, H, W, lam, _p(b["render_colors"]), _p(b["img_slots"]), int(self.has_mask), 1, _p(b["loss_ws"]),
-                                             _p(b["loss3"])), "gs_l1_ssim_fwd_slots")
-            self._ck(L.gs_l1_ssim_bwd_slots(st, H, W, lam, _p(b["render_colors"]), _p(b["img_slots"]), 1, _p(b["loss_ws"]),
-                                             _p(b["one"]), _p(b["v_render"])), "gs_l1_ssim_bwd_slots")
-            self._ck(L.gs_blend_bwd(st, 1, W, H, _p(b["rec"]), _p(b["qlist"]), _p(b["qcnt"]), _p(b["unit_desc"]), self.cap_units,
-                                     _p(b["ckpt"]), _p(b["qmask"]), _p(b["row_base"]), _p(b["walk_state"]),
-                                     _p(b["render_colors"]), _p(b["render_alphas"]), _p(b["v_render"]), None, _p(b["rows"]), _p(b["unit_cls"])), "gs_blend_bwd")
-            sp = send.data_ptr()
-            self._ck(L.gs_row_sums(st, 1, N, _p(b["radii"]), _p(b["colors_post"]), self._tpg(), _p(b["cum_tiles"]), _p(b["rows"]),
-                                    _p(b["row_base"]), _p(b["qmask"]), _p(b["row_sums"]), sp, sp + 4 * 3 * N, float(max(H, W)), _p(b["viewmats"]),
-                                    sp + 4 * 4 * N), "gs_row_sums")
-            # this rank's guard flag: into its record and into the bucket (both collectives carry it)
-            self._ck(L.gs_guard_flag_out(st, _p(b["info"]), sp + 4 * (4 * N + 16), flat.data_ptr() + 4 * vp._flag_off), "gs_guard_flag_out")
-        except TrainStepGraph._Stop:
-            pass
-        finally:
-            L.gs_guard_set(None, 0, 0)
-            L.gs_rounds_set(None, None, None, None, 0)
+    def _enqueue_rest(self, st: int):
+        """The captured part ends with this rank's all-gather record: the row sums, and the guard flag into the record and the bucket."""
+        L, b, N, vp = nat.lib(), self.buf, self.N, self.vp
+        sp, flat = vp._records()[0].data_ptr(), vp._bucket()[2]
+        self._ck(L.gs_row_sums(st, 1, N, _p(b["radii"]), _p(b["colors_post"]), self._tpg(), _p(b["cum_tiles"]), _p(b["rows"]),
+                                _p(b["row_base"]), _p(b["qmask"]), _p(b["row_sums"]), sp, sp + 4 * 3 * N, float(max(self.H, self.W)), _p(b["viewmats"]),
+                                sp + 4 * 4 * N), "gs_row_sums")
+        # this rank's guard flag: into its record and into the bucket (both collectives carry it)
+        self._ck(L.gs_guard_flag_out(st, _p(b["info"]), sp + 4 * (4 * N + 16), flat.data_ptr() + 4 * vp._flag_off), "gs_guard_flag_out")
 
     def _tail(self, t: int, lrs):
         """Behind the graph: the two collectives and the four launches that apply the step (on the runner's stream)."""
@@ -1024,10 +990,10 @@ class ViewParallelGraphStep(TrainStepGraph):
         seg = lambda i, n: flat.data_ptr() + 4 * offs[i]   # noqa: E731
         w_gather = dist.all_gather_into_tensor(recv, send, group=vp.group, async_op=True)
         vp.collectives += 1
-        nat.check(L.gs_guard_set(_p(b["info"]), self.cap, self.cap_tile), "gs_guard_set")
-        try:
+
+        def apply():
             nat.check(L.gs_project_bwd(st, 1, N, self.K, int(m.active_sh_degree), _p(m.means), _p(m.quats), _p(m.log_scales), _p(m.sh_0),
-                                       _p(m.sh_rest) if self.K > 1 else None, 0, _p(b["viewmats"]), _p(b["Ks"]), W, H, 0.3, 0.01, 1e10, _p(b["radii"]),
+                                       _p(m.sh_rest) if self.K > 1 else None, 0, _p(b["viewmats"]), _p(b["Ks"]), W, H, EPS2D, NEAR_PLANE, FAR_PLANE, _p(b["radii"]),
                                        _p(b["colors_post"]), self._tpg(), _p(b["cum_tiles"]), _p(b["rows"]), _p(b["row_base"]), _p(b["qmask"]),
                                        seg(0, 3 * N), seg(2, 4 * N), seg(1, 3 * N), seg(3, N), None, None, _p(b["v_abs"]), None, None, None, None,
                                        _p(m.logit_opacities), 1, _p(b["sh_jac"]), _p(b["row_sums"]), seg(4, N), seg(5, N)), "gs_project_bwd")
@@ -1056,9 +1022,7 @@ class ViewParallelGraphStep(TrainStepGraph):
             nat.check(L.gs_step_applied(st, _p(b["info"]), _p(b["applied"])), "gs_step_applied")
             nat.check(L.gs_step_status(st, _p(b["info"]), _p(b["applied"]), self.status.data_ptr(), _p(b["loss3"]), _p(b["loss_ring"]),
                                        self.LOSS_RING, _p(b["walk_state"])), "gs_step_status")
-        finally:
-            L.gs_guard_set(None, 0, 0)
-            L.gs_rounds_set(None, None, None, None, 0)
+        self._guarded(apply)
 
     def _poll(self, block: bool):
         # every rank must find an overflow at the SAME step: the status words are read behind a synchronisation, never early
