@@ -12,10 +12,10 @@ Public surface (mirrors the reference's names for this path):
   mcmc.MCMCStrategy         -- training to a Gaussian budget: MCMC relocate / grow / noise on the flat Adam buffers
 """
 from .evaluate import Evaluator, evaluate_output, image_metrics  # noqa: F401
-from .mcmc import MCMCStrategy, opacity_weights, relocation_values, sample_by_weight, weight_cdf  # noqa: F401
+from .mcmc import MCMCStrategy, counter_normals, opacity_weights, relocation_values, sample_by_weight, weight_cdf  # noqa: F401
 from .rendering import rasterization  # noqa: F401
 from .viewer import FrameRenderer, camera_interpolation, export_video, finish_frame, viewer_render_func  # noqa: F401
 
 __all__ = ["rasterization", "Evaluator", "image_metrics", "evaluate_output", "FrameRenderer", "finish_frame", "camera_interpolation",
-           "export_video", "viewer_render_func", "MCMCStrategy", "opacity_weights", "weight_cdf", "sample_by_weight", "relocation_values"]
+           "export_video", "viewer_render_func", "MCMCStrategy", "opacity_weights", "weight_cdf", "sample_by_weight", "relocation_values", "counter_normals"]
 __version__ = "0.1.0"

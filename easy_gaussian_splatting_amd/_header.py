@@ -9,7 +9,7 @@ import operator
 import re
 
 _BY_VALUE = {"int": ct.c_int, "int64_t": ct.c_int64, "size_t": ct.c_size_t, "float": ct.c_float, "double": ct.c_double,
-             "int32_t": ct.c_int32, "uint32_t": ct.c_uint32}
+             "int32_t": ct.c_int32, "uint32_t": ct.c_uint32, "uint64_t": ct.c_uint64}
 _RETURNS = {**_BY_VALUE, "const char*": ct.c_char_p, "void": None}
 _OPS = {ast.Add: operator.add, ast.Sub: operator.sub, ast.Mult: operator.mul, ast.USub: operator.neg, ast.UAdd: operator.pos}
 

@@ -328,6 +328,21 @@ __device__ __forceinline__ float scale_reg_term(float l0, float l1, float l2, fl
 // scalar, which torch's device kernel does as a multiply by the scalar's reciprocal)
 inline float scale_reg_upstream(float lambda, int64_t N) { return lambda * (1.0f / (float)N); }
 
+// Budget regulariser of one Gaussian (mcmc.MCMCStrategy.regularization: a mean(opacity) + b mean(scale)): o = sigmoid(logit) and
+// s_k = exp(l_k) in fp64; the gradients ga o (1 - o) and gb s_k with the float32 upstream factors ga = fl32(a / N) and
+// gb = fl32(b / (3 N)), each rounded to float32 once.  No product feeds a sum here, so the stand-alone pass (gs_mcmc_reg) and the
+// fused one (project_bwd_budget_kernel) round alike whatever the compiler contracts around them.
+__device__ __forceinline__ void budget_reg_term(float logit, float l0, float l1, float l2, float ga, float gb, double* o_out,
+                                                double s_out[3], float* g_logit, float gl[3]) {
+    const double o = 1.0 / (1.0 + exp(-(double)logit));
+    const double s[3] = {exp((double)l0), exp((double)l1), exp((double)l2)};
+    *o_out = o;
+    *g_logit = (float)((double)ga * (o * (1.0 - o)));
+#pragma unroll
+    for (int k = 0; k < 3; ++k) { s_out[k] = s[k]; gl[k] = (float)((double)gb * s[k]); }
+}
+inline float budget_reg_upstream(double coeff, int64_t count) { return (float)(coeff / (double)count); }
+
 // streaming (non-temporal) 16-byte accesses for data that is touched once and then dead
 #ifdef __HIPCC__
 typedef float f4v __attribute__((ext_vector_type(4)));

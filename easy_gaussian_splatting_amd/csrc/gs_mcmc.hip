@@ -11,10 +11,14 @@
 //   mcmc_values_kernel       every drawn Gaussian: new opacity and scales (fp64), Adam moments of its six rows to zero
 //   mcmc_copy_kernel         every draw: the six parameter rows src[j] -> dst[j], moments of the destination to zero
 //   mcmc_noise_kernel        means += strength g(o) R diag(s^2) R^T z in fp64, four Gaussians per thread, 16-byte accesses
+//   mcmc_normals_kernel      z[n][3] = the float32 normals of (seed, step, Gaussian): one Philox4x32-10 block each, Box-Muller in fp64
+//   mcmc_step_inputs_kernel  {strength, step, seed} of the step about to run into a device record (values travel as kernel arguments)
+//   mcmc_noise_step_kernel   mcmc_noise_kernel with the normals drawn in the kernel from that record; honours the step guard
 //
 // Everything that decides (weights, opacities against min_opacity, the new values) is formed in fp64 from the fp32 parameters
 // and rounded once at the store, as the projection's covariance chain is.
 #include "gs_common.h"
+#include "gs_counter_normals.h"
 
 namespace gs {
 
@@ -209,6 +213,28 @@ __global__ __launch_bounds__(kMcmcThreads) void mcmc_copy_kernel(const McmcApply
 }
 
 // (e) ------------------------------------------------------------------------------------------------------------------------
+// One Gaussian's move: mu += strength g(o) R diag(s^2) R^T z in fp64, one rounding per component (both noise kernels call this).
+__device__ __forceinline__ void noise_move(const float* __restrict__ q, const float* __restrict__ ls, float lg, const float* __restrict__ z,
+                                           double strength, float* __restrict__ mu) {
+    double qw = q[0], qx = q[1], qy = q[2], qz = q[3];
+    const double inv = 1.0 / fmax(sqrt(qw * qw + qx * qx + qy * qy + qz * qz), 1e-12);
+    qw *= inv; qx *= inv; qy *= inv; qz *= inv;
+    const double r00 = 1.0 - 2.0 * (qy * qy + qz * qz), r01 = 2.0 * (qx * qy - qw * qz), r02 = 2.0 * (qx * qz + qw * qy);
+    const double r10 = 2.0 * (qx * qy + qw * qz), r11 = 1.0 - 2.0 * (qx * qx + qz * qz), r12 = 2.0 * (qy * qz - qw * qx);
+    const double r20 = 2.0 * (qx * qz - qw * qy), r21 = 2.0 * (qy * qz + qw * qx), r22 = 1.0 - 2.0 * (qx * qx + qy * qy);
+    const double z0 = z[0], z1 = z[1], z2 = z[2];
+    const double s0 = exp((double)ls[0]), s1 = exp((double)ls[1]), s2 = exp((double)ls[2]);
+    // R diag(s^2) R^T z
+    const double y0 = s0 * s0 * (r00 * z0 + r10 * z1 + r20 * z2);
+    const double y1 = s1 * s1 * (r01 * z0 + r11 * z1 + r21 * z2);
+    const double y2 = s2 * s2 * (r02 * z0 + r12 * z1 + r22 * z2);
+    const double o = sigmoid64(lg);
+    const double gate = strength / (1.0 + exp(-100.0 * ((1.0 - o) - 0.995)));
+    mu[0] = (float)((double)mu[0] + gate * (r00 * y0 + r01 * y1 + r02 * y2));
+    mu[1] = (float)((double)mu[1] + gate * (r10 * y0 + r11 * y1 + r12 * y2));
+    mu[2] = (float)((double)mu[2] + gate * (r20 * y0 + r21 * y1 + r22 * y2));
+}
+
 // Four Gaussians per thread: their means, log-scales and normals are three float4 each, their quaternions four, their logits
 // one.  Every pointer is 16-byte aligned (the flat buffers' segments are; the entry refuses anything else); the last, ragged
 // group goes element by element.
@@ -253,24 +279,101 @@ __global__ __launch_bounds__(kMcmcThreads) void mcmc_noise_kernel(int64_t n, dou
         }
     }
 #pragma unroll
+    for (int g = 0; g < 4; ++g) noise_move(qq + 4 * g, ls + 3 * g, lg[g], zz + 3 * g, strength, mu + 3 * g);
+    if (vec) {
+#pragma unroll
+        for (int k = 0; k < 3; ++k)
+            reinterpret_cast<float4*>(means + 3 * i0)[k] = make_float4(mu[4 * k], mu[4 * k + 1], mu[4 * k + 2], mu[4 * k + 3]);
+    } else {
+#pragma unroll
+        for (int g = 0; g < 4; ++g) {
+            if (g < cnt) {
+#pragma unroll
+                for (int k = 0; k < 3; ++k) means[3 * (i0 + g) + k] = mu[3 * g + k];
+            }
+        }
+    }
+}
+
+// (f) ------------------------------------------------------------------------------------------------------------------------
+// Same four Gaussians per thread as mcmc_noise_kernel, for the store of the normals: three float4 per full group.
+__global__ __launch_bounds__(kMcmcThreads) void mcmc_normals_kernel(int64_t n, uint64_t step, uint64_t seed, float* __restrict__ z) {
+    const int64_t i0 = 4 * ((int64_t)blockIdx.x * kMcmcThreads + threadIdx.x);
+    if (i0 >= n) return;
+    const int cnt = n - i0 < 4 ? (int)(n - i0) : 4;
+    float zz[12];
+#pragma unroll
+    for (int g = 0; g < 4; ++g) counter_normals((uint64_t)(i0 + g), step, seed, zz + 3 * g);
+    if (cnt == 4) {
+#pragma unroll
+        for (int k = 0; k < 3; ++k)
+            reinterpret_cast<float4*>(z + 3 * i0)[k] = make_float4(zz[4 * k], zz[4 * k + 1], zz[4 * k + 2], zz[4 * k + 3]);
+    } else {
+#pragma unroll
+        for (int g = 0; g < 4; ++g) {
+            if (g < cnt) {
+#pragma unroll
+                for (int k = 0; k < 3; ++k) z[3 * (i0 + g) + k] = zz[3 * g + k];
+            }
+        }
+    }
+}
+
+// The record gs_mcmc_noise_step reads: GS_MCMC_REC_WORDS int64 = {strength (the bits of a double), step, seed, 0}.
+struct McmcStepRec { int64_t w[GS_MCMC_REC_WORDS]; };
+__global__ void mcmc_step_inputs_kernel(const McmcStepRec r, int64_t* __restrict__ rec) {
+    if (threadIdx.x < (unsigned)GS_MCMC_REC_WORDS) rec[threadIdx.x] = r.w[threadIdx.x];
+}
+
+// mcmc_noise_kernel without the z array: every thread draws its four Gaussians' normals (counter_normals) from the record's
+// {step, seed} and applies the record's strength -- 12 bytes per Gaussian less than randn + mcmc_noise_kernel, and no launch
+// between them.  Under the step guard a skipped step moves nothing.
+__global__ __launch_bounds__(kMcmcThreads) void mcmc_noise_step_kernel(int64_t n, const int64_t* __restrict__ rec, const int64_t* guard,
+                                                                       const float* __restrict__ log_scales, const float* __restrict__ quats,
+                                                                       const float* __restrict__ logit, float* means) {
+    if (guard_tripped(guard)) return;
+    const int64_t i0 = 4 * ((int64_t)blockIdx.x * kMcmcThreads + threadIdx.x);
+    if (i0 >= n) return;
+    const double strength = __longlong_as_double(rec[0]);
+    const uint64_t step = (uint64_t)rec[1], seed = (uint64_t)rec[2];
+    const int cnt = n - i0 < 4 ? (int)(n - i0) : 4;
+    float mu[12], ls[12], qq[16], lg[4];
+    const bool vec = cnt == 4;
+    if (vec) {
+#pragma unroll
+        for (int k = 0; k < 3; ++k) {
+            const float4 a = reinterpret_cast<const float4*>(means + 3 * i0)[k];
+            const float4 b = reinterpret_cast<const float4*>(log_scales + 3 * i0)[k];
+            mu[4 * k] = a.x; mu[4 * k + 1] = a.y; mu[4 * k + 2] = a.z; mu[4 * k + 3] = a.w;
+            ls[4 * k] = b.x; ls[4 * k + 1] = b.y; ls[4 * k + 2] = b.z; ls[4 * k + 3] = b.w;
+        }
+#pragma unroll
+        for (int k = 0; k < 4; ++k) {
+            const float4 a = reinterpret_cast<const float4*>(quats + 4 * i0)[k];
+            qq[4 * k] = a.x; qq[4 * k + 1] = a.y; qq[4 * k + 2] = a.z; qq[4 * k + 3] = a.w;
+        }
+        const float4 a = *reinterpret_cast<const float4*>(logit + i0);
+        lg[0] = a.x; lg[1] = a.y; lg[2] = a.z; lg[3] = a.w;
+    } else {
+#pragma unroll
+        for (int g = 0; g < 4; ++g) {
+            const bool in = g < cnt;
+#pragma unroll
+            for (int k = 0; k < 3; ++k) {
+                mu[3 * g + k] = in ? means[3 * (i0 + g) + k] : 0.f;
+                ls[3 * g + k] = in ? log_scales[3 * (i0 + g) + k] : 0.f;
+            }
+#pragma unroll
+            for (int k = 0; k < 4; ++k) qq[4 * g + k] = in ? quats[4 * (i0 + g) + k] : (k == 0 ? 1.f : 0.f);
+            lg[g] = in ? logit[i0 + g] : 0.f;
+        }
+    }
+    // (one Gaussian at a time: its normals live only until its move -- the kernel stays out of scratch)
+#pragma unroll
     for (int g = 0; g < 4; ++g) {
-        double qw = qq[4 * g], qx = qq[4 * g + 1], qy = qq[4 * g + 2], qz = qq[4 * g + 3];
-        const double inv = 1.0 / fmax(sqrt(qw * qw + qx * qx + qy * qy + qz * qz), 1e-12);
-        qw *= inv; qx *= inv; qy *= inv; qz *= inv;
-        const double r00 = 1.0 - 2.0 * (qy * qy + qz * qz), r01 = 2.0 * (qx * qy - qw * qz), r02 = 2.0 * (qx * qz + qw * qy);
-        const double r10 = 2.0 * (qx * qy + qw * qz), r11 = 1.0 - 2.0 * (qx * qx + qz * qz), r12 = 2.0 * (qy * qz - qw * qx);
-        const double r20 = 2.0 * (qx * qz - qw * qy), r21 = 2.0 * (qy * qz + qw * qx), r22 = 1.0 - 2.0 * (qx * qx + qy * qy);
-        const double z0 = zz[3 * g], z1 = zz[3 * g + 1], z2 = zz[3 * g + 2];
-        const double s0 = exp((double)ls[3 * g]), s1 = exp((double)ls[3 * g + 1]), s2 = exp((double)ls[3 * g + 2]);
-        // R diag(s^2) R^T z
-        const double y0 = s0 * s0 * (r00 * z0 + r10 * z1 + r20 * z2);
-        const double y1 = s1 * s1 * (r01 * z0 + r11 * z1 + r21 * z2);
-        const double y2 = s2 * s2 * (r02 * z0 + r12 * z1 + r22 * z2);
-        const double o = sigmoid64(lg[g]);
-        const double gate = strength / (1.0 + exp(-100.0 * ((1.0 - o) - 0.995)));
-        mu[3 * g] = (float)((double)mu[3 * g] + gate * (r00 * y0 + r01 * y1 + r02 * y2));
-        mu[3 * g + 1] = (float)((double)mu[3 * g + 1] + gate * (r10 * y0 + r11 * y1 + r12 * y2));
-        mu[3 * g + 2] = (float)((double)mu[3 * g + 2] + gate * (r20 * y0 + r21 * y1 + r22 * y2));
+        float z[3];
+        counter_normals((uint64_t)(i0 + g), step, seed, z);
+        noise_move(qq + 4 * g, ls + 3 * g, lg[g], z, strength, mu + 3 * g);
     }
     if (vec) {
 #pragma unroll
@@ -403,5 +506,42 @@ extern "C" int gs_mcmc_noise(void* stream, int64_t n, double strength, const flo
     hipStream_t st = (hipStream_t)stream;
     hipLaunchKernelGGL(mcmc_noise_kernel, dim3(nb), dim3(kMcmcThreads), 0, st, n, strength, log_scales, quats, logit_opacities, z, means);
     GS_LAUNCH_CHECK("mcmc_noise_kernel");
+    return GS_OK;
+}
+
+extern "C" int gs_mcmc_normals(void* stream, int64_t n, int64_t step, uint64_t seed, float* z_out) {
+    GS_REQUIRE(n >= 0 && n < (1ll << 31), "0 <= n < 2^31");
+    GS_REQUIRE(step >= 0, "step >= 0");
+    if (n == 0) return GS_OK;
+    GS_REQUIRE(z_out != nullptr && aligned16(z_out), "z_out: non-null, 16-byte aligned");
+    hipLaunchKernelGGL(mcmc_normals_kernel, dim3(blocks_for((n + 3) / 4)), dim3(kMcmcThreads), 0, (hipStream_t)stream, n, (uint64_t)step, seed,
+                       z_out);
+    GS_LAUNCH_CHECK("mcmc_normals_kernel");
+    return GS_OK;
+}
+
+extern "C" int gs_mcmc_step_inputs(void* stream, double strength, int64_t step, uint64_t seed, int64_t* rec_dev) {
+    GS_REQUIRE(strength == strength, "strength is NaN");
+    GS_REQUIRE(step >= 0, "step >= 0");
+    GS_REQUIRE(rec_dev != nullptr && aligned16(rec_dev), "rec_dev: non-null, 16-byte aligned");
+    McmcStepRec r;
+    memcpy(&r.w[0], &strength, sizeof(double));
+    r.w[1] = step; r.w[2] = (int64_t)seed; r.w[3] = 0;
+    // values travel as kernel arguments (copied at launch): no host buffer that a later call could overwrite
+    hipLaunchKernelGGL(mcmc_step_inputs_kernel, dim3(1), dim3(64), 0, (hipStream_t)stream, r, rec_dev);
+    GS_LAUNCH_CHECK("mcmc_step_inputs_kernel");
+    return GS_OK;
+}
+
+extern "C" int gs_mcmc_noise_step(void* stream, int64_t n, const int64_t* rec_dev, const float* log_scales, const float* quats,
+                                  const float* logit_opacities, float* means) {
+    GS_REQUIRE(n >= 0 && n < (1ll << 31), "0 <= n < 2^31");
+    if (n == 0) return GS_OK;
+    GS_REQUIRE(rec_dev && log_scales && quats && logit_opacities && means, "null pointer");
+    GS_REQUIRE(aligned16(rec_dev) && aligned16(log_scales) && aligned16(quats) && aligned16(logit_opacities) && aligned16(means),
+               "pointers must be 16-byte aligned");
+    hipLaunchKernelGGL(mcmc_noise_step_kernel, dim3(blocks_for((n + 3) / 4)), dim3(kMcmcThreads), 0, (hipStream_t)stream, n, rec_dev,
+                       current_guard().info, log_scales, quats, logit_opacities, means);
+    GS_LAUNCH_CHECK("mcmc_noise_step_kernel");
     return GS_OK;
 }

@@ -402,9 +402,12 @@ struct ProjBwdArgs {
     const float* row_sums;            // optional [C*N][12]
     float *st_gn_out, *st_cnt_out;    // optional [N] each (single camera)
     const int64_t* rblk;              // depth rounds (gs_rounds_set phase 3): the rows are two ranges, split at slot rblk[GS_ROUND_BASE]
-    // Scale-ratio regulariser (gs_project_bwd_adam_reg; project_bwd_kernel<.., REG = true> only): the free ratio R and the upstream
+    // Scale-ratio regulariser (gs_project_bwd_adam_reg; REG & 1 only): the free ratio R and the upstream
     // gradient of one term, lambda * (1 / N) -- its gradient joins v_scale of every in-range Gaussian in front of the Adam update
     float reg_ratio, reg_grad;
+    // Budget regulariser (gs_project_bwd_adam_mcmc; REG & 2 only): fl32(a / N) and fl32(b / (3 N)), the upstream gradients of one
+    // opacity and of one scale -- its gradients join v_opacity and v_scale the same way (gs_common.h budget_reg_term)
+    float bud_ga, bud_gb;
 };
 
 __device__ __forceinline__ float* adam_p(const ProjBwdArgs& a, int t) { return a.ad_pbase + a.ad_off[t]; }
@@ -736,191 +739,21 @@ __device__ __forceinline__ void row_sum_wave(const A& a, int nr, int r0, int bas
 
 // SUMS: the row sums come from gs_row_sums (a.row_sums) -- an instantiation of its own, so that the row-walking form keeps the
 // registers it had (a run-time branch cost it its third wave per SIMD and put the fused form into scratch).
-// REG (with ADAM only): the scale-ratio regulariser's gradient is added to v_scale -- likewise an instantiation of its own.
-template <int DEG, bool ADAM, bool SUMS = false, bool REG = false>
+// REG (with ADAM only), a bit mask: 1 -- the scale-ratio regulariser's gradient is added to v_scale; 2 -- the budget regulariser's
+// to v_scale and v_opacity (behind the scale-ratio term when both are on) -- likewise instantiations of their own:
+// project_bwd_kernel<.., SCALE_REG = true> is mask 1, project_bwd_budget_kernel<DEG, REG> masks 2 and 3.  The two kernel templates
+// share their text (gs_project_bwd_body.h) and not a device function: behind a call, inlined or not, the compiler allocated the
+// SH4 instantiation of the existing form 68 bytes of scratch.
+template <int DEG, bool ADAM, bool SUMS = false, bool SCALE_REG = false>
 __global__ __launch_bounds__(kProjThreads) void project_bwd_kernel(const ProjBwdArgs a) {
-    extern __shared__ __attribute__((aligned(16))) float smem[];
-    if (guard_tripped(a.guard)) return;
-    if (ADAM && a.ad_applied != nullptr && blockIdx.x == 0 && threadIdx.x == 0) a.ad_applied[0] += 1;
-    float* lds_cam = smem;
-    int* vis_s = reinterpret_cast<int*>(smem + 32);
-    float* tile = smem + 32 + kProjThreads;
-
-    const int c = a.cam;
-    const int64_t n0 = (int64_t)blockIdx.x * kProjThreads;
-    const int64_t n = n0 + threadIdx.x;
-    const int64_t f = (int64_t)c * a.N + n;
-    const bool in_range = n < a.N;
-    stage_camera(a.viewmats, a.Ks, c, a.W, a.H, lds_cam);   // (read after the row sum: read_camera)
-
-    const bool vis = in_range && a.radii[f] > 0;
-    const int cnt = vis ? a.tiles_per_gauss[f] : 0;
-    const int base = vis ? a.cum_tiles[f] : 0;
-    int r0 = 0, nr = 0;   // this Gaussian's gradient rows: [r0, r0 + nr)
-    if (!SUMS && cnt > 0) { r0 = rows_before(a.row_base, a.qmask, base); nr = rows_before(a.row_base, a.qmask, base + cnt) - r0; }
-
-    // ---- 1. sum this Gaussian's gradient rows (contiguous and compact, written once each by blend_bwd) -- or take the sums gs_row_sums
-    //         left (a.row_sums: the view-parallel step forms them early, for the colour-gradient exchange)
-    RowSum s;
-    if (SUMS) {
-        const float4* rs = reinterpret_cast<const float4*>(a.row_sums) + 3 * f;
-        float4 x = make_float4(0.f, 0.f, 0.f, 0.f), y = x, z = x;
-        if (vis) { x = rs[0]; y = rs[1]; z = rs[2]; }
-        s.v[0] = x.x; s.v[1] = x.y; s.v[2] = x.z; s.v[3] = x.w; s.v[4] = y.x; s.v[5] = y.y; s.v[6] = y.z; s.v[7] = y.w;
-        s.v[8] = z.x; s.v[9] = z.y; s.v[10] = z.z; s.v[11] = 0.f;
-    } else {
-        row_sum_wave(a, nr, r0, base, s, tile + (threadIdx.x >> 6) * kRowWaveFloats);
-    }
-
-    // ---- 2. colour path
-    Camera cam;
-    read_camera(lds_cam, cam);
-    float v_mean[3] = {0.f, 0.f, 0.f}, v_quat[4] = {0.f, 0.f, 0.f, 0.f}, v_scale[3] = {0.f, 0.f, 0.f};
-    float mean[3] = {0.f, 0.f, 0.f};
-    // (the fused form reads its parameters through the flat buffer it updates: six pointers fewer to keep in SGPRs)
-    const float* p_means = ADAM ? adam_p(a, 0) : a.means;
-    const float* p_scales = ADAM ? adam_p(a, 1) : a.scales;
-    const float* p_quats = ADAM ? adam_p(a, 2) : a.quats;
-    const float* p_opac = ADAM ? adam_p(a, 5) : a.opacities;
-    if (in_range) { mean[0] = p_means[3 * n]; mean[1] = p_means[3 * n + 1]; mean[2] = p_means[3 * n + 2]; }
-    const float v_rgb[3] = {s.v[8], s.v[9], s.v[10]};
-    if (DEG >= 0) {
-        const int row_f = 3 * a.K, stride = row_f + 1;
-        constexpr int ka3 = 3 * (DEG + 1) * (DEG + 1);
-        // With the forward's direction Jacobian (a.sh_jac) the backward needs no SH coefficient: v_sh = Y (x) v_pre, and the
-        // direction term of v_mean is J^T v_pre -- the block neither streams its 48 floats per Gaussian into LDS nor waits
-        // for them (0.04 ms of the fused step kernel; the forward pays 36 B per visible Gaussian and ~200 FMAs).
-        const bool use_jac = a.sh_jac != nullptr;
-        float G[12] = {0.f, 0.f, 0.f, 0.f, 0.f, 0.f, 0.f, 0.f, 0.f, 0.f, 0.f, 0.f};
-        float rgb[3] = {0.f, 0.f, 0.f};
-        if (vis) {   // (requested before the barrier)
-            rgb[0] = a.colors_post[3 * f]; rgb[1] = a.colors_post[3 * f + 1]; rgb[2] = a.colors_post[3 * f + 2];
-            if (use_jac && DEG >= 1) {
-                const float4 j0 = a.sh_jac[2 * f], j1 = a.sh_jac[2 * f + 1];
-                G[10] = reinterpret_cast<const float*>(a.sh_jac + 2 * (int64_t)a.C * a.N)[f];
-                G[0] = j0.x; G[1] = j0.y; G[2] = j0.z; G[4] = j0.w; G[5] = j1.x; G[6] = j1.y; G[8] = j1.z; G[9] = j1.w;
-            }
-        }
-        vis_s[threadIdx.x] = vis ? 1 : 0;
-        __syncthreads();   // (every wave is done with its row-sum scratch in `tile`)
-        const int rows = (int)min((int64_t)kProjThreads, a.N - n0);
-        if (!use_jac) {
-            if (a.sh_rest) {
-                if (DEG == 4) stage_sh_rows_split<25>(a.colors_in, a.sh_rest, n0, rows, 25, ka3, vis_s, tile);   // (SH4: K = 25)
-                else if (a.K == 16) stage_sh_rows_split<16>(a.colors_in, a.sh_rest, n0, rows, 16, ka3, vis_s, tile);
-                else stage_sh_rows_split<0>(a.colors_in, a.sh_rest, n0, rows, a.K, ka3, vis_s, tile);
-            } else {
-                if (DEG == 4) stage_sh_rows<25>(a.colors_in, n0, rows, 25, ka3, vis_s, tile);
-                else if (a.K == 16) stage_sh_rows<16>(a.colors_in, n0, rows, 16, ka3, vis_s, tile);
-                else stage_sh_rows<0>(a.colors_in, n0, rows, a.K, ka3, vis_s, tile);
-            }
-            __syncthreads();
-        }
-        float* my = tile + threadIdx.x * stride;
-        if (vis) {
-            float ux, uy, uz;
-            const float dn = view_dir(mean, cam, ux, uy, uz);
-            if (use_jac) sh_vjp_jac(DEG < 0 ? 0 : DEG, G, rgb, v_rgb, ux, uy, uz, dn, my, v_mean);
-            else sh_vjp(DEG < 0 ? 0 : DEG, my, rgb, v_rgb, ux, uy, uz, dn, my, v_mean, false);
-            for (int o = ka3; o < row_f; ++o) my[o] = 0.f;
-            if (a.v_colors_pre) {  // gradient w.r.t. the pre-clamp colour: what gs_sh_grad_views consumes
-                float* d = a.v_colors_pre + 3 * f;
-                d[0] = rgb[0] > 0.f ? v_rgb[0] : 0.f; d[1] = rgb[1] > 0.f ? v_rgb[1] : 0.f; d[2] = rgb[2] > 0.f ? v_rgb[2] : 0.f;
-            }
-        } else if (in_range) {
-            for (int o = 0; o < row_f; ++o) my[o] = 0.f;
-            if (a.v_colors_pre) { float* d = a.v_colors_pre + 3 * f; d[0] = 0.f; d[1] = 0.f; d[2] = 0.f; }
-        }
-        if (ADAM) {
-            __syncthreads();
-            if (DEG == 4) adam_sh_tile<25>(tile, rows, 25, n0, a);
-            else if (a.K == 16) adam_sh_tile<16>(tile, rows, 16, n0, a);
-            else adam_sh_tile<0>(tile, rows, a.K, n0, a);
-        } else if (a.v_colors) {  // NULL: the caller rebuilds the SH gradients from v_colors_pre (gs_sh_grad_views)
-            __syncthreads();
-            if (DEG == 4) write_sh_tile_k<25>(tile, rows, 25, n0, a.v_colors, a.v_sh_rest, a.accumulate);
-            else write_sh_tile(tile, rows, a.K, n0, a.v_colors, a.v_sh_rest, a.accumulate);
-        }
-    } else if (in_range) {
-        if (a.colors_per_camera) {
-            float* d = a.v_colors + 3 * f;
-            d[0] = v_rgb[0]; d[1] = v_rgb[1]; d[2] = v_rgb[2];
-        } else {
-            float* d = a.v_colors + 3 * n;
-            if (a.accumulate) { d[0] += v_rgb[0]; d[1] += v_rgb[1]; d[2] += v_rgb[2]; }
-            else { d[0] = v_rgb[0]; d[1] = v_rgb[1]; d[2] = v_rgb[2]; }
-        }
-    }
-
-    // ---- 3. projection VJP
-    float sc_fac[3] = {1.f, 1.f, 1.f}, op_fac = 1.f;   // d activated / d raw (identity without activations)
-    if (vis) {
-        const float4 q4 = reinterpret_cast<const float4*>(p_quats)[n];
-        const float quat[4] = {q4.x, q4.y, q4.z, q4.w};
-        const float scale[3] = {act_scale(p_scales[3 * n], a.activations), act_scale(p_scales[3 * n + 1], a.activations),
-                                act_scale(p_scales[3 * n + 2], a.activations)};
-        if (a.activations) { sc_fac[0] = scale[0]; sc_fac[1] = scale[1]; sc_fac[2] = scale[2]; }
-        ProjChainT<preal> p;
-        if (project_chain<preal>(mean, quat, scale, cam, a.eps2d, a.near_p, a.far_p, p))
-            project_vjp<preal>(scale, cam, p, s.v[0], s.v[1], s.v[4], s.v[5], s.v[6], 0.f, v_mean, v_quat, v_scale);
-    }
-    float geo_op = 0.f;
-    if (in_range) {
-        if (a.activations && vis) { const float o = act_opacity(p_opac[n], 1); op_fac = o * (1.f - o); }
-        v_scale[0] *= sc_fac[0]; v_scale[1] *= sc_fac[1]; v_scale[2] *= sc_fac[2];
-        if (REG) {   // + the regulariser's gradient (culled Gaussians too: every Gaussian has a term), from the parameters before the update
-            float gl[3];
-            scale_reg_term(p_scales[3 * n], p_scales[3 * n + 1], p_scales[3 * n + 2], a.reg_ratio, a.reg_grad, gl);
-            v_scale[0] = fp_opaque(v_scale[0]) + gl[0]; v_scale[1] = fp_opaque(v_scale[1]) + gl[1]; v_scale[2] = fp_opaque(v_scale[2]) + gl[2];
-        }
-        const float v_op = s.v[7] * op_fac;
-        float* vm = a.v_means + 3 * n; float* vq = a.v_quats + 4 * n; float* vs = a.v_scales + 3 * n;
-        if (ADAM) {
-            geo_op = v_op;   // (applied block-wide below: adam_geo_tile)
-            if (a.st_max_radii != nullptr && vis) {   // same arithmetic as update_statistics_kernel
-                a.st_max_radii[n] = fmaxf(a.st_max_radii[n], (float)a.radii[f] * (1.f / a.st_max_hw));
-                a.st_grad_norm[n] += sqrtf(s.v[2] * s.v[2] + s.v[3] * s.v[3]) * a.st_max_hw;
-                a.st_counts[n] += 1.f;
-            }
-        } else if (a.accumulate) {
-            vm[0] += v_mean[0]; vm[1] += v_mean[1]; vm[2] += v_mean[2];
-            vq[0] += v_quat[0]; vq[1] += v_quat[1]; vq[2] += v_quat[2]; vq[3] += v_quat[3];
-            vs[0] += v_scale[0]; vs[1] += v_scale[1]; vs[2] += v_scale[2];
-            a.v_opacities[n] += v_op;
-        } else {
-            vm[0] = v_mean[0]; vm[1] = v_mean[1]; vm[2] = v_mean[2];
-            vq[0] = v_quat[0]; vq[1] = v_quat[1]; vq[2] = v_quat[2]; vq[3] = v_quat[3];
-            vs[0] = v_scale[0]; vs[1] = v_scale[1]; vs[2] = v_scale[2];
-            a.v_opacities[n] = v_op;
-        }
-        reinterpret_cast<float2*>(a.v_means2d_abs)[f] = make_float2(s.v[2], s.v[3]);
-        if (SUMS && a.st_gn_out) {   // (only with row_sums: the view-parallel step; the row-walking form keeps HEAD's registers)
-            a.st_gn_out[n] = vis ? sqrtf(s.v[2] * s.v[2] + s.v[3] * s.v[3]) * a.st_max_hw : 0.f;   // (update_statistics_kernel's arithmetic)
-            a.st_cnt_out[n] = vis ? 1.f : 0.f;
-        }
-        if (a.v_means2d) reinterpret_cast<float2*>(a.v_means2d)[f] = make_float2(s.v[0], s.v[1]);
-        if (a.v_conics) { a.v_conics[3 * f] = s.v[4]; a.v_conics[3 * f + 1] = s.v[5]; a.v_conics[3 * f + 2] = s.v[6]; }
-        if (a.v_colors_post) { a.v_colors_post[3 * f] = v_rgb[0]; a.v_colors_post[3 * f + 1] = v_rgb[1]; a.v_colors_post[3 * f + 2] = v_rgb[2]; }
-    }
-    if (DEG >= 0 && ADAM) {
-        // Geometry Adam, block-wide: the 11 gradients of every Gaussian of the block go through LDS into element order, and
-        // means / log-scales / quaternions / logit-opacities (+ their moments) are updated with 16-byte accesses, every load
-        // of a thread issued before its first store.  One gradient per thread and launch-order scalar accesses (33 dependent
-        // load -> store round trips per thread: the in-place stores may alias the next loads as far as the compiler can
-        // tell) took 0.08 ms of the step for 0.3 GB; same arithmetic per element, bit-identical update.
-        __syncthreads();   // (adam_sh_tile is done with the tile; every thread has read its own parameters)
-        float* gm = tile;
-        float* gs = tile + 3 * kProjThreads;
-        float* gq = tile + 6 * kProjThreads;
-        float* go = tile + 10 * kProjThreads;
-        const int tid = threadIdx.x;
-        gm[3 * tid] = v_mean[0]; gm[3 * tid + 1] = v_mean[1]; gm[3 * tid + 2] = v_mean[2];
-        gs[3 * tid] = v_scale[0]; gs[3 * tid + 1] = v_scale[1]; gs[3 * tid + 2] = v_scale[2];
-        gq[4 * tid] = v_quat[0]; gq[4 * tid + 1] = v_quat[1]; gq[4 * tid + 2] = v_quat[2]; gq[4 * tid + 3] = v_quat[3];
-        go[tid] = geo_op;
-        __syncthreads();
-        adam_geo_tile(tile, (int)min((int64_t)kProjThreads, a.N - n0), n0, a);
-    }
+    constexpr int REG = SCALE_REG ? 1 : 0;
+#include "gs_project_bwd_body.h"
+}
+// the fused form under a Gaussian budget (gs_project_bwd_adam_mcmc): REG = 2 the budget term alone, 3 behind the scale-ratio term
+template <int DEG, int REG>
+__global__ __launch_bounds__(kProjThreads) void project_bwd_budget_kernel(const ProjBwdArgs a) {
+    constexpr bool ADAM = true, SUMS = false;
+#include "gs_project_bwd_body.h"
 }
 
 static size_t proj_lds_bytes(int K, int degree);
@@ -1470,7 +1303,7 @@ static int project_bwd_adam(void* stream, int64_t N, int K, int sh_degree, float
                             const int32_t* tiles_per_gauss, const int32_t* cum_tiles, const float* rows, const int32_t* row_base, const uint8_t* qmask,
                             float* v_means2d_abs, float beta1, float beta2, float eps, const float* hyper_dev,
                             int64_t* applied_dev, float* max_radii, float* grad_norm_accum, float* counts,
-                            const float* sh_jac, bool reg, float max_ratio, float lambda) {
+                            const float* sh_jac, int reg, float max_ratio, float lambda, double bud_a, double bud_b) {
     GS_REQUIRE(N >= 0 && width > 0 && height > 0, "N>=0, positive image size");
     GS_REQUIRE(sh_degree >= 0 && sh_degree <= 4 && K >= (sh_degree + 1) * (sh_degree + 1) && K <= 25, "SH colours: 0 <= degree <= 4, (degree+1)^2 <= K <= 25");
     if (N == 0) return GS_OK;
@@ -1499,15 +1332,17 @@ static int project_bwd_adam(void* stream, int64_t N, int K, int sh_degree, float
     a.ad_pbase = params; a.ad_mbase = exp_avg; a.ad_vbase = exp_avg_sq;
     for (int t = 0; t < 6; ++t) a.ad_off[t] = offsets_host[t];
     a.cam = 0; a.accumulate = 0;
-    a.reg_ratio = max_ratio; a.reg_grad = reg ? scale_reg_upstream(lambda, N) : 0.f;
+    a.reg_ratio = max_ratio; a.reg_grad = (reg & 1) ? scale_reg_upstream(lambda, N) : 0.f;
+    a.bud_ga = (reg & 2) ? budget_reg_upstream(bud_a, N) : 0.f; a.bud_gb = (reg & 2) ? budget_reg_upstream(bud_b, 3 * N) : 0.f;
     dim3 grid((unsigned)((N + kProjThreads - 1) / kProjThreads));
     const size_t lds = proj_bwd_lds_bytes(K, sh_degree);
     hipStream_t st = (hipStream_t)stream;
     // (no row_sums form of the fused kernel: its instantiation kept a dead 36-byte stack object, and a kernel that declares
     //  scratch makes the runtime provision it -- gs_blend.hip, GS_FWD_TRAIN_WAVES_PER_EU)
+#define GS_PBK(...) { GS_LDS((__VA_ARGS__)); hipLaunchKernelGGL((__VA_ARGS__), grid, dim3(kProjThreads), lds, st, a); }
 #define GS_PB(D)                                                                                                        \
-    if (reg) { GS_LDS((project_bwd_kernel<D, true, false, true>)); hipLaunchKernelGGL((project_bwd_kernel<D, true, false, true>), grid, dim3(kProjThreads), lds, st, a); } \
-    else { GS_LDS((project_bwd_kernel<D, true, false>)); hipLaunchKernelGGL((project_bwd_kernel<D, true, false>), grid, dim3(kProjThreads), lds, st, a); }
+    if (reg == 3) GS_PBK(project_bwd_budget_kernel<D, 3>) else if (reg == 2) GS_PBK(project_bwd_budget_kernel<D, 2>)    \
+    else if (reg == 1) GS_PBK(project_bwd_kernel<D, true, false, true>) else GS_PBK(project_bwd_kernel<D, true, false>)
     switch (sh_degree) {
         case 0: GS_PB(0); break;
         case 1: GS_PB(1); break;
@@ -1516,6 +1351,7 @@ static int project_bwd_adam(void* stream, int64_t N, int K, int sh_degree, float
         default: GS_PB(4); break;
     }
 #undef GS_PB
+#undef GS_PBK
     GS_LAUNCH_CHECK("project_bwd_kernel (fused Adam)");
     return GS_OK;
 }
@@ -1529,7 +1365,7 @@ extern "C" int gs_project_bwd_adam(void* stream, int64_t N, int K, int sh_degree
                                    const float* sh_jac) {
     return project_bwd_adam(stream, N, K, sh_degree, params, exp_avg, exp_avg_sq, offsets_host, viewmats, Ks, width, height, eps2d,
                             near_plane, far_plane, radii, colors_post, tiles_per_gauss, cum_tiles, rows, row_base, qmask, v_means2d_abs,
-                            beta1, beta2, eps, hyper_dev, applied_dev, max_radii, grad_norm_accum, counts, sh_jac, false, 0.f, 0.f);
+                            beta1, beta2, eps, hyper_dev, applied_dev, max_radii, grad_norm_accum, counts, sh_jac, 0, 0.f, 0.f, 0.0, 0.0);
 }
 
 // ... with the scale-ratio regulariser's gradient in v_scale (its value: gs_scale_reg in front of this call)
@@ -1543,5 +1379,23 @@ extern "C" int gs_project_bwd_adam_reg(void* stream, int64_t N, int K, int sh_de
     GS_REQUIRE(((uintptr_t)params & 3) == 0, "params must be 4-byte aligned");
     return project_bwd_adam(stream, N, K, sh_degree, params, exp_avg, exp_avg_sq, offsets_host, viewmats, Ks, width, height, eps2d,
                             near_plane, far_plane, radii, colors_post, tiles_per_gauss, cum_tiles, rows, row_base, qmask, v_means2d_abs,
-                            beta1, beta2, eps, hyper_dev, applied_dev, max_radii, grad_norm_accum, counts, sh_jac, true, max_ratio, lambda);
+                            beta1, beta2, eps, hyper_dev, applied_dev, max_radii, grad_norm_accum, counts, sh_jac, 1, max_ratio, lambda, 0.0, 0.0);
+}
+
+// ... with the budget regulariser's gradients in v_opacity and v_scale (its value: gs_mcmc_reg in front of this call), behind the
+// scale-ratio term when `scale_reg` is set
+extern "C" int gs_project_bwd_adam_mcmc(void* stream, int64_t N, int K, int sh_degree, float* params, float* exp_avg, float* exp_avg_sq,
+                                        const int64_t* offsets_host, const float* viewmats, const float* Ks, int width, int height,
+                                        float eps2d, float near_plane, float far_plane, const int32_t* radii, const float* colors_post,
+                                        const int32_t* tiles_per_gauss, const int32_t* cum_tiles, const float* rows, const int32_t* row_base,
+                                        const uint8_t* qmask, float* v_means2d_abs, float beta1, float beta2, float eps, const float* hyper_dev,
+                                        int64_t* applied_dev, float* max_radii, float* grad_norm_accum, float* counts,
+                                        const float* sh_jac, int scale_reg, float max_ratio, float lambda, double a, double b) {
+    GS_REQUIRE(((uintptr_t)params & 3) == 0, "params must be 4-byte aligned");
+    GS_REQUIRE(scale_reg == 0 || scale_reg == 1, "scale_reg is 0 or 1");
+    GS_REQUIRE(a == a && b == b, "a or b is NaN");
+    return project_bwd_adam(stream, N, K, sh_degree, params, exp_avg, exp_avg_sq, offsets_host, viewmats, Ks, width, height, eps2d,
+                            near_plane, far_plane, radii, colors_post, tiles_per_gauss, cum_tiles, rows, row_base, qmask, v_means2d_abs,
+                            beta1, beta2, eps, hyper_dev, applied_dev, max_radii, grad_norm_accum, counts, sh_jac, 2 | scale_reg,
+                            max_ratio, lambda, a, b);
 }

@@ -7,6 +7,13 @@
     loss.backward(); optimizer.step(); optimizer.zero_grad()
     strategy.after_step(step)
 
+or, inside the captured step (`train_graph.TrainStepGraph`; INTEGRATION.md "Training to a budget, captured"):
+
+    strategy = MCMCStrategy(model, cap_max=1_500_000, noise="counter", seed=7)
+    runner = TrainStepGraph(model, optimizer, loss_computer, data, gt, mcmc=strategy)
+    ...
+    runner.step(data, gt); strategy.after_step(step, runner)
+
 Three parts: `relocate()` moves dead Gaussians (opacity <= min_opacity) onto live ones drawn in proportion to opacity, `grow()`
 adds 5 % per refinement until the hard cap `cap_max`, `inject_noise()` perturbs the means after every optimizer step.  N is known
 on the host at all times and stops changing at the cap; nothing reads the device to size anything.  `densify_and_prune` stays the
@@ -15,8 +22,13 @@ model's default refinement; this is the alternative for "train this scene with a
 The seams (`opacity_weights`, `weight_cdf`, `sample_by_weight`, `relocation_values`) are the stages of the kernels as functions
 that return tensors.  There is no torch or CPU path: HIP tensors only.
 
-Out of scope: `train_graph.TrainStepGraph` (the eager loop is the supported one; running the strategy between replays is a
-follow-up) and `distributed.ViewParallelStep` (replicas would need broadcast draws).  No default of the package changes.
+`noise="counter"`: the normals of Gaussian n at optimizer step t are a pure function of (seed, t, n) (Philox4x32-10 in the kernel,
+`counter_normals` is the seam), drawn where they are applied -- no `torch.randn`, no z array, and a captured step the guard skipped
+draws the same normals when the runner replays it.  In that mode the noise of a step comes BEFORE its relocate / grow (inside the
+captured step it cannot come anywhere else), in the eager loop too, so that the two loops walk the same trajectory.
+
+Out of scope: `distributed.ViewParallelStep` / `train_graph.ViewParallelGraphStep` (replicas would need broadcast draws), and
+relocate / grow inside the graph.  No default of the package changes.
 """
 from __future__ import annotations
 
@@ -146,6 +158,52 @@ def relocation_values(opacities: Tensor, scales: Tensor, ratio: Tensor) -> Tuple
     return new_o, new_s
 
 
+def counter_normals(n: int, step: int, seed: int, device) -> Tensor:
+    """float32 [n, 3]: the standard normals of Gaussians 0 .. n-1 at optimizer step `step` under the 64-bit `seed` -- one
+    Philox4x32-10 block per Gaussian (counter: n and step, key: seed), Box-Muller in fp64, one rounding (include/gs_raster.h)."""
+    dev = torch.device(device)
+    if dev.type != "cuda":
+        raise NotImplementedError("easy_gaussian_splatting_amd.mcmc runs on a HIP device only: there is no torch or CPU path")
+    nat, L = _native()
+    z = torch.empty((int(n), 3), dtype=torch.float32, device=dev)
+    with torch.cuda.device(dev):
+        nat.check(L.gs_mcmc_normals(_stream(dev), int(n), int(step), int(seed) & _U64, z.data_ptr()), "gs_mcmc_normals")
+    return z
+
+
+_U64 = (1 << 64) - 1
+
+
+class _BudgetReg(torch.autograd.Function):
+    """a mean(sigmoid(logit)) + b mean(exp(log_scale)) through gs_mcmc_reg: the value in forward, the gradients in backward."""
+
+    @staticmethod
+    def forward(ctx, logit: Tensor, log_scales: Tensor, a: float, b: float) -> Tensor:
+        dev = _on_device(logit, log_scales)
+        nat, L = _native()
+        n = logit.numel()
+        if logit.dtype != torch.float32 or log_scales.dtype != torch.float32 or not logit.is_contiguous() or not log_scales.is_contiguous() \
+                or log_scales.numel() != 3 * n:
+            raise ValueError("regularization(fused=True): contiguous float32 logit_opacities [N] and log_scales [N, 3]")
+        ws = torch.empty((int(L.gs_mcmc_reg_workspace_floats(n)),), dtype=torch.float32, device=dev)
+        with torch.cuda.device(dev):
+            nat.check(L.gs_mcmc_reg(_stream(dev), n, logit.data_ptr(), log_scales.data_ptr(), a, b, None, ws.data_ptr(), None, None), "gs_mcmc_reg")
+        ctx.save_for_backward(logit, log_scales)
+        ctx.ab, ctx.ws = (a, b), ws
+        return ws[0].clone()
+
+    @staticmethod
+    def backward(ctx, g: Tensor):
+        logit, log_scales = ctx.saved_tensors
+        nat, L = _native()
+        dev, n = logit.device, logit.numel()
+        v_l, v_s = torch.zeros_like(logit), torch.zeros_like(log_scales)
+        with torch.cuda.device(dev):
+            nat.check(L.gs_mcmc_reg(_stream(dev), n, logit.data_ptr(), log_scales.data_ptr(), ctx.ab[0], ctx.ab[1], None, ctx.ws.data_ptr(),
+                                    v_l.data_ptr(), v_s.data_ptr()), "gs_mcmc_reg")
+        return v_l * g, v_s * g, None, None
+
+
 def random_bits(n: int, device, generator: Optional[torch.Generator] = None) -> Tensor:
     """n words of 64 random bits as int64 (two 32-bit draws each)."""
     hi = torch.randint(-2 ** 31, 2 ** 31, (n,), dtype=torch.int64, device=device, generator=generator)
@@ -159,8 +217,14 @@ class MCMCStrategy:
 
     def __init__(self, model, cap_max: int, noise_lr: float = 5e5, refine_start: int = 500, refine_stop: int = 25_000,
                  refine_every: int = 100, min_opacity: float = 0.005, grow_factor: float = 1.05,
-                 generator: Optional[torch.Generator] = None):
+                 generator: Optional[torch.Generator] = None, noise: str = "torch", seed: int = 0):
+        """`noise`: "torch" (default) -- `inject_noise` draws `torch.randn` from `generator`; "counter" -- the draws are a pure function
+        of (`seed`, step, Gaussian), made in the kernel: the form `TrainStepGraph(mcmc=...)` needs (module docstring)."""
         from .optim import FusedAdam
+        if noise not in ("torch", "counter"):
+            raise ValueError("noise: 'torch' or 'counter'")
+        self.noise, self.seed = noise, int(seed) & _U64
+        self._rec: Optional[Tensor] = None
         if is_distributed():
             raise NotImplementedError("MCMCStrategy under torch.distributed: the replicas would need broadcast draws")
         if int(cap_max) < model.nbr_gaussians:
@@ -175,8 +239,12 @@ class MCMCStrategy:
         self.min_opacity, self.grow_factor, self.generator = float(min_opacity), float(grow_factor), generator
 
     # ---- the loss term
-    def regularization(self, opacity_reg: float = 0.01, scale_reg: float = 0.01) -> Tensor:
-        """opacity_reg mean(opacities) + scale_reg mean(scales): what makes unused Gaussians die so that relocation can move them."""
+    def regularization(self, opacity_reg: float = 0.01, scale_reg: float = 0.01, fused: bool = False) -> Tensor:
+        """opacity_reg mean(opacities) + scale_reg mean(scales): what makes unused Gaussians die so that relocation can move them.
+        `fused=True`: one HIP pass over the raw logits and log-scales (gs_mcmc_reg) for the value and one for the gradients --
+        the arithmetic of the captured step's term, bit for bit."""
+        if fused:
+            return _BudgetReg.apply(self.model.logit_opacities, self.model.log_scales, float(opacity_reg), float(scale_reg))
         return opacity_reg * self.model.opacities.mean() + scale_reg * self.model.scales.mean()
 
     # ---- plumbing
@@ -241,27 +309,58 @@ class MCMCStrategy:
         return n_new
 
     @torch.no_grad()
-    def inject_noise(self, means_lr: float) -> None:
+    def inject_noise(self, means_lr: float, step: Optional[int] = None) -> None:
         """means += noise_lr means_lr g(o) Sigma z with z standard normal, Sigma = R diag(s^2) R^T and g a sharp gate that is
-        1 for transparent Gaussians and 0 for opaque ones (1 / (1 + exp(-100 ((1 - o) - 0.995))))."""
+        1 for transparent Gaussians and 0 for opaque ones (1 / (1 + exp(-100 ((1 - o) - 0.995)))).  `noise="counter"`: z is the
+        draw of (seed, `step`, Gaussian), made inside the kernel (gs_mcmc_step_inputs + gs_mcmc_noise_step)."""
         nat, L = _native()
         model = self.model
         model.optimizer._check_views()
         n, dev = model.nbr_gaussians, model.means.device
+        if self.noise == "counter":
+            if step is None:
+                raise ValueError("inject_noise: noise='counter' draws per optimizer step, pass `step`")
+            if self._rec is None or self._rec.device != dev:
+                self._rec = torch.zeros((nat.GS_MCMC_REC_WORDS,), dtype=torch.int64, device=dev)
+            # (every argument is formed first, so that the two launches reach the queue back to back)
+            rec, strength = self._rec.data_ptr(), self.noise_lr * float(means_lr)
+            ptrs = (model.log_scales.data_ptr(), model.quats.data_ptr(), model.logit_opacities.data_ptr(), model.means.data_ptr())
+            with torch.cuda.device(dev):
+                st = _stream(dev)
+                rc0 = L.gs_mcmc_step_inputs(st, strength, int(step), self.seed, rec)
+                rc1 = L.gs_mcmc_noise_step(st, n, rec, *ptrs)
+            nat.check(rc0, "gs_mcmc_step_inputs")
+            nat.check(rc1, "gs_mcmc_noise_step")
+            return
         z = torch.randn((n, 3), device=dev, generator=self.generator)
         with torch.cuda.device(dev):
             nat.check(L.gs_mcmc_noise(_stream(dev), n, self.noise_lr * float(means_lr), model.log_scales.data_ptr(), model.quats.data_ptr(),
                                       model.logit_opacities.data_ptr(), z.data_ptr(), model.means.data_ptr()), "gs_mcmc_noise")
 
-    def after_step(self, step: int) -> Dict[str, Any]:
-        """To be called after `optimizer.step()`: relocate + grow every `refine_every` steps inside (refine_start, refine_stop],
-        noise always, at the current learning rate of the optimizer's `means` group."""
-        info: Dict[str, Any] = {}
-        if self.refine_start < step <= self.refine_stop and step % self.refine_every == 0:
-            info["relocate"] = self.relocate()
-            info["n_new"] = self.grow()
+    def _means_lr(self) -> float:
         for group in self.model.optimizer.param_groups:
             if group.get("name") == "means":
-                self.inject_noise(float(group["lr"]))
-                return info
+                return float(group["lr"])
         raise RuntimeError("the param_group 'means' isn't in the optimizer")
+
+    def after_step(self, step: int, runner=None) -> Dict[str, Any]:
+        """To be called after `optimizer.step()`: relocate + grow every `refine_every` steps inside (refine_start, refine_stop],
+        noise always, at the current learning rate of the optimizer's `means` group.
+        `runner` (a `TrainStepGraph(mcmc=self)`, to be called after its `step()`): the noise ran inside the step; before rows move
+        the runner's pending steps are applied (`finish()`: one block per `refine_every` steps).  `relocate()` works in place and the
+        graph is kept; `grow()` changes N and the storage, which the runner answers with a re-build on its next `step()`."""
+        info: Dict[str, Any] = {}
+        refine = self.refine_start < step <= self.refine_stop and step % self.refine_every == 0
+        if runner is not None:
+            if getattr(runner, "mcmc", None) is not self:
+                raise ValueError("after_step(step, runner): the runner was not built with mcmc=<this strategy>")
+            if refine:
+                runner.finish()
+        elif self.noise == "counter":   # in front of relocate / grow, where the captured step has it
+            self.inject_noise(self._means_lr(), step)
+        if refine:
+            info["relocate"] = self.relocate()
+            info["n_new"] = self.grow()
+        if runner is None and self.noise == "torch":
+            self.inject_noise(self._means_lr())
+        return info

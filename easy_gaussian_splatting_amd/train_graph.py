@@ -29,6 +29,11 @@ them, so the two paths agree bit for bit (tests/test_gpu_train_graph.py) -- but
 
 A change of N (densify_and_prune), of the parameter storage (reset_opacities), of the active SH degree or of
 the image size re-builds the workspace and re-captures.
+
+Training to a Gaussian budget (`mcmc=MCMCStrategy(..., noise="counter")`): the budget regulariser joins the loss total and the
+gradients (gs_mcmc_reg / gs_project_bwd_adam_mcmc), and the noise runs behind Adam inside the guarded sequence with draws that are a
+pure function of (seed, step, Gaussian) (gs_mcmc_noise_step) -- a skipped step that is replayed draws what it would have drawn.
+Relocate / grow stay between the steps: `strategy.after_step(step, runner)`.
 """
 from __future__ import annotations
 
@@ -37,7 +42,7 @@ import math
 import time
 from collections import deque
 from collections.abc import Mapping
-from typing import Any, Dict, Optional
+from typing import Any, Dict, Optional, Tuple
 
 import torch
 from torch import Tensor
@@ -80,8 +85,11 @@ class TrainStepGraph:
     def __init__(self, model, optimizer: FusedAdam, loss_computer, data: Dict[str, Any], gt_img: Tensor,
                  mask: Optional[Tensor] = None, margin: float = 1.3, use_graph: bool = True, check_every: int = 16,
                  fuse_adam: bool = True, handback: str = "eager", copy_targets: bool = False, rounds: str = "auto",
-                 round_fraction: float = 0.125):
-        """`handback`: when the caller's stream is ordered behind a step.
+                 round_fraction: float = 0.125, mcmc=None, mcmc_reg: Tuple[float, float] = (0.01, 0.01)):
+        """`mcmc`: an `mcmc.MCMCStrategy(model, ..., noise="counter")` -- the step then trains under its Gaussian budget: `mcmc_reg` =
+        (opacity_reg, scale_reg) of `strategy.regularization()` enters the loss (out["mcmc_reg"]) and the update, and the strategy's
+        noise runs behind Adam inside the step, at noise_lr x the means learning rate of that step.  None (default): nothing changes.
+        `handback`: when the caller's stream is ordered behind a step.
         "eager" (default): on return from every `step()` -- whatever the caller enqueues next (a read of the outputs, an eval
         render that reads the parameters, `densify_and_prune`) sees the finished step, no thought required.
         "lazy": only when the caller touches the returned outputs (`out["loss3"]`, ...), calls `fence()` or `finish()`.
@@ -91,6 +99,14 @@ class TrainStepGraph:
         and statistics are NOT intercepted: a lazy caller that reads them between steps calls `fence()` first.
         Cameras are constants here: a `data["w2c"]` that requires grad raises `ValueError` (here and in `step`) -- the captured
         step's fused-Adam projection backward has no camera output; refine poses in the eager loop."""
+        self.mcmc = mcmc
+        if mcmc is not None:
+            if getattr(mcmc, "noise", None) != "counter":
+                raise ValueError("TrainStepGraph(mcmc=...): the strategy must draw counter-based noise, MCMCStrategy(..., noise='counter') -- "
+                                 "a skipped step that is replayed has to draw the normals it would have drawn")
+            if mcmc.model is not model:
+                raise ValueError("TrainStepGraph: the MCMCStrategy works on another model than the one the runner trains")
+            self.mcmc_reg = (float(mcmc_reg[0]), float(mcmc_reg[1]))
         _refuse_camera_grads(data)
         if handback not in ("eager", "lazy"):
             raise ValueError("handback: 'eager' or 'lazy'")
@@ -221,6 +237,11 @@ class TrainStepGraph:
         b["hyper"] = torch.zeros((16,), **f32)
         # {reg, -, fp64 block partials}: the regulariser's value and its reduction scratch (gs_scale_reg)
         b["scale_reg"] = self._take("scale_reg", (int(L.gs_scale_reg_workspace_floats(N)),), torch.float32) if self.scale_reg else None
+        if self.mcmc is not None:
+            # {reg, -, fp64 block partials} of the budget regulariser (gs_mcmc_reg); {strength, step, seed} of the step's noise
+            b["mcmc_reg"] = self._take("mcmc_reg", (int(L.gs_mcmc_reg_workspace_floats(N)),), torch.float32)
+            b["mcmc_rec"] = torch.zeros((nat.GS_MCMC_REC_WORDS,), dtype=torch.int64, device=dev)
+            self._means_seg = [grp["name"] for grp, _ in self.opt._plist].index("means")
         self._stage_inputs(max(self.opt._step, 0) + 1, [float(grp["lr"]) for grp, _ in self.opt._plist], data["w2c"], data["K"], gt_img, mask)
         probe_walk = False
         front_before, self.front_only = self.front_only, False   # (the probes below run both rounds)
@@ -442,6 +463,9 @@ class TrainStepGraph:
         b1, b2 = opt.defaults["betas"]
         nat.check(L.gs_step_inputs(self._st(), ns, (ct.c_float * ns)(*lrs), float(b1), float(b2), int(t), _p(b["hyper"]), _p(vm_src),
                                    _p(b["viewmats"]), _p(k_src), _p(b["Ks"]), _p(gt), _p(mask), _p(b["img_slots"])), "gs_step_inputs")
+        if self.mcmc is not None:   # the step's noise: its strength at the means learning rate this step's Adam uses, its counter, the seed
+            nat.check(L.gs_mcmc_step_inputs(self._st(), self.mcmc.noise_lr * float(lrs[self._means_seg]), int(t), self.mcmc.seed,
+                                            _p(b["mcmc_rec"])), "gs_mcmc_step_inputs")
         self._cur_images = (gt, mask)
         return gt, mask
 
@@ -624,6 +648,8 @@ class TrainStepGraph:
                                              _p(b["one"]), _p(b["v_render"])), "gs_l1_ssim_bwd_slots")
             if self.scale_reg and self.fuse_adam:   # the value, from the parameters before the in-place update; the gradient: `_enqueue_rest`
                 self._scale_reg(None)
+            if self.mcmc is not None and self.fuse_adam:   # likewise the budget regulariser's, behind it in the total
+                self._mcmc_reg(None, None)
             rendering.stage_blend_bwd(L, st, self.lease, 1, W, H, 3, _p(b["render_colors"]), _p(b["render_alphas"]), _p(b["v_render"]), None,
                                       _p(b["unit_cls"]), self._ck)
             self._enqueue_rest(st)
@@ -642,7 +668,10 @@ class TrainStepGraph:
                     _p(b["rows"]), _p(b["row_base"]), _p(b["qmask"]), _p(b["v_abs"]), float(b1), float(b2),
                     float(opt.defaults["eps"]), _p(b["hyper"]), _p(b["applied"]), _p(m.max_radii),
                     _p(m.grad_norm_accum), _p(m.collecting_counts), _p(b["sh_jac"]))
-            if self.scale_reg:
+            if self.mcmc is not None:
+                self._ck(L.gs_project_bwd_adam_mcmc(*args, int(self.scale_reg), self.max_scale_ratio if self.scale_reg else 0.0,
+                                                     self.lambda_scale if self.scale_reg else 0.0, *self.mcmc_reg), "gs_project_bwd_adam_mcmc")
+            elif self.scale_reg:
                 self._ck(L.gs_project_bwd_adam_reg(*args, self.max_scale_ratio, self.lambda_scale), "gs_project_bwd_adam_reg")
             else:
                 self._ck(L.gs_project_bwd_adam(*args), "gs_project_bwd_adam")
@@ -656,6 +685,8 @@ class TrainStepGraph:
                                       None, None, None, None, _p(m.logit_opacities), 1, _p(b["sh_jac"]), None, None, None), "gs_project_bwd")
             if self.scale_reg:   # value into the loss total, gradient onto the render's
                 self._scale_reg(g["log_scales"])
+            if self.mcmc is not None:
+                self._mcmc_reg(g["logit_opacities"], g["log_scales"])
             self._ck(L.gs_update_statistics(st, N, float(max(H, W)), _p(b["radii"]), _p(b["v_abs"]), _p(m.max_radii),
                                             _p(m.grad_norm_accum), _p(m.collecting_counts)), "gs_update_statistics")
             ns = len(opt._plist)
@@ -665,6 +696,9 @@ class TrainStepGraph:
             self._ck(L.gs_adam_step_dev(st, opt.flat_param.numel(), _p(opt.flat_param), _p(opt.exp_avg), _p(opt.exp_avg_sq), ns,
                                         ends, lens, gptr, float(b1), float(b2), float(opt.defaults["eps"]), 1.0, _p(b["hyper"]),
                                         _p(b["applied"])), "gs_adam_step_dev")
+        if self.mcmc is not None:   # the noise, on the updated parameters; a skipped step adds none
+            self._ck(L.gs_mcmc_noise_step(st, N, _p(b["mcmc_rec"]), _p(m.log_scales), _p(m.quats), _p(m.logit_opacities), _p(m.means)),
+                     "gs_mcmc_noise_step")
         self._ck(L.gs_step_status(st, _p(b["info"]), _p(b["applied"]), self.status.data_ptr(), _p(b["loss3"]), _p(b["loss_ring"]),
                                   self.LOSS_RING, _p(b["walk_state"])), "gs_step_status")
 
@@ -675,6 +709,13 @@ class TrainStepGraph:
         v = v_log_scales if (v_log_scales is None or isinstance(v_log_scales, int)) else v_log_scales.data_ptr()
         (check or self._ck)(nat.lib().gs_scale_reg(self._st(), self.N, _p(m.log_scales), self.max_scale_ratio, self.lambda_scale, _p(b["loss3"]),
                                         _p(b["scale_reg"]), v), "gs_scale_reg")
+
+    def _mcmc_reg(self, v_logit: Optional[Tensor], v_log_scales: Optional[Tensor]):
+        """The budget regulariser on the current stream: reg into loss3[2] and buf["mcmc_reg"][0], and (gradient tensors given) its
+        gradients added to them."""
+        b, m = self.buf, self.model
+        self._ck(nat.lib().gs_mcmc_reg(self._st(), self.N, _p(m.logit_opacities), _p(m.log_scales), self.mcmc_reg[0], self.mcmc_reg[1],
+                                       _p(b["loss3"]), _p(b["mcmc_reg"]), _p(v_logit), _p(v_log_scales)), "gs_mcmc_reg")
 
     def _tail(self, t: int, lrs):
         """What a step enqueues behind its graph (nothing: the single-GPU step is the graph)."""
@@ -855,6 +896,8 @@ class TrainStepGraph:
         outs = {"render_img": b["render_colors"][0], "loss3": b["loss3"], "batch_radii": b["radii"], "absgrad": b["v_abs"]}
         if self.scale_reg:
             outs["scale_reg"] = b["scale_reg"][0]   # (0-d, the eager loss dict's "scale_reg")
+        if self.mcmc is not None:
+            outs["mcmc_reg"] = b["mcmc_reg"][0]   # (0-d, `strategy.regularization(*mcmc_reg)`)
         return TrainStepGraph._StepOutputs(self, outs, lazy=self.handback == "lazy")
 
     def _poll(self, block: bool):
@@ -925,6 +968,8 @@ class TrainStepGraph:
 
     def report(self) -> Dict[str, Any]:
         extra = dict(scale_reg=True, max_scale_ratio=self.max_scale_ratio, lambda_scale=self.lambda_scale) if self.scale_reg else {}
+        if self.mcmc is not None:
+            extra.update(mcmc=True, mcmc_reg=self.mcmc_reg, mcmc_seed=self.mcmc.seed, mcmc_noise_lr=self.mcmc.noise_lr)
         return dict(self.stats, **extra, binning=self.binning, probed_isects=self.probed[0], probed_longest_list=self.probed[1],
                     probed_coarse_entries=getattr(self, "probed_coarse", (0, 0))[0] if self.binning == "bins" else 0,
                     capacity_isects=self.cap, capacity_tile_list=self.cap_tile, capacity_work_units=self.cap_units,
@@ -953,6 +998,9 @@ class ViewParallelGraphStep(TrainStepGraph):
     rasterizer (`fuse_activations`, the default)."""
 
     def __init__(self, model, optimizer, loss_computer, data, gt_img, mask=None, vp=None, **kw):
+        if kw.get("mcmc") is not None:
+            raise ValueError("ViewParallelGraphStep: no `mcmc` -- MCMCStrategy refuses torch.distributed (the replicas would need "
+                             "broadcast draws)")
         if vp is None or not vp.exchange or not vp.native or not vp.guard_words:
             raise ValueError("ViewParallelGraphStep needs a native ViewParallelStep(..., guard_words=True) with the exchange on")
         if not vp._raw_parameters():

@@ -721,6 +721,44 @@ int gs_mcmc_apply(void* stream, int64_t n, int64_t n_rows, int K, double min_opa
 int gs_mcmc_noise(void* stream, int64_t n, double strength, const float* log_scales, const float* quats,
                   const float* logit_opacities, const float* z, float* means);
 
+/* Counter-based noise, for the captured step (DESIGN.md "Training to a budget"): the normals of Gaussian n at optimizer step t
+ * under a 64-bit seed are a pure function of (seed, t, n) -- one Philox4x32-10 block with counter (n lo, n hi, t lo, t hi) and key
+ * (seed lo, seed hi), multipliers 0xD2511F53 / 0xCD9E8D57, key increments 0x9E3779B9 / 0xBB67AE85 -- so a step the guard skipped
+ * draws the same normals when it is replayed.  From the block's words x0..x3, in fp64: u_i = (x_i + 0.5) 2^-32,
+ * z0 = sqrt(-2 ln u0) cos(2 pi u1), z1 = sqrt(-2 ln u0) sin(2 pi u1), z2 = sqrt(-2 ln u2) cos(2 pi u3), each rounded to float32
+ * once: the z of gs_mcmc_noise.
+ * gs_mcmc_normals: z_out[n][3] = those normals (16-byte aligned).
+ * gs_mcmc_step_inputs: a one-thread launch that writes rec_dev[GS_MCMC_REC_WORDS] int64 (16-byte aligned) = {the bits of the
+ * double `strength`, step, seed, 0}; the values travel as kernel arguments, as gs_adam_hyper's.
+ * gs_mcmc_noise_step: gs_mcmc_noise with strength, step and seed read from rec_dev and the normals drawn in the kernel -- no z
+ * array; the same means, bit for bit, as gs_mcmc_normals + gs_mcmc_noise.  Honours the step guard. */
+#define GS_MCMC_REC_WORDS 4
+int gs_mcmc_normals(void* stream, int64_t n, int64_t step, uint64_t seed, float* z_out);
+int gs_mcmc_step_inputs(void* stream, double strength, int64_t step, uint64_t seed, int64_t* rec_dev);
+int gs_mcmc_noise_step(void* stream, int64_t n, const int64_t* rec_dev, const float* log_scales, const float* quats,
+                       const float* logit_opacities, float* means);
+
+/* Budget regulariser (mcmc.MCMCStrategy.regularization): reg = a mean_N sigmoid(logit_n) + b mean_3N exp(log_scale_nk) over ALL N
+ * Gaussians, o and s in fp64; d reg / d logit_n = fl32(a / N) o_n (1 - o_n) and d reg / d log_scale_nk = fl32(b / (3 N)) s_nk, each
+ * rounded to float32 once.
+ * gs_mcmc_reg: gs_scale_reg's contract -- reg_ws[gs_mcmc_reg_workspace_floats(N)] f32, 16-byte aligned, reg_ws[0] = reg, the rest
+ *   scratch; loss3 (optional): loss3[2] += reg; v_logit_opacities[N] / v_log_scales[N*3] (each optional): += the gradient.  The
+ *   sums run in a fixed order without float atomics (replays give the same bits).  Honours the step guard.  N = 0: no launch.
+ * gs_project_bwd_adam_mcmc: gs_project_bwd_adam with both gradients added for every in-range Gaussian in front of the update (read
+ *   from the parameters before it) -- behind the scale-ratio regulariser's when scale_reg = 1 (max_ratio, lambda as in
+ *   gs_project_bwd_adam_reg).  Same update, bit for bit, as gs_project_bwd, [gs_scale_reg,] gs_mcmc_reg into its gradients,
+ *   gs_adam_step_dev. */
+size_t gs_mcmc_reg_workspace_floats(int64_t N);
+int gs_mcmc_reg(void* stream, int64_t N, const float* logit_opacities, const float* log_scales, double a, double b, float* loss3,
+                float* reg_ws, float* v_logit_opacities, float* v_log_scales);
+int gs_project_bwd_adam_mcmc(void* stream, int64_t N, int K, int sh_degree, float* params, float* exp_avg, float* exp_avg_sq,
+                             const int64_t* offsets_host, const float* viewmats, const float* Ks, int width, int height, float eps2d,
+                             float near_plane, float far_plane, const int32_t* radii, const float* colors_post,
+                             const int32_t* tiles_per_gauss, const int32_t* cum_tiles, const float* rows, const int32_t* row_base,
+                             const uint8_t* qmask, float* v_means2d_abs, float beta1, float beta2, float eps, const float* hyper_dev,
+                             int64_t* applied_dev, float* max_radii, float* grad_norm_accum, float* counts, const float* sh_jac,
+                             int scale_reg, float max_ratio, float lambda, double a, double b);
+
 /* gs_project_bwd + gs_adam_step_dev in one pass, for the reference's own single-camera step with the model's raw
  * parameters (log-scales, logit opacities, split SH: activations as in gs_project_bwd(..., activations = 1)): no
  * gradient is written; each parameter element and its two moments are updated in place where its gradient is
