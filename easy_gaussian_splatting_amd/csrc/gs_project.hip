@@ -750,9 +750,9 @@ __global__ __launch_bounds__(kProjThreads) void project_bwd_kernel(const ProjBwd
 #include "gs_project_bwd_body.h"
 }
 // the fused form under a Gaussian budget (gs_project_bwd_adam_mcmc): REG = 2 the budget term alone, 3 behind the scale-ratio term
-template <int DEG, int REG>
+template <int DEG, int REG, bool SUMS = false>
 __global__ __launch_bounds__(kProjThreads) void project_bwd_budget_kernel(const ProjBwdArgs a) {
-    constexpr bool ADAM = true, SUMS = false;
+    constexpr bool ADAM = true;
 #include "gs_project_bwd_body.h"
 }
 
@@ -924,13 +924,16 @@ struct ProjCamArgs {
     const int32_t* radii;
     const float4* sh_jac;     // optional (gs_project_fwd): the coefficients are then not read
     const float *v_means2d, *v_conics, *v_colors_post;
+    const float4* row_sums;   // SUMS: gs_row_sums' [N][12] in their place (C = 1)
     double* cam_partials;     // [C][gridDim.x][16]
     const int64_t* guard;
 };
 
 constexpr int kCamTerms = 15;
 
-template <int DEG>
+// SUMS (gs_cam_grad_sums, the captured step with poses): the three gradients are elements of the Gaussian's row sums -- floats
+// 0-1, 4-6 and 8-10, as project_bwd_kernel hands them out -- and the gradient tensors do not exist.
+template <int DEG, bool SUMS = false>
 __global__ __launch_bounds__(kProjThreads) void project_cam_kernel(const ProjCamArgs a) {
     __shared__ float lds_cam[32];
     __shared__ double wave_sums[kProjThreads / 64][16];
@@ -951,7 +954,9 @@ __global__ __launch_bounds__(kProjThreads) void project_cam_kernel(const ProjCam
                                 act_scale(a.scales[3 * n + 2], a.activations)};
         if (DEG >= 1) {   // the SH colour's dependence on the camera centre: minus the direction term of v_mean
             const float rgb[3] = {a.colors_post[3 * f], a.colors_post[3 * f + 1], a.colors_post[3 * f + 2]};
-            const float v_rgb[3] = {a.v_colors_post[3 * f], a.v_colors_post[3 * f + 1], a.v_colors_post[3 * f + 2]};
+            float v_rgb[3];
+            if (SUMS) { const float4 z = a.row_sums[3 * f + 2]; v_rgb[0] = z.x; v_rgb[1] = z.y; v_rgb[2] = z.z; }
+            else { v_rgb[0] = a.v_colors_post[3 * f]; v_rgb[1] = a.v_colors_post[3 * f + 1]; v_rgb[2] = a.v_colors_post[3 * f + 2]; }
             float ux, uy, uz, term[3];
             const float dn = view_dir(mean, cam, ux, uy, uz);
             if (a.sh_jac) {   // (project_bwd_kernel's layout)
@@ -968,9 +973,16 @@ __global__ __launch_bounds__(kProjThreads) void project_cam_kernel(const ProjCam
         ProjChainT<preal> p;
         if (project_chain<preal>(mean, quat, scale, cam, a.eps2d, a.near_p, a.far_p, p)) {
             float v_mean[3] = {0.f, 0.f, 0.f}, v_quat[4] = {0.f, 0.f, 0.f, 0.f}, v_scale[3] = {0.f, 0.f, 0.f};   // (not used here)
-            const float2 vm = reinterpret_cast<const float2*>(a.v_means2d)[f];
-            project_vjp_cam<preal>(mean, scale, cam, p, vm.x, vm.y, a.v_conics[3 * f], a.v_conics[3 * f + 1], a.v_conics[3 * f + 2], 0.f,
-                                   v_mean, v_quat, v_scale, acc, acc + 9);
+            float2 vm;
+            float vc[3];
+            if (SUMS) {
+                const float4 x = a.row_sums[3 * f], y = a.row_sums[3 * f + 1];
+                vm = make_float2(x.x, x.y); vc[0] = y.x; vc[1] = y.y; vc[2] = y.z;
+            } else {
+                vm = reinterpret_cast<const float2*>(a.v_means2d)[f];
+                vc[0] = a.v_conics[3 * f]; vc[1] = a.v_conics[3 * f + 1]; vc[2] = a.v_conics[3 * f + 2];
+            }
+            project_vjp_cam<preal>(mean, scale, cam, p, vm.x, vm.y, vc[0], vc[1], vc[2], 0.f, v_mean, v_quat, v_scale, acc, acc + 9);
         }
     }
     const int lane = lane_id(), wave = threadIdx.x >> 6;
@@ -1272,7 +1284,7 @@ extern "C" int gs_project_bwd_cam(void* stream, int C, int64_t N, int K, int sh_
     const bool split = sh_degree >= 0 && sh_rest != nullptr;
     a.sh_from_1 = split ? sh_rest : colors_in + 3; a.sh_stride = split ? 3 * (int64_t)(K - 1) : 3 * (int64_t)K;
     a.radii = radii; a.sh_jac = sh_degree >= 1 ? reinterpret_cast<const float4*>(sh_jac) : nullptr;
-    a.v_means2d = v_means2d; a.v_conics = v_conics; a.v_colors_post = v_colors_post;
+    a.v_means2d = v_means2d; a.v_conics = v_conics; a.v_colors_post = v_colors_post; a.row_sums = nullptr;
     a.cam_partials = cam_partials; a.guard = current_guard().info;
     const int n_blocks = (int)((N + kProjThreads - 1) / kProjThreads);
     dim3 grid((unsigned)n_blocks, (unsigned)C);
@@ -1291,6 +1303,50 @@ extern "C" int gs_project_bwd_cam(void* stream, int C, int64_t N, int K, int sh_
     return GS_OK;
 }
 
+// The camera gradients of the single-camera step from gs_row_sums' per-Gaussian sums (the captured step with poses): the kernels and
+// the reduction of gs_project_bwd_cam, fed from the sums because the fused projection backward + Adam writes no gradient tensor.
+extern "C" int gs_cam_grad_sums(void* stream, int64_t N, int K, int sh_degree, const float* means, const float* quats, const float* scales,
+                                const float* sh_rest, const float* viewmats, const float* Ks, int width, int height, float eps2d,
+                                float near_plane, float far_plane, const int32_t* radii, const float* colors_post, int activations,
+                                const float* sh_jac, const float* row_sums, double* cam_partials, float* v_viewmats, float* v_campos) {
+    GS_REQUIRE(N >= 0 && width > 0 && height > 0, "N>=0, positive image size");
+    GS_REQUIRE(sh_degree <= 4 && (sh_degree < 0 || (K >= (sh_degree + 1) * (sh_degree + 1) && K <= 25)), "sh_degree <= 4, (degree+1)^2 <= K <= 25");
+    GS_REQUIRE(v_viewmats && v_campos && (N == 0 || cam_partials), "null camera-gradient pointer");
+    hipStream_t st = (hipStream_t)stream;
+    if (N == 0) {
+        GS_HIP_CHECK(hipMemsetAsync(v_viewmats, 0, sizeof(float) * 16, st));
+        GS_HIP_CHECK(hipMemsetAsync(v_campos, 0, sizeof(float) * 3, st));
+        return GS_OK;
+    }
+    GS_REQUIRE(means && quats && scales && viewmats && Ks && radii && colors_post && row_sums, "null input pointer");
+    GS_REQUIRE(sh_degree < 1 || sh_jac || sh_rest, "SH degree >= 1 needs sh_jac or the coefficients (sh_rest)");
+    GS_REQUIRE(((uintptr_t)quats & 15) == 0 && ((uintptr_t)row_sums & 15) == 0 && ((uintptr_t)cam_partials & 7) == 0,
+               "quats and row_sums 16-byte, cam_partials 8-byte aligned");
+    ProjCamArgs a;
+    a.K = K; a.W = width; a.H = height; a.activations = activations != 0; a.N = N;
+    a.eps2d = eps2d; a.near_p = near_plane; a.far_p = far_plane;
+    a.means = means; a.quats = quats; a.scales = scales; a.viewmats = viewmats; a.Ks = Ks; a.colors_post = colors_post;
+    a.sh_from_1 = sh_rest; a.sh_stride = 3 * (int64_t)(K - 1);   // (the split layout)
+    a.radii = radii; a.sh_jac = sh_degree >= 1 ? reinterpret_cast<const float4*>(sh_jac) : nullptr;
+    a.v_means2d = a.v_conics = a.v_colors_post = nullptr; a.row_sums = reinterpret_cast<const float4*>(row_sums);
+    a.cam_partials = cam_partials; a.guard = current_guard().info;
+    const int n_blocks = (int)((N + kProjThreads - 1) / kProjThreads);
+    dim3 grid((unsigned)n_blocks, 1u);
+#define GS_PC(D) hipLaunchKernelGGL((project_cam_kernel<D, true>), grid, dim3(kProjThreads), 0, st, a)
+    switch (sh_degree) {
+        case 1: GS_PC(1); break;
+        case 2: GS_PC(2); break;
+        case 3: GS_PC(3); break;
+        case 4: GS_PC(4); break;
+        default: GS_PC(0); break;
+    }
+#undef GS_PC
+    GS_LAUNCH_CHECK("project_cam_kernel (row sums)");
+    hipLaunchKernelGGL(cam_sum_kernel, dim3(1u), dim3(16 * kCamSumChains), 0, st, (const double*)cam_partials, n_blocks, v_viewmats, v_campos, a.guard);
+    GS_LAUNCH_CHECK("cam_sum_kernel");
+    return GS_OK;
+}
+
 // Row reduction + SH-bwd + P-bwd + Adam in ONE pass (train-step graph, single camera): gs_project_bwd with the
 // reference model's raw parameters (log-scales, logit opacities, split SH), but instead of writing the 59 gradients
 // per Gaussian and reading them back in gs_adam_step, every parameter and both of its moments are updated in place
@@ -1303,12 +1359,15 @@ static int project_bwd_adam(void* stream, int64_t N, int K, int sh_degree, float
                             const int32_t* tiles_per_gauss, const int32_t* cum_tiles, const float* rows, const int32_t* row_base, const uint8_t* qmask,
                             float* v_means2d_abs, float beta1, float beta2, float eps, const float* hyper_dev,
                             int64_t* applied_dev, float* max_radii, float* grad_norm_accum, float* counts,
-                            const float* sh_jac, int reg, float max_ratio, float lambda, double bud_a, double bud_b) {
+                            const float* sh_jac, int reg, float max_ratio, float lambda, double bud_a, double bud_b,
+                            const float* row_sums = nullptr) {
     GS_REQUIRE(N >= 0 && width > 0 && height > 0, "N>=0, positive image size");
     GS_REQUIRE(sh_degree >= 0 && sh_degree <= 4 && K >= (sh_degree + 1) * (sh_degree + 1) && K <= 25, "SH colours: 0 <= degree <= 4, (degree+1)^2 <= K <= 25");
     if (N == 0) return GS_OK;
     GS_REQUIRE(params && exp_avg && exp_avg_sq && offsets_host && viewmats && Ks && radii && colors_post && tiles_per_gauss &&
-               cum_tiles && rows && row_base && qmask && v_means2d_abs && hyper_dev, "null pointer");
+               cum_tiles && v_means2d_abs && hyper_dev, "null pointer");
+    GS_REQUIRE(row_sums ? ((uintptr_t)row_sums & 15) == 0 : (rows && row_base && qmask),
+               "the gradient rows (rows + row_base + qmask) or their sums (row_sums, 16-byte aligned, from gs_row_sums)");
     ProjBwdArgs a;
     a.C = 1; a.N = N; a.K = K; a.colors_per_camera = 0; a.W = width; a.H = height;
     a.eps2d = eps2d; a.near_p = near_plane; a.far_p = far_plane;
@@ -1328,7 +1387,7 @@ static int project_bwd_adam(void* stream, int64_t N, int K, int sh_degree, float
                "the three statistics buffers come together or not at all");
     a.st_max_radii = max_radii; a.st_grad_norm = grad_norm_accum; a.st_counts = counts;
     a.st_max_hw = (float)(width > height ? width : height);
-    a.row_sums = nullptr; a.st_gn_out = a.st_cnt_out = nullptr;
+    a.row_sums = row_sums; a.st_gn_out = a.st_cnt_out = nullptr;
     a.ad_pbase = params; a.ad_mbase = exp_avg; a.ad_vbase = exp_avg_sq;
     for (int t = 0; t < 6; ++t) a.ad_off[t] = offsets_host[t];
     a.cam = 0; a.accumulate = 0;
@@ -1337,11 +1396,14 @@ static int project_bwd_adam(void* stream, int64_t N, int K, int sh_degree, float
     dim3 grid((unsigned)((N + kProjThreads - 1) / kProjThreads));
     const size_t lds = proj_bwd_lds_bytes(K, sh_degree);
     hipStream_t st = (hipStream_t)stream;
-    // (no row_sums form of the fused kernel: its instantiation kept a dead 36-byte stack object, and a kernel that declares
-    //  scratch makes the runtime provision it -- gs_blend.hip, GS_FWD_TRAIN_WAVES_PER_EU)
+    // (the row_sums forms -- gs_project_bwd_adam_sums -- are instantiations of their own; the compiler's resource report shows
+    //  none of them with scratch: a kernel that declares it makes the runtime provision it -- gs_blend.hip, GS_FWD_TRAIN_WAVES_PER_EU)
 #define GS_PBK(...) { GS_LDS((__VA_ARGS__)); hipLaunchKernelGGL((__VA_ARGS__), grid, dim3(kProjThreads), lds, st, a); }
 #define GS_PB(D)                                                                                                        \
-    if (reg == 3) GS_PBK(project_bwd_budget_kernel<D, 3>) else if (reg == 2) GS_PBK(project_bwd_budget_kernel<D, 2>)    \
+    if (row_sums) {                                                                                                     \
+        if (reg == 3) GS_PBK(project_bwd_budget_kernel<D, 3, true>) else if (reg == 2) GS_PBK(project_bwd_budget_kernel<D, 2, true>)    \
+        else if (reg == 1) GS_PBK(project_bwd_kernel<D, true, true, true>) else GS_PBK(project_bwd_kernel<D, true, true>)               \
+    } else if (reg == 3) GS_PBK(project_bwd_budget_kernel<D, 3>) else if (reg == 2) GS_PBK(project_bwd_budget_kernel<D, 2>)             \
     else if (reg == 1) GS_PBK(project_bwd_kernel<D, true, false, true>) else GS_PBK(project_bwd_kernel<D, true, false>)
     switch (sh_degree) {
         case 0: GS_PB(0); break;
@@ -1398,4 +1460,24 @@ extern "C" int gs_project_bwd_adam_mcmc(void* stream, int64_t N, int K, int sh_d
                             near_plane, far_plane, radii, colors_post, tiles_per_gauss, cum_tiles, rows, row_base, qmask, v_means2d_abs,
                             beta1, beta2, eps, hyper_dev, applied_dev, max_radii, grad_norm_accum, counts, sh_jac, 2 | scale_reg,
                             max_ratio, lambda, a, b);
+}
+
+// ... from the row sums gs_row_sums left (the captured step with poses: the camera gradient is formed from the same sums in front of
+// this call, so the gradient rows are walked once per step), with any of the two regularisers: the same update, bit for bit, as the
+// row-walking entries above -- row_sums_kernel and project_bwd_kernel share row_sum_wave.
+extern "C" int gs_project_bwd_adam_sums(void* stream, int64_t N, int K, int sh_degree, float* params, float* exp_avg, float* exp_avg_sq,
+                                        const int64_t* offsets_host, const float* viewmats, const float* Ks, int width, int height,
+                                        float eps2d, float near_plane, float far_plane, const int32_t* radii, const float* colors_post,
+                                        const int32_t* tiles_per_gauss, const int32_t* cum_tiles, const float* row_sums,
+                                        float* v_means2d_abs, float beta1, float beta2, float eps, const float* hyper_dev,
+                                        int64_t* applied_dev, float* max_radii, float* grad_norm_accum, float* counts,
+                                        const float* sh_jac, int scale_reg, float max_ratio, float lambda, int budget, double a, double b) {
+    GS_REQUIRE(((uintptr_t)params & 3) == 0, "params must be 4-byte aligned");
+    GS_REQUIRE((scale_reg == 0 || scale_reg == 1) && (budget == 0 || budget == 1), "scale_reg and budget are 0 or 1");
+    GS_REQUIRE(a == a && b == b, "a or b is NaN");
+    GS_REQUIRE(N == 0 || row_sums, "row_sums: gs_row_sums' per-Gaussian sums");
+    return project_bwd_adam(stream, N, K, sh_degree, params, exp_avg, exp_avg_sq, offsets_host, viewmats, Ks, width, height, eps2d,
+                            near_plane, far_plane, radii, colors_post, tiles_per_gauss, cum_tiles, nullptr, nullptr, nullptr, v_means2d_abs,
+                            beta1, beta2, eps, hyper_dev, applied_dev, max_radii, grad_norm_accum, counts, sh_jac, (budget ? 2 : 0) | scale_reg,
+                            max_ratio, lambda, a, b, row_sums);
 }

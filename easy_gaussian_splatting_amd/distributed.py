@@ -114,10 +114,13 @@ class ViewParallelStep:
     SH = ("sh_0", "sh_rest")
     GEOMETRY = ("means", "log_scales", "quats", "logit_opacities")
 
-    def __init__(self, model, optimizer, group=None, sh_grad_fn=None, force_exchange: bool = False, guard_words: bool = False):
+    def __init__(self, model, optimizer, group=None, sh_grad_fn=None, force_exchange: bool = False, guard_words: bool = False, poses=None):
         """`guard_words`: the all-gather record and the all-reduce bucket each carry one more word (16 bytes with its pad) -- the
         rank's step-guard flag, for the captured form of the step (train_graph.ViewParallelGraphStep): a rank that skips a step on
         the device must take every replica with it."""
+        if poses is not None:
+            raise ValueError("ViewParallelStep: no `poses` -- the view-parallel step exchanges no camera gradient; refine poses on one "
+                             "GPU (TrainStepGraph(poses=...), or the eager loop with pose.CameraDeltas)")
         self.model, self.opt, self.group = model, optimizer, group
         self.guard_words = bool(guard_words)
         self.world = dist.get_world_size(group) if group_ready() else 1

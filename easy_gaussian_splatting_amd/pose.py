@@ -1,6 +1,8 @@
-"""Per-view camera corrections for pose refinement: plain torch, no kernel.  The gradient of the corrected view matrix comes
-from the rasterizer (`rasterization(_camera_grads=True)`, which `GaussianModel.forward` asks for whenever `data["w2c"]` requires
-grad); see INTEGRATION.md "Refining camera poses"."""
+"""Per-view camera corrections for pose refinement.  In the eager loop: plain torch, no kernel -- the gradient of the corrected view
+matrix comes from the rasterizer (`rasterization(_camera_grads=True)`, which `GaussianModel.forward` asks for whenever
+`data["w2c"]` requires grad).  In the captured step (`TrainStepGraph(..., poses=CameraDeltas(n))`): composed, differentiated and
+stepped on the device (csrc/gs_pose.h), with `PoseAdamState` holding the optimizer state.  See INTEGRATION.md "Refining camera
+poses"."""
 from __future__ import annotations
 
 import torch
@@ -30,3 +32,27 @@ class CameraDeltas(nn.Module):
         top = torch.cat([torch.linalg.matrix_exp(skew), tau[:, None]], dim=1)                 # [3,4]
         bottom = torch.tensor([[0.0, 0.0, 0.0, 1.0]], dtype=d.dtype, device=d.device)
         return torch.cat([top, bottom], dim=0) @ w2c.to(d.dtype)
+
+
+class PoseAdamState:
+    """Adam's state for a `CameraDeltas` stepped inside the captured train step (`TrainStepGraph(poses=...)` makes one:
+    `runner.pose_state`): the two moments [n_views, 6] on the deltas' device and the number of pose steps taken -- dense Adam, every
+    step counts for every row.  `state_dict()` / `load_state_dict()` let a checkpoint carry it next to `poses.state_dict()`."""
+
+    def __init__(self, poses: CameraDeltas):
+        d = poses.deltas
+        self.exp_avg = torch.zeros(tuple(d.shape), dtype=torch.float32, device=d.device)
+        self.exp_avg_sq = torch.zeros(tuple(d.shape), dtype=torch.float32, device=d.device)
+        self.step = 0
+
+    def state_dict(self):
+        return {"exp_avg": self.exp_avg.clone(), "exp_avg_sq": self.exp_avg_sq.clone(), "step": int(self.step)}
+
+    def load_state_dict(self, state) -> None:
+        """In place: the captured step keeps reading the same buffers."""
+        for name in ("exp_avg", "exp_avg_sq"):
+            src, dst = state[name], getattr(self, name)
+            if tuple(src.shape) != tuple(dst.shape):
+                raise ValueError(f"PoseAdamState.load_state_dict: {name} of shape {tuple(src.shape)}, expected {tuple(dst.shape)}")
+            dst.copy_(src)
+        self.step = int(state["step"])

@@ -34,6 +34,11 @@ Training to a Gaussian budget (`mcmc=MCMCStrategy(..., noise="counter")`): the b
 gradients (gs_mcmc_reg / gs_project_bwd_adam_mcmc), and the noise runs behind Adam inside the guarded sequence with draws that are a
 pure function of (seed, step, Gaussian) (gs_mcmc_noise_step) -- a skipped step that is replayed draws what it would have drawn.
 Relocate / grow stay between the steps: `strategy.after_step(step, runner)`.
+
+Refining camera poses (`poses=pose.CameraDeltas(n_views)`, `step(..., view_index=i)`): the corrected view matrix is composed on the
+device in front of the projection (gs_pose_compose), the camera gradient is formed from the step's gradient rows beside the fused
+kernel (gs_row_sums + gs_cam_grad_sums; gs_project_bwd_cam without fuse_adam), and one launch chains it to the view's 6-vector and
+applies dense Adam to all corrections under the step guard (gs_pose_adam).  DESIGN.md "Poses in the captured step".
 """
 from __future__ import annotations
 
@@ -76,16 +81,33 @@ def _p(t: Optional[Tensor]):
 
 def _refuse_camera_grads(data) -> None:
     if data is not None and isinstance(data.get("w2c"), Tensor) and data["w2c"].requires_grad:
-        raise ValueError("TrainStepGraph: data['w2c'] requires grad, but the captured step has no camera gradient (its fused-Adam "
-                         "projection backward writes none): detach it, or refine poses in the eager loop (model(data) with "
+        raise ValueError("TrainStepGraph: data['w2c'] requires grad, but the captured step hands no camera gradient to autograd: "
+                         "detach it and refine poses INSIDE the step -- TrainStepGraph(..., poses=pose.CameraDeltas(n_views)) with "
+                         "step(..., view_index=i) and the uncorrected data['w2c'] -- or in the eager loop (model(data) with "
                          "pose.CameraDeltas)")
+
+
+def _pose_view(poses, view_index) -> Optional[int]:
+    """The view a step refines, validated before anything reaches the device: required with `poses`, refused without."""
+    if poses is None:
+        if view_index is not None:
+            raise ValueError("TrainStepGraph.step: view_index given, but the runner was built without `poses`")
+        return None
+    if view_index is None:
+        raise ValueError("TrainStepGraph.step: the runner refines poses (poses=CameraDeltas): every step needs view_index=i, the row of "
+                         "`poses.deltas` that corrects data['w2c']")
+    i, n = int(view_index), int(poses.deltas.shape[0])
+    if not 0 <= i < n:
+        raise ValueError(f"TrainStepGraph.step: view_index {i} outside the {n} views of `poses`")
+    return i
 
 
 class TrainStepGraph:
     def __init__(self, model, optimizer: FusedAdam, loss_computer, data: Dict[str, Any], gt_img: Tensor,
                  mask: Optional[Tensor] = None, margin: float = 1.3, use_graph: bool = True, check_every: int = 16,
                  fuse_adam: bool = True, handback: str = "eager", copy_targets: bool = False, rounds: str = "auto",
-                 round_fraction: float = 0.125, mcmc=None, mcmc_reg: Tuple[float, float] = (0.01, 0.01)):
+                 round_fraction: float = 0.125, mcmc=None, mcmc_reg: Tuple[float, float] = (0.01, 0.01), poses=None,
+                 pose_lr: float = 1e-3, pose_betas: Tuple[float, float] = (0.9, 0.999), pose_eps: float = 1e-15):
         """`mcmc`: an `mcmc.MCMCStrategy(model, ..., noise="counter")` -- the step then trains under its Gaussian budget: `mcmc_reg` =
         (opacity_reg, scale_reg) of `strategy.regularization()` enters the loss (out["mcmc_reg"]) and the update, and the strategy's
         noise runs behind Adam inside the step, at noise_lr x the means learning rate of that step.  None (default): nothing changes.
@@ -97,8 +119,34 @@ class TrainStepGraph:
         entry (below) costs nothing; with the eager form that wait sits behind the previous step's hand-back on the caller's
         stream -- two cross-queue signal hops, 24 us of idle GPU per step in the kernel trace of the bench loop.  Parameters
         and statistics are NOT intercepted: a lazy caller that reads them between steps calls `fence()` first.
-        Cameras are constants here: a `data["w2c"]` that requires grad raises `ValueError` (here and in `step`) -- the captured
-        step's fused-Adam projection backward has no camera output; refine poses in the eager loop."""
+        `poses`: a `pose.CameraDeltas(n_views)` on the runner's device -- the step then refines the cameras: `data["w2c"]` is the
+        UNCORRECTED matrix, `step(..., view_index=i)` names the row of `poses.deltas` that corrects it (the build's own view:
+        `data.get("view_index", 0)`), the step renders with the corrected matrix (out["viewmat"]), and behind the model's update one
+        launch chains the camera gradient to that row (out["v_delta"]) and applies Adam(pose_lr, pose_betas, pose_eps) to ALL rows in
+        place in `poses.deltas.data` -- `torch.optim.Adam(poses.parameters())`'s dense update: idle rows decay their moments and
+        move -- under the step guard.  The moments and the pose step count: `runner.pose_state` (`pose.PoseAdamState`, with
+        `state_dict` / `load_state_dict`).  `poses.deltas` must keep its storage while the runner lives.  None (default): nothing
+        changes, launch for launch.
+        `data["w2c"]` itself never requires grad here: one that does raises `ValueError` (here and in `step`) -- the captured step
+        hands nothing to autograd (INTEGRATION.md "Refining camera poses")."""
+        if poses is not None:
+            from .pose import CameraDeltas, PoseAdamState
+            if not isinstance(poses, CameraDeltas):
+                raise TypeError("TrainStepGraph(poses=...): a pose.CameraDeltas")
+            d = poses.deltas
+            if d.device != model.means.device or d.dtype != torch.float32 or not d.is_contiguous() or d.dim() != 2 or d.shape[1] != 6:
+                raise ValueError("TrainStepGraph(poses=...): `poses.deltas` must be a contiguous float32 [n_views, 6] on the model's device")
+            if not 1 <= d.shape[0] <= nat.GS_POSE_MAX_VIEWS:
+                raise ValueError("TrainStepGraph(poses=...): 1 .. GS_POSE_MAX_VIEWS views")
+            self.pose_lr, self.pose_betas, self.pose_eps = float(pose_lr), (float(pose_betas[0]), float(pose_betas[1])), float(pose_eps)
+            self.pose_state = PoseAdamState(poses)
+            # runner-owned, outside the workspace layout, alive across re-builds: the record (its first 16 floats: the raw view matrix,
+            # the step's static camera input), the camera gradient and the 6-vector's
+            f32d = dict(dtype=torch.float32, device=d.device)
+            self._pose_bufs = {"pose_rec": torch.zeros((nat.GS_POSE_REC_FLOATS,), **f32d), "v_viewmats": torch.zeros((1, 4, 4), **f32d),
+                               "v_campos": torch.zeros((1, 3), **f32d), "v_delta": torch.zeros((6,), **f32d)}
+            self._pose_cur = (_pose_view(poses, data.get("view_index", 0)), self.pose_state.step + 1)
+        self.poses = poses
         self.mcmc = mcmc
         if mcmc is not None:
             if getattr(mcmc, "noise", None) != "counter":
@@ -235,6 +283,17 @@ class TrainStepGraph:
             "sh_rest": torch.empty((N, self.K - 1, 3), **f32) if self.K > 1 else None,
             "logit_opacities": torch.empty((N,), **f32)}
         b["hyper"] = torch.zeros((16,), **f32)
+        if self.poses is not None:
+            b.update(self._pose_bufs)
+            b["w2c_raw"] = b["pose_rec"][:16].view(1, 4, 4)
+            b["cam_partials"] = self._take("cam_partials", (int(L.gs_cam_partials_doubles(1, N)),), torch.float64)
+            if self.fuse_adam:   # the camera kernel reads the row sums: the fused kernel writes no gradient tensor
+                b["pose_row_sums"] = self._take("pose_row_sums", (N, 12), torch.float32)
+                b["pose_v_pre"] = self._take("pose_v_pre", (N, 3), torch.float32)
+            else:                # gs_project_bwd_cam's three gradient tensors
+                b["v_means2d"] = self._take("pose_v_means2d", (1, N, 2), torch.float32)
+                b["v_conics"] = self._take("pose_v_conics", (1, N, 3), torch.float32)
+                b["v_colors_post"] = self._take("pose_v_colors_post", (1, N, 3), torch.float32)
         # {reg, -, fp64 block partials}: the regulariser's value and its reduction scratch (gs_scale_reg)
         b["scale_reg"] = self._take("scale_reg", (int(L.gs_scale_reg_workspace_floats(N)),), torch.float32) if self.scale_reg else None
         if self.mcmc is not None:
@@ -433,19 +492,24 @@ class TrainStepGraph:
             t = t.to(device=self.dev, dtype=torch.float32).contiguous()
         return t
 
-    def _stage_inputs(self, t: int, lrs, w2c: Tensor, K: Tensor, gt: Tensor, mask: Optional[Tensor]):
+    def _static_w2c(self) -> Tensor:
+        """The step's static camera INPUT [1,4,4]: the view matrix the projection reads, or (poses) the raw matrix in the pose record."""
+        return self.buf["w2c_raw"] if self.poses is not None else self.buf["viewmats"]
+
+    def _stage_inputs(self, t: int, lrs, w2c: Tensor, K: Tensor, gt: Tensor, mask: Optional[Tensor], pose=None):
         """Everything that differs from the previous step, in ONE launch on the current stream (gs_step_inputs): Adam's bias
         corrections / learning rates, the camera into the static buffers, and the POINTERS to the target image and mask.
         Returns the (gt, mask) tensors whose pointers went in -- the caller keeps them alive until the step is applied."""
         L, b, opt = nat.lib(), self.buf, self.opt
         ok = lambda x, n: x.device == self.dev and x.dtype == torch.float32 and x.is_contiguous() and x.numel() == n   # noqa: E731
         vm_src = k_src = None
-        if w2c.data_ptr() != b["viewmats"].data_ptr():   # (the static buffer itself = "same as last step")
-            self._protect_pending(b["viewmats"])
+        static_vm = self._static_w2c()
+        if w2c.data_ptr() != static_vm.data_ptr():   # (the static buffer itself = "same as last step")
+            self._protect_pending(static_vm)
             if ok(w2c, 16):
                 vm_src = w2c
             else:
-                b["viewmats"][0].copy_(w2c, non_blocking=True)
+                static_vm[0].copy_(w2c, non_blocking=True)
         if K.data_ptr() != b["Ks"].data_ptr():
             self._protect_pending(b["Ks"])
             if ok(K, 9):
@@ -461,8 +525,13 @@ class TrainStepGraph:
             mask = None
         ns = len(opt._plist)
         b1, b2 = opt.defaults["betas"]
-        nat.check(L.gs_step_inputs(self._st(), ns, (ct.c_float * ns)(*lrs), float(b1), float(b2), int(t), _p(b["hyper"]), _p(vm_src),
-                                   _p(b["viewmats"]), _p(k_src), _p(b["Ks"]), _p(gt), _p(mask), _p(b["img_slots"])), "gs_step_inputs")
+        nat.check(L.gs_step_inputs(self._st(), ns, (ct.c_float * ns)(*lrs), float(b1), float(b2), int(t), _p(b["hyper"]),
+                                   None if self.poses is not None else _p(vm_src), _p(b["viewmats"]), _p(k_src), _p(b["Ks"]), _p(gt), _p(mask),
+                                   _p(b["img_slots"])), "gs_step_inputs")
+        if self.poses is not None:   # the view, its raw matrix into the record, the pose Adam's bias corrections at ITS step count
+            view, pose_t = pose if pose is not None else self._pose_cur
+            nat.check(L.gs_pose_step_inputs(self._st(), int(view), int(self.poses.deltas.shape[0]), _p(vm_src), None, self.pose_lr,
+                                            self.pose_betas[0], self.pose_betas[1], int(pose_t), _p(b["pose_rec"])), "gs_pose_step_inputs")
         if self.mcmc is not None:   # the step's noise: its strength at the means learning rate this step's Adam uses, its counter, the seed
             nat.check(L.gs_mcmc_step_inputs(self._st(), self.mcmc.noise_lr * float(lrs[self._means_seg]), int(t), self.mcmc.seed,
                                             _p(b["mcmc_rec"])), "gs_mcmc_step_inputs")
@@ -547,6 +616,9 @@ class TrainStepGraph:
         # (the runner hands out no list arrays: "gsplat" -- exact arrays, built when read -- renders from the short lists
         #  like "tight"; "gsplat_eager" walks gsplat's own lists)
         culling = {"gsplat": 1, "tight": 1, "gsplat_eager": 0}[getattr(m, "tile_culling", "tight")]
+        if self.poses is not None:   # the corrected view matrix of the record's view, from the deltas as they stand
+            self._ck(L.gs_pose_compose(self._st(), int(self.poses.deltas.shape[0]), _p(b["pose_rec"]), _p(self.poses.deltas.data),
+                                       _p(b["viewmats"])), "gs_pose_compose")
         self._ck(L.gs_project_fwd(self._st(), 1, self.N, self.K, int(m.active_sh_degree), _p(m.means), _p(m.quats), _p(m.log_scales),
                                    _p(m.logit_opacities), _p(m.sh_0), _p(m.sh_rest) if self.K > 1 else None, 0,
                                    _p(b["viewmats"]), _p(b["Ks"]), self.W, self.H, EPS2D, NEAR_PLANE, FAR_PLANE, RADIUS_CLIP, culling, 0, 1,
@@ -660,15 +732,33 @@ class TrainStepGraph:
         L, b, m, opt = nat.lib(), self.buf, self.model, self.opt
         N, W, H = self.N, self.W, self.H
         b1, b2 = opt.defaults["betas"]
+        poses = self.poses is not None
         if self.fuse_adam:
+            if poses:
+                # The gradient rows are walked ONCE, by gs_row_sums; the camera gradient is formed from the per-Gaussian sums BEFORE the
+                # fused kernel moves the parameters (gs_project_bwd_cam's kernels on the sums), and the fused kernel consumes the same
+                # sums (gs_project_bwd_adam_sums: the same update bit for bit).  DESIGN.md "Poses in the captured step".
+                self._ck(L.gs_row_sums(st, 1, N, _p(b["radii"]), _p(b["colors_post"]), self._tpg(), _p(b["cum_tiles"]), _p(b["rows"]),
+                                        _p(b["row_base"]), _p(b["qmask"]), _p(b["pose_row_sums"]), _p(b["pose_v_pre"]), None, float(max(H, W)),
+                                        None, None), "gs_row_sums")
+                self._ck(L.gs_cam_grad_sums(st, N, self.K, int(m.active_sh_degree), _p(m.means), _p(m.quats), _p(m.log_scales),
+                                             _p(m.sh_rest) if self.K > 1 else None, _p(b["viewmats"]), _p(b["Ks"]), W, H, EPS2D, NEAR_PLANE,
+                                             FAR_PLANE, _p(b["radii"]), _p(b["colors_post"]), 1, _p(b["sh_jac"]), _p(b["pose_row_sums"]),
+                                             _p(b["cam_partials"]), _p(b["v_viewmats"]), _p(b["v_campos"])), "gs_cam_grad_sums")
             offs = (ct.c_int64 * 6)(*opt._offs)
-            args = (st, N, self.K, int(m.active_sh_degree), _p(opt.flat_param), _p(opt.exp_avg),
+            head = (st, N, self.K, int(m.active_sh_degree), _p(opt.flat_param), _p(opt.exp_avg),
                     _p(opt.exp_avg_sq), offs, _p(b["viewmats"]), _p(b["Ks"]), W, H, EPS2D, NEAR_PLANE, FAR_PLANE,
-                    _p(b["radii"]), _p(b["colors_post"]), self._tpg(), _p(b["cum_tiles"]),
-                    _p(b["rows"]), _p(b["row_base"]), _p(b["qmask"]), _p(b["v_abs"]), float(b1), float(b2),
+                    _p(b["radii"]), _p(b["colors_post"]), self._tpg(), _p(b["cum_tiles"]))
+            tail = (_p(b["v_abs"]), float(b1), float(b2),
                     float(opt.defaults["eps"]), _p(b["hyper"]), _p(b["applied"]), _p(m.max_radii),
                     _p(m.grad_norm_accum), _p(m.collecting_counts), _p(b["sh_jac"]))
-            if self.mcmc is not None:
+            args = head + (_p(b["rows"]), _p(b["row_base"]), _p(b["qmask"])) + tail
+            if poses:   # (the sums in place of rows, row_base, qmask; one entry for the three variants)
+                self._ck(L.gs_project_bwd_adam_sums(*head, _p(b["pose_row_sums"]), *tail, int(self.scale_reg),
+                                                     self.max_scale_ratio if self.scale_reg else 0.0, self.lambda_scale if self.scale_reg else 0.0,
+                                                     int(self.mcmc is not None), *(self.mcmc_reg if self.mcmc is not None else (0.0, 0.0))),
+                         "gs_project_bwd_adam_sums")
+            elif self.mcmc is not None:
                 self._ck(L.gs_project_bwd_adam_mcmc(*args, int(self.scale_reg), self.max_scale_ratio if self.scale_reg else 0.0,
                                                      self.lambda_scale if self.scale_reg else 0.0, *self.mcmc_reg), "gs_project_bwd_adam_mcmc")
             elif self.scale_reg:
@@ -677,12 +767,18 @@ class TrainStepGraph:
                 self._ck(L.gs_project_bwd_adam(*args), "gs_project_bwd_adam")
         else:
             g = self.grads
-            self._ck(L.gs_project_bwd(st, 1, N, self.K, int(m.active_sh_degree), _p(m.means), _p(m.quats), _p(m.log_scales),
-                                      _p(m.sh_0), _p(m.sh_rest) if self.K > 1 else None, 0, _p(b["viewmats"]), _p(b["Ks"]), W, H,
-                                      EPS2D, NEAR_PLANE, FAR_PLANE, _p(b["radii"]), _p(b["colors_post"]), self._tpg(),
-                                      _p(b["cum_tiles"]), _p(b["rows"]), _p(b["row_base"]), _p(b["qmask"]), _p(g["means"]), _p(g["quats"]),
-                                      _p(g["log_scales"]), _p(g["logit_opacities"]), _p(g["sh_0"]), _p(g["sh_rest"]), _p(b["v_abs"]),
-                                      None, None, None, None, _p(m.logit_opacities), 1, _p(b["sh_jac"]), None, None, None), "gs_project_bwd")
+            bwd_args = (st, 1, N, self.K, int(m.active_sh_degree), _p(m.means), _p(m.quats), _p(m.log_scales),
+                        _p(m.sh_0), _p(m.sh_rest) if self.K > 1 else None, 0, _p(b["viewmats"]), _p(b["Ks"]), W, H,
+                        EPS2D, NEAR_PLANE, FAR_PLANE, _p(b["radii"]), _p(b["colors_post"]), self._tpg(),
+                        _p(b["cum_tiles"]), _p(b["rows"]), _p(b["row_base"]), _p(b["qmask"]), _p(g["means"]), _p(g["quats"]),
+                        _p(g["log_scales"]), _p(g["logit_opacities"]), _p(g["sh_0"]), _p(g["sh_rest"]), _p(b["v_abs"]))
+            if poses:   # the same gradients, and the camera's from the three tensors it hands out
+                self._ck(L.gs_project_bwd_cam(*bwd_args, _p(b["v_means2d"]), _p(b["v_conics"]), _p(b["v_colors_post"]), None,
+                                               _p(m.logit_opacities), 1, _p(b["sh_jac"]), None, None, None, _p(b["cam_partials"]),
+                                               _p(b["v_viewmats"]), _p(b["v_campos"])), "gs_project_bwd_cam")
+            else:
+                self._ck(L.gs_project_bwd(*bwd_args, None, None, None, None, _p(m.logit_opacities), 1, _p(b["sh_jac"]), None, None, None),
+                         "gs_project_bwd")
             if self.scale_reg:   # value into the loss total, gradient onto the render's
                 self._scale_reg(g["log_scales"])
             if self.mcmc is not None:
@@ -699,6 +795,11 @@ class TrainStepGraph:
         if self.mcmc is not None:   # the noise, on the updated parameters; a skipped step adds none
             self._ck(L.gs_mcmc_noise_step(st, N, _p(b["mcmc_rec"]), _p(m.log_scales), _p(m.quats), _p(m.logit_opacities), _p(m.means)),
                      "gs_mcmc_noise_step")
+        if poses:   # the chain to the view's 6-vector and Adam over all corrections; a skipped step moves none
+            ps = self.pose_state
+            self._ck(L.gs_pose_adam(st, int(self.poses.deltas.shape[0]), _p(b["pose_rec"]), _p(self.poses.deltas.data), _p(ps.exp_avg),
+                                    _p(ps.exp_avg_sq), _p(b["v_viewmats"]), _p(b["v_campos"]), _p(b["v_delta"]), self.pose_betas[0],
+                                    self.pose_betas[1], self.pose_eps), "gs_pose_adam")
         self._ck(L.gs_step_status(st, _p(b["info"]), _p(b["applied"]), self.status.data_ptr(), _p(b["loss3"]), _p(b["loss_ring"]),
                                   self.LOSS_RING, _p(b["walk_state"])), "gs_step_status")
 
@@ -738,6 +839,8 @@ class TrainStepGraph:
             if warm_up:
                 self._warm.add((self.binning, self.cap_tile))
                 saved = [opt.flat_param.clone(), opt.exp_avg.clone(), opt.exp_avg_sq.clone()] + [getattr(m, n).clone() for n in names]
+                pose_live = (self.poses.deltas.data, self.pose_state.exp_avg, self.pose_state.exp_avg_sq) if self.poses is not None else ()
+                pose_saved = [x.clone() for x in pose_live]
                 self._hyper(max(opt._step, 0) + 1, [float(grp["lr"]) for grp, _ in opt._plist])
                 self._enqueue_step()
                 self.stream.synchronize()
@@ -746,6 +849,8 @@ class TrainStepGraph:
                     opt.flat_param.copy_(saved[0]); opt.exp_avg.copy_(saved[1]); opt.exp_avg_sq.copy_(saved[2])
                     for n, s in zip(names, saved[3:]):
                         getattr(m, n).copy_(s)
+                    for x, s in zip(pose_live, pose_saved):
+                        x.copy_(s)
                 self.buf["applied"].zero_()
                 if info[nat.GS_INFO_FLAGS] != 0:   # the capacities learnt from the probe do not hold (cannot happen unless inputs changed in between)
                     self.buf["info"].zero_()
@@ -767,6 +872,7 @@ class TrainStepGraph:
         t, lrs, w2c, K, gt, mask, ready = entry[:7]
         conv = entry[7] if len(entry) > 7 else None
         after = entry[8] if len(entry) > 8 else None
+        pose = entry[10] if len(entry) > 10 else None   # (view index, pose step count): poses
         # The step waits for the caller's stream on entry: that orders it behind pending WRITERS of the inputs handed in and
         # behind pending READERS of what the replay overwrites -- the static outputs the previous `step()` returned, the
         # parameters and moments (fused Adam), the statistics.  (Round 3 skipped the wait for steps that take no input from
@@ -784,7 +890,7 @@ class TrainStepGraph:
                 for ev in (after if isinstance(after, (list, tuple)) else (after,)):
                     self.stream.wait_event(ev)
                 entry[8] = None
-            entry[4], entry[5] = self._stage_inputs(t, lrs, w2c, K, gt, mask)   # (the tensors the step reads: kept by the entry)
+            entry[4], entry[5] = self._stage_inputs(t, lrs, w2c, K, gt, mask, pose)   # (the tensors the step reads: kept by the entry)
             if self.graph is not None:
                 self.graph.replay()
             else:
@@ -794,7 +900,8 @@ class TrainStepGraph:
         self.issued += 1
 
     def step(self, data: Optional[Dict[str, Any]] = None, gt_img: Optional[Tensor] = None, mask: Optional[Tensor] = None,
-             inputs_ready: bool = False, ready_event: Optional["torch.cuda.Event"] = None, host_src=None):
+             inputs_ready: bool = False, ready_event: Optional["torch.cuda.Event"] = None, host_src=None,
+             view_index: Optional[int] = None):
         """One training iteration.  `data` / `gt_img` / `mask` default to the previous step's (the camera's static buffers are
         re-used as they are; the target image and the mask are the previous step's own tensors, read in place).  Returns the
         runner's static output tensors (valid until the next `step()` is CALLED: reads
@@ -809,8 +916,11 @@ class TrainStepGraph:
         `ready_event`: an event the step's stream waits for before it reads anything (the upload of the inputs on a copy stream:
         `HostFeed`).  `host_src = {"w2c", "K", "image"[, "mask"]}` host tensors the device inputs were uploaded from: a feeder that
         recycles its device slots hands them in, and an overflow recovery replays the step from a FRESH upload of those instead
-        of from slots that have been refilled since.  A `data["w2c"]` that requires grad raises `ValueError` (see `__init__`)."""
+        of from slots that have been refilled since.  A `data["w2c"]` that requires grad raises `ValueError` (see `__init__`).
+        `view_index`: with `poses`, required -- the row of `poses.deltas` that corrects this step's `data["w2c"]` (data=None: the
+        previous step's raw matrix)."""
         _refuse_camera_grads(data)
+        view = _pose_view(self.poses, view_index)
         W, H = (self.W, self.H) if data is None else (int(data["width"]), int(data["height"]))
         if self._state_key(W, H) != self._key:
             self.finish()
@@ -863,7 +973,7 @@ class TrainStepGraph:
             else:
                 self._build({"w2c": cur[0], "K": cur[1]}, cur[2], cur[3] if self.has_mask else None, projected=projected)
         b = self.buf
-        w2c = b["viewmats"][0] if data is None else data["w2c"]
+        w2c = self._static_w2c()[0] if data is None else data["w2c"]
         K = b["Ks"][0] if data is None else data["K"]
         gt = self._last_inputs[2] if gt_img is None else gt_img   # (the previous step's own tensors, by reference)
         mk = (self._last_inputs[3] if mask is None else mask) if self.has_mask else None
@@ -890,7 +1000,12 @@ class TrainStepGraph:
         # target and the mask are not even copied: the step reads them where they lie (`_stage_inputs`).  Entries that alias the
         # runner's OWN static camera buffers (data=None steps) are snapshotted right before a later step overwrites those
         # buffers (`_protect_pending`), so a skipped step is always replayed with its own inputs.
-        self._issue([opt._step, [float(grp["lr"]) for grp, _ in opt._plist], w2c, K, gt, mk, bool(inputs_ready), conv, ready_event, host_src])
+        entry = [opt._step, [float(grp["lr"]) for grp, _ in opt._plist], w2c, K, gt, mk, bool(inputs_ready), conv, ready_event, host_src]
+        if view is not None:   # the view and the pose step count travel with the step, like t and the learning rates: a replay re-stages them
+            self.pose_state.step += 1
+            self._pose_cur = (view, self.pose_state.step)
+            entry.append(self._pose_cur)
+        self._issue(entry)
         if self.issued % self.check_every == 0:
             self._poll(block=False)
         outs = {"render_img": b["render_colors"][0], "loss3": b["loss3"], "batch_radii": b["radii"], "absgrad": b["v_abs"]}
@@ -898,6 +1013,9 @@ class TrainStepGraph:
             outs["scale_reg"] = b["scale_reg"][0]   # (0-d, the eager loss dict's "scale_reg")
         if self.mcmc is not None:
             outs["mcmc_reg"] = b["mcmc_reg"][0]   # (0-d, `strategy.regularization(*mcmc_reg)`)
+        if self.poses is not None:
+            outs["viewmat"] = b["viewmats"][0]    # the corrected matrix the step rendered with
+            outs["v_delta"] = b["v_delta"]        # dL / d poses.deltas[view_index] of the step (unchanged by a step the guard skipped)
         return TrainStepGraph._StepOutputs(self, outs, lazy=self.handback == "lazy")
 
     def _poll(self, block: bool):
@@ -945,6 +1063,8 @@ class TrainStepGraph:
                 e[4] = HostFeed.to_target(src["image"], self.dev)
                 e[5] = src["mask"].to(self.dev, torch.float32) if (self.has_mask and src.get("mask") is not None) else e[5]
         first = redo[0]
+        if self.poses is not None:
+            self._pose_cur = first[10]   # (the probe of the re-build runs on the first skipped step's own view)
         # (min_cap >= 1 forces a fresh probe even when only a coarse-bin capacity was exceeded and the list sizes read 0)
         self._build({"w2c": first[2], "K": first[3]}, first[4], first[5], min_cap=max(n_isects, 1), min_cap_tile=max_tile, min_walk=walk)
         for e in redo:
@@ -970,6 +1090,8 @@ class TrainStepGraph:
         extra = dict(scale_reg=True, max_scale_ratio=self.max_scale_ratio, lambda_scale=self.lambda_scale) if self.scale_reg else {}
         if self.mcmc is not None:
             extra.update(mcmc=True, mcmc_reg=self.mcmc_reg, mcmc_seed=self.mcmc.seed, mcmc_noise_lr=self.mcmc.noise_lr)
+        if self.poses is not None:   # (like the two above: a runner without the feature reports what it always reported)
+            extra.update(poses=True, pose_lr=self.pose_lr, pose_steps=self.pose_state.step)
         return dict(self.stats, **extra, binning=self.binning, probed_isects=self.probed[0], probed_longest_list=self.probed[1],
                     probed_coarse_entries=getattr(self, "probed_coarse", (0, 0))[0] if self.binning == "bins" else 0,
                     capacity_isects=self.cap, capacity_tile_list=self.cap_tile, capacity_work_units=self.cap_units,
@@ -998,6 +1120,9 @@ class ViewParallelGraphStep(TrainStepGraph):
     rasterizer (`fuse_activations`, the default)."""
 
     def __init__(self, model, optimizer, loss_computer, data, gt_img, mask=None, vp=None, **kw):
+        if kw.get("poses") is not None:
+            raise ValueError("ViewParallelGraphStep: no `poses` -- pose refinement inside the captured step is single-GPU "
+                             "(TrainStepGraph(poses=...)): the view-parallel step has no camera gradient")
         if kw.get("mcmc") is not None:
             raise ValueError("ViewParallelGraphStep: no `mcmc` -- MCMCStrategy refuses torch.distributed (the replicas would need "
                              "broadcast draws)")
@@ -1085,7 +1210,7 @@ class HostFeed:
     step waits for exactly that upload (an event), not for the caller's stream:
 
         feed = HostFeed(runner)                      # runner: TrainStepGraph
-        for batch in loader:                         # batch: {"w2c", "K", "width", "height", "image"[, "mask"]} pinned host tensors
+        for batch in loader:                         # batch: {"w2c", "K", "width", "height", "image"[, "mask"][, "view_index"]} pinned host tensors
             feed.step(batch)
 
     A slot is refilled once the step that read it last has run -- the copy stream waits for that (an event on the runner's
@@ -1152,8 +1277,9 @@ class HostFeed:
                 self.mask[j].copy_(batch["mask"], non_blocking=True)
             ev = torch.cuda.Event()
             ev.record(cs)
+        view = batch.get("view_index") if getattr(r, "poses", None) is not None else None   # (poses: the batch names its row of the deltas)
         out = r.step({"w2c": self.w2c[j], "K": self.K[j], "width": r.W, "height": r.H}, self.gt[j], self.mask[j] if r.has_mask else None,
-                     inputs_ready=self.inputs_ready, ready_event=ev, host_src=batch)
+                     inputs_ready=self.inputs_ready, ready_event=ev, host_src=batch, view_index=view)
         self.done[j] = torch.cuda.Event()
         self.done[j].record(r.stream)
         return out

@@ -841,6 +841,51 @@ size_t gs_knn_workspace_bytes(int64_t N);
 int gs_knn_codes(void* stream, int64_t N, const float* points, void* workspace, int64_t* codes);
 int gs_knn_dists(void* stream, int64_t N, int k, const float* points, const int32_t* order, float* dists, void* workspace);
 
+/* ---- Pose refinement in the captured step (DESIGN.md "Poses in the captured step"): pose.CameraDeltas' per-view correction
+ * delta = {omega[3], tau[3]}, viewmat = [[exp([omega]x), tau], [0, 1]] @ w2c, composed, differentiated and stepped on the device.
+ * The math is csrc/gs_pose.h: closed-form Rodrigues in fp64 with series below theta = 0.1, every entry rounded to fp32 once;
+ * delta == 0 gives w2c bit for bit.
+ * gs_pose_step_inputs: a one-thread launch in front of a step (as gs_mcmc_step_inputs: the values travel as kernel arguments) that
+ *   writes rec_dev[GS_POSE_REC_FLOATS] f32, 16-byte aligned = {raw w2c[16], lr / (1 - beta1^step), 1 / sqrt(1 - beta2^step), the
+ *   bits of the int32 view index, 0}.  The raw matrix: w2c_dev (device, 16 floats, read by the launch) or w2c_host (16 values, copied
+ *   at the call) or neither -- the record keeps the one it holds.  0 <= view < n_views <= GS_POSE_MAX_VIEWS, step >= 1.
+ * gs_pose_compose: viewmat_out[16] = the corrected matrix of the record's view from deltas[n_views][6]; in front of gs_project_fwd.
+ * gs_cam_grad_sums: the camera gradients of gs_project_bwd_cam for C = 1 -- v_viewmats[16] (rows 0-2 = [v_A | v_t], row 3 = 0) and
+ *   v_campos[3], the same kernels, the same fp64 fixed-order reduction through cam_partials[gs_cam_partials_doubles(1, N)] -- formed
+ *   from the per-Gaussian row sums gs_row_sums leaves (row_sums[N][12]: floats 0-1 = v_means2d, 4-6 = v_conics, 8-10 = v_colors_post)
+ *   in place of the gradient tensors, which a step that applies Adam inside its projection backward never writes.  Reads the
+ *   parameters (activations as in gs_project_bwd; sh_rest: the split layout's coefficients 1.., needed with sh_degree >= 1 when
+ *   sh_jac is NULL), so it runs BEFORE gs_project_bwd_adam* updates them.  Honours the step guard.
+ * gs_project_bwd_adam_sums: gs_project_bwd_adam / _reg / _mcmc (scale_reg, budget: 0 or 1, with their parameters) fed from the same
+ *   row_sums in place of rows / row_base / qmask -- the gradient rows are then walked once per step, by gs_row_sums.  The same
+ *   update, bit for bit, as the row-walking entries.
+ * gs_pose_adam: one launch behind it.  v_delta[6] = the chain from {v_viewmats, v_campos} to the view's 6-vector in fp64 (the
+ *   camera centre's term through the general 3x3 inverse, the product with w2c, the left Jacobian of SO(3)), rounded to fp32 once
+ *   and left readable; then Adam (gs_adam_step's arithmetic per element) over ALL n_views x 6 corrections with the gradient v_delta
+ *   on the view's row and exactly 0 on every other row -- what torch.optim.Adam over the whole tensor does: idle rows decay their
+ *   moments and move.  Honours the step guard: a voided step leaves deltas, moments and v_delta as they were. */
+#define GS_POSE_REC_FLOATS 20
+#define GS_POSE_REC_SS 16
+#define GS_POSE_REC_ISBC2 17
+#define GS_POSE_REC_VIEW 18
+#define GS_POSE_MAX_VIEWS 1048576
+int gs_pose_step_inputs(void* stream, int view, int n_views, const float* w2c_dev, const float* w2c_host, float lr, float beta1,
+                        float beta2, int64_t step, float* rec_dev);
+int gs_pose_compose(void* stream, int n_views, const float* rec_dev, const float* deltas, float* viewmat_out);
+int gs_cam_grad_sums(void* stream, int64_t N, int K, int sh_degree, const float* means, const float* quats, const float* scales,
+                     const float* sh_rest, const float* viewmats, const float* Ks, int width, int height, float eps2d,
+                     float near_plane, float far_plane, const int32_t* radii, const float* colors_post, int activations,
+                     const float* sh_jac, const float* row_sums, double* cam_partials, float* v_viewmats, float* v_campos);
+int gs_project_bwd_adam_sums(void* stream, int64_t N, int K, int sh_degree, float* params, float* exp_avg, float* exp_avg_sq,
+                             const int64_t* offsets_host, const float* viewmats, const float* Ks, int width, int height, float eps2d,
+                             float near_plane, float far_plane, const int32_t* radii, const float* colors_post,
+                             const int32_t* tiles_per_gauss, const int32_t* cum_tiles, const float* row_sums, float* v_means2d_abs,
+                             float beta1, float beta2, float eps, const float* hyper_dev, int64_t* applied_dev, float* max_radii,
+                             float* grad_norm_accum, float* counts, const float* sh_jac, int scale_reg, float max_ratio, float lambda,
+                             int budget, double a, double b);
+int gs_pose_adam(void* stream, int n_views, const float* rec_dev, float* deltas, float* exp_avg, float* exp_avg_sq,
+                 const float* v_viewmats, const float* v_campos, float* v_delta, float beta1, float beta2, float eps);
+
 #ifdef __cplusplus
 }
 #endif
