@@ -10,6 +10,7 @@ Public surface (mirrors the reference's names for this path):
   evaluate.Evaluator        -- the reference's held-out evaluation (eval.py): PSNR / SSIM from one fused kernel per view
   viewer.FrameRenderer      -- the viewer's render_func (launch_viewer.py) and the camera-path video export, finished on the device
   mcmc.MCMCStrategy         -- training to a Gaussian budget: MCMC relocate / grow / noise on the flat Adam buffers
+  exposure.ExposureTable    -- per-view exposure compensation: a learnable 3x4 colour affine per training image
 """
 from .evaluate import Evaluator, evaluate_output, image_metrics  # noqa: F401
 from .mcmc import MCMCStrategy, counter_normals, opacity_weights, relocation_values, sample_by_weight, weight_cdf  # noqa: F401

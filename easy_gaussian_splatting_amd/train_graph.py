@@ -39,6 +39,11 @@ Refining camera poses (`poses=pose.CameraDeltas(n_views)`, `step(..., view_index
 device in front of the projection (gs_pose_compose), the camera gradient is formed from the step's gradient rows beside the fused
 kernel (gs_row_sums + gs_cam_grad_sums; gs_project_bwd_cam without fuse_adam), and one launch chains it to the view's 6-vector and
 applies dense Adam to all corrections under the step guard (gs_pose_adam).  DESIGN.md "Poses in the captured step".
+
+Compensating per-view exposure (`exposure=exposure.ExposureTable(n_views)`, `step(..., view_index=i)`): the view's 3x4 colour affine is
+applied to the render in front of the loss (gs_exposure_apply), the loss gradient is taken back to the raw render in place while the
+12 sums of the view's row are formed (gs_exposure_bwd), and one launch applies dense Adam to the whole table under the step guard
+(gs_exposure_adam).  DESIGN.md "Exposure in the captured step".
 """
 from __future__ import annotations
 
@@ -87,18 +92,23 @@ def _refuse_camera_grads(data) -> None:
                          "pose.CameraDeltas)")
 
 
-def _pose_view(poses, view_index) -> Optional[int]:
-    """The view a step refines, validated before anything reaches the device: required with `poses`, refused without."""
-    if poses is None:
+def _pose_view(poses, view_index, exposure=None) -> Optional[int]:
+    """The view a step refines, validated before anything reaches the device: required with `poses` or `exposure` (one index for
+    both), refused without."""
+    if poses is None and exposure is None:
         if view_index is not None:
-            raise ValueError("TrainStepGraph.step: view_index given, but the runner was built without `poses`")
+            raise ValueError("TrainStepGraph.step: view_index given, but the runner was built without `poses` and without `exposure`")
         return None
     if view_index is None:
+        if poses is None:
+            raise ValueError("TrainStepGraph.step: the runner compensates exposure (exposure=ExposureTable): every step needs view_index=i, "
+                             "the row of `exposure.affine` that belongs to the step's target image")
         raise ValueError("TrainStepGraph.step: the runner refines poses (poses=CameraDeltas): every step needs view_index=i, the row of "
                          "`poses.deltas` that corrects data['w2c']")
-    i, n = int(view_index), int(poses.deltas.shape[0])
-    if not 0 <= i < n:
-        raise ValueError(f"TrainStepGraph.step: view_index {i} outside the {n} views of `poses`")
+    i = int(view_index)
+    for what, table in (("poses", None if poses is None else poses.deltas), ("exposure", None if exposure is None else exposure.affine)):
+        if table is not None and not 0 <= i < int(table.shape[0]):
+            raise ValueError(f"TrainStepGraph.step: view_index {i} outside the {int(table.shape[0])} views of `{what}`")
     return i
 
 
@@ -107,7 +117,8 @@ class TrainStepGraph:
                  mask: Optional[Tensor] = None, margin: float = 1.3, use_graph: bool = True, check_every: int = 16,
                  fuse_adam: bool = True, handback: str = "eager", copy_targets: bool = False, rounds: str = "auto",
                  round_fraction: float = 0.125, mcmc=None, mcmc_reg: Tuple[float, float] = (0.01, 0.01), poses=None,
-                 pose_lr: float = 1e-3, pose_betas: Tuple[float, float] = (0.9, 0.999), pose_eps: float = 1e-15):
+                 pose_lr: float = 1e-3, pose_betas: Tuple[float, float] = (0.9, 0.999), pose_eps: float = 1e-15, exposure=None,
+                 exposure_lr: float = 1e-2, exposure_betas: Tuple[float, float] = (0.9, 0.999), exposure_eps: float = 1e-15):
         """`mcmc`: an `mcmc.MCMCStrategy(model, ..., noise="counter")` -- the step then trains under its Gaussian budget: `mcmc_reg` =
         (opacity_reg, scale_reg) of `strategy.regularization()` enters the loss (out["mcmc_reg"]) and the update, and the strategy's
         noise runs behind Adam inside the step, at noise_lr x the means learning rate of that step.  None (default): nothing changes.
@@ -128,7 +139,32 @@ class TrainStepGraph:
         `state_dict` / `load_state_dict`).  `poses.deltas` must keep its storage while the runner lives.  None (default): nothing
         changes, launch for launch.
         `data["w2c"]` itself never requires grad here: one that does raises `ValueError` (here and in `step`) -- the captured step
-        hands nothing to autograd (INTEGRATION.md "Refining camera poses")."""
+        hands nothing to autograd (INTEGRATION.md "Refining camera poses").
+        `exposure`: an `exposure.ExposureTable(n_views)` on the runner's device -- the step then compensates per-view exposure:
+        `step(..., view_index=i)` names the row of `exposure.affine` (the same index `poses` uses when both are given), the loss reads
+        the affine of that row applied to the un-clamped render (out["exposed"]), the gradient of the raw render is A^T times the loss
+        gradient, and beside the pose update one launch applies Adam(exposure_lr, exposure_betas, exposure_eps) to ALL rows in place in
+        `exposure.affine.data` -- the 12 sums of the step (out["v_affine"]) on the view's row, zeros on the others -- under the step
+        guard.  `runner.exposure_lr` is a plain attribute, staged every step outside the graph: a schedule is an assignment between
+        steps.  The moments and the step count: `runner.exposure_state` (`exposure.ExposureAdamState`).  `exposure.affine` must keep
+        its storage while the runner lives.  None (default): nothing changes, launch for launch."""
+        if exposure is not None:
+            from .exposure import ExposureAdamState, ExposureTable
+            if not isinstance(exposure, ExposureTable):
+                raise TypeError("TrainStepGraph(exposure=...): an exposure.ExposureTable")
+            a = exposure.affine
+            if a.device != model.means.device or a.dtype != torch.float32 or not a.is_contiguous() or tuple(a.shape[1:]) != (3, 4):
+                raise ValueError("TrainStepGraph(exposure=...): `exposure.affine` must be a contiguous float32 [n_views, 3, 4] on the model's device")
+            if not 1 <= a.shape[0] <= nat.GS_EXPOSURE_MAX_VIEWS:
+                raise ValueError("TrainStepGraph(exposure=...): 1 .. GS_EXPOSURE_MAX_VIEWS views")
+            self.exposure_lr, self.exposure_eps = float(exposure_lr), float(exposure_eps)
+            self.exposure_betas = (float(exposure_betas[0]), float(exposure_betas[1]))
+            self.exposure_state = ExposureAdamState(exposure)
+            # runner-owned, outside the workspace layout, alive across re-builds: the record and the 12 sums (the image and the
+            # partials are sized by the frame: `_build`)
+            self._exposure_bufs = {"exposure_rec": torch.zeros((nat.GS_EXPOSURE_REC_FLOATS,), dtype=torch.float32, device=a.device),
+                                   "v_affine": torch.zeros((12,), dtype=torch.float32, device=a.device)}
+        self.exposure = exposure
         if poses is not None:
             from .pose import CameraDeltas, PoseAdamState
             if not isinstance(poses, CameraDeltas):
@@ -147,6 +183,8 @@ class TrainStepGraph:
                                "v_campos": torch.zeros((1, 3), **f32d), "v_delta": torch.zeros((6,), **f32d)}
             self._pose_cur = (_pose_view(poses, data.get("view_index", 0)), self.pose_state.step + 1)
         self.poses = poses
+        if exposure is not None:   # (view, exposure step count, learning rate) of the step about to be staged: the build's own
+            self._exposure_cur = (_pose_view(poses, data.get("view_index", 0), exposure), self.exposure_state.step + 1, self.exposure_lr)
         self.mcmc = mcmc
         if mcmc is not None:
             if getattr(mcmc, "noise", None) != "counter":
@@ -294,6 +332,12 @@ class TrainStepGraph:
                 b["v_means2d"] = self._take("pose_v_means2d", (1, N, 2), torch.float32)
                 b["v_conics"] = self._take("pose_v_conics", (1, N, 3), torch.float32)
                 b["v_colors_post"] = self._take("pose_v_colors_post", (1, N, 3), torch.float32)
+        if self.exposure is not None:
+            eb = self._exposure_bufs
+            if "exposed" not in eb or tuple(eb["exposed"].shape) != (H, W, 3):   # (the first build, or another frame size)
+                eb["exposed"] = torch.empty((H, W, 3), **f32)
+                eb["exposure_partials"] = torch.empty((int(L.gs_exposure_partials_doubles(H, W)),), dtype=torch.float64, device=dev)
+            b.update(eb)
         # {reg, -, fp64 block partials}: the regulariser's value and its reduction scratch (gs_scale_reg)
         b["scale_reg"] = self._take("scale_reg", (int(L.gs_scale_reg_workspace_floats(N)),), torch.float32) if self.scale_reg else None
         if self.mcmc is not None:
@@ -496,7 +540,7 @@ class TrainStepGraph:
         """The step's static camera INPUT [1,4,4]: the view matrix the projection reads, or (poses) the raw matrix in the pose record."""
         return self.buf["w2c_raw"] if self.poses is not None else self.buf["viewmats"]
 
-    def _stage_inputs(self, t: int, lrs, w2c: Tensor, K: Tensor, gt: Tensor, mask: Optional[Tensor], pose=None):
+    def _stage_inputs(self, t: int, lrs, w2c: Tensor, K: Tensor, gt: Tensor, mask: Optional[Tensor], pose=None, exposure=None):
         """Everything that differs from the previous step, in ONE launch on the current stream (gs_step_inputs): Adam's bias
         corrections / learning rates, the camera into the static buffers, and the POINTERS to the target image and mask.
         Returns the (gt, mask) tensors whose pointers went in -- the caller keeps them alive until the step is applied."""
@@ -532,6 +576,10 @@ class TrainStepGraph:
             view, pose_t = pose if pose is not None else self._pose_cur
             nat.check(L.gs_pose_step_inputs(self._st(), int(view), int(self.poses.deltas.shape[0]), _p(vm_src), None, self.pose_lr,
                                             self.pose_betas[0], self.pose_betas[1], int(pose_t), _p(b["pose_rec"])), "gs_pose_step_inputs")
+        if self.exposure is not None:   # the view and the exposure Adam's bias corrections at ITS step count and the step's own rate
+            view, exp_t, exp_lr = exposure if exposure is not None else self._exposure_cur
+            nat.check(L.gs_exposure_step_inputs(self._st(), int(view), int(self.exposure.affine.shape[0]), float(exp_lr), self.exposure_betas[0],
+                                                self.exposure_betas[1], int(exp_t), _p(b["exposure_rec"])), "gs_exposure_step_inputs")
         if self.mcmc is not None:   # the step's noise: its strength at the means learning rate this step's Adam uses, its counter, the seed
             nat.check(L.gs_mcmc_step_inputs(self._st(), self.mcmc.noise_lr * float(lrs[self._means_seg]), int(t), self.mcmc.seed,
                                             _p(b["mcmc_rec"])), "gs_mcmc_step_inputs")
@@ -714,10 +762,17 @@ class TrainStepGraph:
         def enqueue():
             self._enqueue_forward()
             lam = float(self.lc.lambda_ssim)
-            self._ck(L.gs_l1_ssim_fwd_slots(st, H, W, lam, _p(b["render_colors"]), _p(b["img_slots"]), int(self.has_mask), 1, _p(b["loss_ws"]),
+            img = b["render_colors"]
+            if self.exposure is not None:   # the loss reads the view's affine of the render; the blend backward keeps the raw render
+                n_exp, tab, img = int(self.exposure.affine.shape[0]), _p(self.exposure.affine.data), b["exposed"]
+                self._ck(L.gs_exposure_apply(st, H, W, n_exp, _p(b["exposure_rec"]), 0, tab, _p(b["render_colors"]), _p(img)), "gs_exposure_apply")
+            self._ck(L.gs_l1_ssim_fwd_slots(st, H, W, lam, _p(img), _p(b["img_slots"]), int(self.has_mask), 1, _p(b["loss_ws"]),
                                              _p(b["loss3"])), "gs_l1_ssim_fwd_slots")
-            self._ck(L.gs_l1_ssim_bwd_slots(st, H, W, lam, _p(b["render_colors"]), _p(b["img_slots"]), 1, _p(b["loss_ws"]),
+            self._ck(L.gs_l1_ssim_bwd_slots(st, H, W, lam, _p(img), _p(b["img_slots"]), 1, _p(b["loss_ws"]),
                                              _p(b["one"]), _p(b["v_render"])), "gs_l1_ssim_bwd_slots")
+            if self.exposure is not None:   # v_render: dL/d exposed -> dL/d render in place; the 12 sums of the view's row
+                self._ck(L.gs_exposure_bwd(st, H, W, n_exp, _p(b["exposure_rec"]), 0, tab, _p(b["render_colors"]), _p(b["v_render"]),
+                                           _p(b["exposure_partials"]), _p(b["v_affine"])), "gs_exposure_bwd")
             if self.scale_reg and self.fuse_adam:   # the value, from the parameters before the in-place update; the gradient: `_enqueue_rest`
                 self._scale_reg(None)
             if self.mcmc is not None and self.fuse_adam:   # likewise the budget regulariser's, behind it in the total
@@ -800,6 +855,11 @@ class TrainStepGraph:
             self._ck(L.gs_pose_adam(st, int(self.poses.deltas.shape[0]), _p(b["pose_rec"]), _p(self.poses.deltas.data), _p(ps.exp_avg),
                                     _p(ps.exp_avg_sq), _p(b["v_viewmats"]), _p(b["v_campos"]), _p(b["v_delta"]), self.pose_betas[0],
                                     self.pose_betas[1], self.pose_eps), "gs_pose_adam")
+        if self.exposure is not None:   # Adam over the whole table, the step's sums on the view's row; a skipped step moves none
+            es = self.exposure_state
+            self._ck(L.gs_exposure_adam(st, int(self.exposure.affine.shape[0]), _p(b["exposure_rec"]), _p(self.exposure.affine.data),
+                                        _p(es.exp_avg), _p(es.exp_avg_sq), _p(b["v_affine"]), self.exposure_betas[0], self.exposure_betas[1],
+                                        self.exposure_eps), "gs_exposure_adam")
         self._ck(L.gs_step_status(st, _p(b["info"]), _p(b["applied"]), self.status.data_ptr(), _p(b["loss3"]), _p(b["loss_ring"]),
                                   self.LOSS_RING, _p(b["walk_state"])), "gs_step_status")
 
@@ -840,6 +900,8 @@ class TrainStepGraph:
                 self._warm.add((self.binning, self.cap_tile))
                 saved = [opt.flat_param.clone(), opt.exp_avg.clone(), opt.exp_avg_sq.clone()] + [getattr(m, n).clone() for n in names]
                 pose_live = (self.poses.deltas.data, self.pose_state.exp_avg, self.pose_state.exp_avg_sq) if self.poses is not None else ()
+                if self.exposure is not None:   # (the table and its moments are throw-away state of the warm-up step like the deltas)
+                    pose_live += (self.exposure.affine.data, self.exposure_state.exp_avg, self.exposure_state.exp_avg_sq)
                 pose_saved = [x.clone() for x in pose_live]
                 self._hyper(max(opt._step, 0) + 1, [float(grp["lr"]) for grp, _ in opt._plist])
                 self._enqueue_step()
@@ -873,6 +935,7 @@ class TrainStepGraph:
         conv = entry[7] if len(entry) > 7 else None
         after = entry[8] if len(entry) > 8 else None
         pose = entry[10] if len(entry) > 10 else None   # (view index, pose step count): poses
+        expo = entry[11] if len(entry) > 11 else None   # (view index, exposure step count, learning rate): exposure
         # The step waits for the caller's stream on entry: that orders it behind pending WRITERS of the inputs handed in and
         # behind pending READERS of what the replay overwrites -- the static outputs the previous `step()` returned, the
         # parameters and moments (fused Adam), the statistics.  (Round 3 skipped the wait for steps that take no input from
@@ -890,7 +953,7 @@ class TrainStepGraph:
                 for ev in (after if isinstance(after, (list, tuple)) else (after,)):
                     self.stream.wait_event(ev)
                 entry[8] = None
-            entry[4], entry[5] = self._stage_inputs(t, lrs, w2c, K, gt, mask, pose)   # (the tensors the step reads: kept by the entry)
+            entry[4], entry[5] = self._stage_inputs(t, lrs, w2c, K, gt, mask, pose, expo)   # (the tensors the step reads: kept by the entry)
             if self.graph is not None:
                 self.graph.replay()
             else:
@@ -918,9 +981,10 @@ class TrainStepGraph:
         recycles its device slots hands them in, and an overflow recovery replays the step from a FRESH upload of those instead
         of from slots that have been refilled since.  A `data["w2c"]` that requires grad raises `ValueError` (see `__init__`).
         `view_index`: with `poses`, required -- the row of `poses.deltas` that corrects this step's `data["w2c"]` (data=None: the
-        previous step's raw matrix)."""
+        previous step's raw matrix); with `exposure`, required -- the row of `exposure.affine` of this step's target image."""
         _refuse_camera_grads(data)
-        view = _pose_view(self.poses, view_index)
+        exposure = getattr(self, "exposure", None)
+        view = _pose_view(self.poses, view_index, exposure)
         W, H = (self.W, self.H) if data is None else (int(data["width"]), int(data["height"]))
         if self._state_key(W, H) != self._key:
             self.finish()
@@ -1002,9 +1066,14 @@ class TrainStepGraph:
         # buffers (`_protect_pending`), so a skipped step is always replayed with its own inputs.
         entry = [opt._step, [float(grp["lr"]) for grp, _ in opt._plist], w2c, K, gt, mk, bool(inputs_ready), conv, ready_event, host_src]
         if view is not None:   # the view and the pose step count travel with the step, like t and the learning rates: a replay re-stages them
-            self.pose_state.step += 1
-            self._pose_cur = (view, self.pose_state.step)
-            entry.append(self._pose_cur)
+            if self.poses is not None:
+                self.pose_state.step += 1
+                self._pose_cur = (view, self.pose_state.step)
+            entry.append(self._pose_cur if self.poses is not None else None)
+            if exposure is not None:   # ... and so do the exposure step count and the rate as it stands at this call
+                self.exposure_state.step += 1
+                self._exposure_cur = (view, self.exposure_state.step, float(self.exposure_lr))
+                entry.append(self._exposure_cur)
         self._issue(entry)
         if self.issued % self.check_every == 0:
             self._poll(block=False)
@@ -1016,6 +1085,9 @@ class TrainStepGraph:
         if self.poses is not None:
             outs["viewmat"] = b["viewmats"][0]    # the corrected matrix the step rendered with
             outs["v_delta"] = b["v_delta"]        # dL / d poses.deltas[view_index] of the step (unchanged by a step the guard skipped)
+        if exposure is not None:
+            outs["exposed"] = b["exposed"]        # the image the loss read: the view's affine of render_img
+            outs["v_affine"] = b["v_affine"]      # dL / d exposure.affine[view_index], 12 floats row-major [3][4]
         return TrainStepGraph._StepOutputs(self, outs, lazy=self.handback == "lazy")
 
     def _poll(self, block: bool):
@@ -1065,6 +1137,8 @@ class TrainStepGraph:
         first = redo[0]
         if self.poses is not None:
             self._pose_cur = first[10]   # (the probe of the re-build runs on the first skipped step's own view)
+        if self.exposure is not None:
+            self._exposure_cur = first[11]
         # (min_cap >= 1 forces a fresh probe even when only a coarse-bin capacity was exceeded and the list sizes read 0)
         self._build({"w2c": first[2], "K": first[3]}, first[4], first[5], min_cap=max(n_isects, 1), min_cap_tile=max_tile, min_walk=walk)
         for e in redo:
@@ -1092,6 +1166,8 @@ class TrainStepGraph:
             extra.update(mcmc=True, mcmc_reg=self.mcmc_reg, mcmc_seed=self.mcmc.seed, mcmc_noise_lr=self.mcmc.noise_lr)
         if self.poses is not None:   # (like the two above: a runner without the feature reports what it always reported)
             extra.update(poses=True, pose_lr=self.pose_lr, pose_steps=self.pose_state.step)
+        if self.exposure is not None:
+            extra.update(exposure=True, exposure_lr=self.exposure_lr, exposure_steps=self.exposure_state.step)
         return dict(self.stats, **extra, binning=self.binning, probed_isects=self.probed[0], probed_longest_list=self.probed[1],
                     probed_coarse_entries=getattr(self, "probed_coarse", (0, 0))[0] if self.binning == "bins" else 0,
                     capacity_isects=self.cap, capacity_tile_list=self.cap_tile, capacity_work_units=self.cap_units,
@@ -1123,6 +1199,9 @@ class ViewParallelGraphStep(TrainStepGraph):
         if kw.get("poses") is not None:
             raise ValueError("ViewParallelGraphStep: no `poses` -- pose refinement inside the captured step is single-GPU "
                              "(TrainStepGraph(poses=...)): the view-parallel step has no camera gradient")
+        if kw.get("exposure") is not None:
+            raise ValueError("ViewParallelGraphStep: no `exposure` -- exposure compensation inside the captured step is single-GPU "
+                             "(TrainStepGraph(exposure=...)): the view-parallel step's loss reads each rank's raw render")
         if kw.get("mcmc") is not None:
             raise ValueError("ViewParallelGraphStep: no `mcmc` -- MCMCStrategy refuses torch.distributed (the replicas would need "
                              "broadcast draws)")
@@ -1277,7 +1356,8 @@ class HostFeed:
                 self.mask[j].copy_(batch["mask"], non_blocking=True)
             ev = torch.cuda.Event()
             ev.record(cs)
-        view = batch.get("view_index") if getattr(r, "poses", None) is not None else None   # (poses: the batch names its row of the deltas)
+        per_view = getattr(r, "poses", None) is not None or getattr(r, "exposure", None) is not None
+        view = batch.get("view_index") if per_view else None   # (poses / exposure: the batch names its row of the tables)
         out = r.step({"w2c": self.w2c[j], "K": self.K[j], "width": r.W, "height": r.H}, self.gt[j], self.mask[j] if r.has_mask else None,
                      inputs_ready=self.inputs_ready, ready_event=ev, host_src=batch, view_index=view)
         self.done[j] = torch.cuda.Event()

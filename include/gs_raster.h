@@ -886,6 +886,41 @@ int gs_project_bwd_adam_sums(void* stream, int64_t N, int K, int sh_degree, floa
 int gs_pose_adam(void* stream, int n_views, const float* rec_dev, float* deltas, float* exp_avg, float* exp_avg_sq,
                  const float* v_viewmats, const float* v_campos, float* v_delta, float beta1, float beta2, float eps);
 
+/* ---- Per-view exposure compensation (DESIGN.md "Exposure in the captured step"): exposure.ExposureTable's learnable 3x4 colour
+ * affine per training image, table[n_views][3][4] row-major = [A | b], applied to the UN-clamped render in front of the loss:
+ * out[p] = A render[p] + b.  The math is csrc/gs_exposure.h (shared with the host tests), in fp32 with one fixed order of fused
+ * multiply-adds per channel i:
+ *     out_i = fma(A_i2, c_2, fma(A_i1, c_1, fma(A_i0, c_0, b_i)))
+ * -- three roundings; at [I | 0] the input comes back exactly (a -0 as +0).  Images are [height][width][3] f32, 16-byte aligned.
+ * gs_exposure_step_inputs: a one-thread launch in front of a step (as gs_pose_step_inputs: the values travel as kernel arguments)
+ *   that writes rec_dev[GS_EXPOSURE_REC_FLOATS] f32, 16-byte aligned = {lr / (1 - beta1^step), 1 / sqrt(1 - beta2^step), the bits
+ *   of the int32 view index, 0}.  0 <= view < n_views <= GS_EXPOSURE_MAX_VIEWS and step >= 1: anything else is GS_ERR_ARG before
+ *   any launch.
+ * gs_exposure_apply: out = the affine of a view applied to render.  The view: the record's when rec_dev is non-NULL (the captured
+ *   step), else `view` (eager).  out may not alias render.
+ * gs_exposure_bwd: v_image holds dL/d out on entry and dL/d render = A^T v on exit, in place, per channel j
+ *     fma(A_2j, v_2, fma(A_1j, v_1, A_0j * v_0));
+ *   v_affine12[3][4] row-major = {dA_ij = sum_p v_i[p] render_j[p], db_i = sum_p v_i[p]} of the gradient as it came in.  Every
+ *   product is formed exactly in fp64 from its fp32 factors; the sums are fp64 in a fixed order -- per thread over its grid-stride
+ *   pixels, over the wave, over the block's waves, then one pass over the per-block partials[gs_exposure_partials_doubles(height,
+ *   width)] -- and rounded to fp32 once.  No atomics: two runs give the same bits.
+ * gs_exposure_adam: Adam (gs_adam_step's arithmetic per element) over ALL n_views x 12 entries with the gradient v_affine12 on the
+ *   record's row and exactly 0 on every other row -- torch.optim.Adam over the whole table: idle rows decay their moments and move.
+ *   Honours the step guard: a voided step leaves the table and the moments untouched. */
+#define GS_EXPOSURE_REC_FLOATS 4
+#define GS_EXPOSURE_REC_SS 0
+#define GS_EXPOSURE_REC_ISBC2 1
+#define GS_EXPOSURE_REC_VIEW 2
+#define GS_EXPOSURE_MAX_VIEWS 1048576
+int gs_exposure_step_inputs(void* stream, int view, int n_views, float lr, float beta1, float beta2, int64_t step, float* rec_dev);
+int gs_exposure_apply(void* stream, int height, int width, int n_views, const float* rec_dev, int view, const float* table,
+                      const float* render, float* out);
+size_t gs_exposure_partials_doubles(int height, int width);
+int gs_exposure_bwd(void* stream, int height, int width, int n_views, const float* rec_dev, int view, const float* table,
+                    const float* render, float* v_image, double* partials, float* v_affine12);
+int gs_exposure_adam(void* stream, int n_views, const float* rec_dev, float* table, float* exp_avg, float* exp_avg_sq,
+                     const float* v_affine12, float beta1, float beta2, float eps);
+
 #ifdef __cplusplus
 }
 #endif
