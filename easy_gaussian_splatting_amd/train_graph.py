@@ -44,6 +44,12 @@ Compensating per-view exposure (`exposure=exposure.ExposureTable(n_views)`, `ste
 applied to the render in front of the loss (gs_exposure_apply), the loss gradient is taken back to the raw render in place while the
 12 sums of the view's row are formed (gs_exposure_bwd), and one launch applies dense Adam to the whole table under the step guard
 (gs_exposure_adam).  DESIGN.md "Exposure in the captured step".
+
+Correcting per-view appearance (`bilagrid=bilagrid.BilateralGrids(n_views)`, `step(..., view_index=i)`): the view's bilateral grid of
+colour affines is sliced and applied to the render in front of the loss (gs_bilagrid_apply), the loss gradient is taken back to the
+raw render in place -- through the luminance guide too -- while the slice's adjoint fills the view's slab (gs_bilagrid_bwd), the
+total variation of all grids enters the loss and the gradient (gs_bilagrid_tv), and one launch applies dense Adam to every grid
+under the step guard (gs_bilagrid_adam).  DESIGN.md "Bilateral grids in the captured step".
 """
 from __future__ import annotations
 
@@ -92,21 +98,25 @@ def _refuse_camera_grads(data) -> None:
                          "pose.CameraDeltas)")
 
 
-def _pose_view(poses, view_index, exposure=None) -> Optional[int]:
-    """The view a step refines, validated before anything reaches the device: required with `poses` or `exposure` (one index for
-    both), refused without."""
-    if poses is None and exposure is None:
+def _pose_view(poses, view_index, exposure=None, bilagrid=None) -> Optional[int]:
+    """The view a step refines, validated before anything reaches the device: required with `poses`, `exposure` or `bilagrid` (one
+    index for all), refused without."""
+    if poses is None and exposure is None and bilagrid is None:
         if view_index is not None:
             raise ValueError("TrainStepGraph.step: view_index given, but the runner was built without `poses` and without `exposure`")
         return None
     if view_index is None:
+        if poses is None and exposure is None:
+            raise ValueError("TrainStepGraph.step: the runner corrects appearance (bilagrid=BilateralGrids): every step needs view_index=i, "
+                             "the grid of `bilagrid.grids` that belongs to the step's target image")
         if poses is None:
             raise ValueError("TrainStepGraph.step: the runner compensates exposure (exposure=ExposureTable): every step needs view_index=i, "
                              "the row of `exposure.affine` that belongs to the step's target image")
         raise ValueError("TrainStepGraph.step: the runner refines poses (poses=CameraDeltas): every step needs view_index=i, the row of "
                          "`poses.deltas` that corrects data['w2c']")
     i = int(view_index)
-    for what, table in (("poses", None if poses is None else poses.deltas), ("exposure", None if exposure is None else exposure.affine)):
+    for what, table in (("poses", None if poses is None else poses.deltas), ("exposure", None if exposure is None else exposure.affine),
+                        ("bilagrid", None if bilagrid is None else bilagrid.grids)):
         if table is not None and not 0 <= i < int(table.shape[0]):
             raise ValueError(f"TrainStepGraph.step: view_index {i} outside the {int(table.shape[0])} views of `{what}`")
     return i
@@ -118,7 +128,9 @@ class TrainStepGraph:
                  fuse_adam: bool = True, handback: str = "eager", copy_targets: bool = False, rounds: str = "auto",
                  round_fraction: float = 0.125, mcmc=None, mcmc_reg: Tuple[float, float] = (0.01, 0.01), poses=None,
                  pose_lr: float = 1e-3, pose_betas: Tuple[float, float] = (0.9, 0.999), pose_eps: float = 1e-15, exposure=None,
-                 exposure_lr: float = 1e-2, exposure_betas: Tuple[float, float] = (0.9, 0.999), exposure_eps: float = 1e-15):
+                 exposure_lr: float = 1e-2, exposure_betas: Tuple[float, float] = (0.9, 0.999), exposure_eps: float = 1e-15, bilagrid=None,
+                 bilagrid_lr: float = 2e-3, bilagrid_betas: Tuple[float, float] = (0.9, 0.999), bilagrid_eps: float = 1e-15,
+                 bilagrid_tv: float = 10.0):
         """`mcmc`: an `mcmc.MCMCStrategy(model, ..., noise="counter")` -- the step then trains under its Gaussian budget: `mcmc_reg` =
         (opacity_reg, scale_reg) of `strategy.regularization()` enters the loss (out["mcmc_reg"]) and the update, and the strategy's
         noise runs behind Adam inside the step, at noise_lr x the means learning rate of that step.  None (default): nothing changes.
@@ -147,7 +159,41 @@ class TrainStepGraph:
         `exposure.affine.data` -- the 12 sums of the step (out["v_affine"]) on the view's row, zeros on the others -- under the step
         guard.  `runner.exposure_lr` is a plain attribute, staged every step outside the graph: a schedule is an assignment between
         steps.  The moments and the step count: `runner.exposure_state` (`exposure.ExposureAdamState`).  `exposure.affine` must keep
-        its storage while the runner lives.  None (default): nothing changes, launch for launch."""
+        its storage while the runner lives.  None (default): nothing changes, launch for launch.
+        `bilagrid`: a `bilagrid.BilateralGrids(n_views)` on the runner's device -- the step then corrects per-view appearance:
+        `step(..., view_index=i)` names the grid (the same index `poses` uses), the loss reads the slice of that grid applied to the
+        un-clamped render (out["exposed"]) plus `bilagrid_tv` times the total variation of ALL grids (out["bilagrid_tv"]), the
+        gradient of the raw render includes the part through the luminance guide, and beside the pose update one launch applies
+        Adam(bilagrid_lr, bilagrid_betas, bilagrid_eps) to every element of `bilagrid.grids.data` with the step's dense gradient
+        (out["v_grids"]: the slice's adjoint on the view's slab plus the TV gradient everywhere) under the step guard.
+        `runner.bilagrid_lr` is a plain attribute, staged every step outside the graph.  The moments and the step count:
+        `runner.bilagrid_state` (`bilagrid.BilagridAdamState`).  `bilagrid.grids` must keep its storage while the runner lives.  Not
+        together with `exposure` (`ValueError`): two colour models in front of one loss.  None (default): nothing changes, launch
+        for launch."""
+        if bilagrid is not None:
+            from .bilagrid import BilagridAdamState, BilateralGrids
+            if exposure is not None:
+                raise ValueError("TrainStepGraph: `exposure` and `bilagrid` together -- two colour models in front of one loss are ambiguous; "
+                                 "a bilateral grid contains the global affine")
+            if not isinstance(bilagrid, BilateralGrids):
+                raise TypeError("TrainStepGraph(bilagrid=...): a bilagrid.BilateralGrids")
+            g = bilagrid.grids
+            if g.device != model.means.device or g.dtype != torch.float32 or not g.is_contiguous() or g.dim() != 5 or g.shape[1] != 12:
+                raise ValueError("TrainStepGraph(bilagrid=...): `bilagrid.grids` must be a contiguous float32 [n_views, 12, L, Hg, Wg] on the "
+                                 "model's device")
+            if not 1 <= g.shape[0] <= nat.GS_BILAGRID_MAX_VIEWS:
+                raise ValueError("TrainStepGraph(bilagrid=...): 1 .. GS_BILAGRID_MAX_VIEWS views")
+            self.bilagrid_lr, self.bilagrid_eps, self.bilagrid_tv = float(bilagrid_lr), float(bilagrid_eps), float(bilagrid_tv)
+            self.bilagrid_betas = (float(bilagrid_betas[0]), float(bilagrid_betas[1]))
+            self.bilagrid_state = BilagridAdamState(bilagrid)
+            # runner-owned, outside the workspace layout, alive across re-builds: the record, the view's slab, the dense gradient, the
+            # TV value and its scratch (the image and the partials are sized by the frame: `_build`)
+            f32g = dict(dtype=torch.float32, device=g.device)
+            self._bilagrid_bufs = {"bilagrid_rec": torch.zeros((nat.GS_BILAGRID_REC_FLOATS,), **f32g),
+                                   "v_slab": torch.zeros(tuple(g.shape[1:]), **f32g), "v_grids": torch.zeros(tuple(g.shape), **f32g),
+                                   "bilagrid_tv": torch.zeros((1,), **f32g),
+                                   "bilagrid_tv_ws": torch.zeros((nat.GS_BILAGRID_TV_DOUBLES,), dtype=torch.float64, device=g.device)}
+        self.bilagrid = bilagrid
         if exposure is not None:
             from .exposure import ExposureAdamState, ExposureTable
             if not isinstance(exposure, ExposureTable):
@@ -185,6 +231,8 @@ class TrainStepGraph:
         self.poses = poses
         if exposure is not None:   # (view, exposure step count, learning rate) of the step about to be staged: the build's own
             self._exposure_cur = (_pose_view(poses, data.get("view_index", 0), exposure), self.exposure_state.step + 1, self.exposure_lr)
+        if bilagrid is not None:   # likewise (view, the grids' step count, learning rate)
+            self._bilagrid_cur = (_pose_view(poses, data.get("view_index", 0), None, bilagrid), self.bilagrid_state.step + 1, self.bilagrid_lr)
         self.mcmc = mcmc
         if mcmc is not None:
             if getattr(mcmc, "noise", None) != "counter":
@@ -338,6 +386,13 @@ class TrainStepGraph:
                 eb["exposed"] = torch.empty((H, W, 3), **f32)
                 eb["exposure_partials"] = torch.empty((int(L.gs_exposure_partials_doubles(H, W)),), dtype=torch.float64, device=dev)
             b.update(eb)
+        if self.bilagrid is not None:
+            gb = self._bilagrid_bufs
+            if "exposed" not in gb or tuple(gb["exposed"].shape) != (H, W, 3):   # (the first build, or another frame size)
+                gl, gy, gx = (int(x) for x in self.bilagrid.grids.shape[2:])
+                gb["exposed"] = torch.empty((H, W, 3), **f32)
+                gb["bilagrid_partials"] = torch.empty((int(L.gs_bilagrid_partials_doubles(H, W, gx, gy, gl)),), dtype=torch.float64, device=dev)
+            b.update(gb)
         # {reg, -, fp64 block partials}: the regulariser's value and its reduction scratch (gs_scale_reg)
         b["scale_reg"] = self._take("scale_reg", (int(L.gs_scale_reg_workspace_floats(N)),), torch.float32) if self.scale_reg else None
         if self.mcmc is not None:
@@ -540,7 +595,8 @@ class TrainStepGraph:
         """The step's static camera INPUT [1,4,4]: the view matrix the projection reads, or (poses) the raw matrix in the pose record."""
         return self.buf["w2c_raw"] if self.poses is not None else self.buf["viewmats"]
 
-    def _stage_inputs(self, t: int, lrs, w2c: Tensor, K: Tensor, gt: Tensor, mask: Optional[Tensor], pose=None, exposure=None):
+    def _stage_inputs(self, t: int, lrs, w2c: Tensor, K: Tensor, gt: Tensor, mask: Optional[Tensor], pose=None, exposure=None,
+                      bilagrid=None):
         """Everything that differs from the previous step, in ONE launch on the current stream (gs_step_inputs): Adam's bias
         corrections / learning rates, the camera into the static buffers, and the POINTERS to the target image and mask.
         Returns the (gt, mask) tensors whose pointers went in -- the caller keeps them alive until the step is applied."""
@@ -580,6 +636,10 @@ class TrainStepGraph:
             view, exp_t, exp_lr = exposure if exposure is not None else self._exposure_cur
             nat.check(L.gs_exposure_step_inputs(self._st(), int(view), int(self.exposure.affine.shape[0]), float(exp_lr), self.exposure_betas[0],
                                                 self.exposure_betas[1], int(exp_t), _p(b["exposure_rec"])), "gs_exposure_step_inputs")
+        if self.bilagrid is not None:   # the view and the grids' Adam's bias corrections at ITS step count and the step's own rate
+            view, bg_t, bg_lr = bilagrid if bilagrid is not None else self._bilagrid_cur
+            nat.check(L.gs_bilagrid_step_inputs(self._st(), int(view), int(self.bilagrid.grids.shape[0]), float(bg_lr), self.bilagrid_betas[0],
+                                                self.bilagrid_betas[1], int(bg_t), _p(b["bilagrid_rec"])), "gs_bilagrid_step_inputs")
         if self.mcmc is not None:   # the step's noise: its strength at the means learning rate this step's Adam uses, its counter, the seed
             nat.check(L.gs_mcmc_step_inputs(self._st(), self.mcmc.noise_lr * float(lrs[self._means_seg]), int(t), self.mcmc.seed,
                                             _p(b["mcmc_rec"])), "gs_mcmc_step_inputs")
@@ -766,6 +826,11 @@ class TrainStepGraph:
             if self.exposure is not None:   # the loss reads the view's affine of the render; the blend backward keeps the raw render
                 n_exp, tab, img = int(self.exposure.affine.shape[0]), _p(self.exposure.affine.data), b["exposed"]
                 self._ck(L.gs_exposure_apply(st, H, W, n_exp, _p(b["exposure_rec"]), 0, tab, _p(b["render_colors"]), _p(img)), "gs_exposure_apply")
+            if self.bilagrid is not None:   # the loss reads the slice of the view's grid applied to the render
+                img = b["exposed"]
+                n_bg, gx, gy, gl = self._bilagrid_shape()
+                self._ck(L.gs_bilagrid_apply(st, H, W, n_bg, gx, gy, gl, _p(b["bilagrid_rec"]), 0, _p(self.bilagrid.grids.data),
+                                             _p(b["render_colors"]), _p(img)), "gs_bilagrid_apply")
             self._ck(L.gs_l1_ssim_fwd_slots(st, H, W, lam, _p(img), _p(b["img_slots"]), int(self.has_mask), 1, _p(b["loss_ws"]),
                                              _p(b["loss3"])), "gs_l1_ssim_fwd_slots")
             self._ck(L.gs_l1_ssim_bwd_slots(st, H, W, lam, _p(img), _p(b["img_slots"]), 1, _p(b["loss_ws"]),
@@ -773,10 +838,16 @@ class TrainStepGraph:
             if self.exposure is not None:   # v_render: dL/d exposed -> dL/d render in place; the 12 sums of the view's row
                 self._ck(L.gs_exposure_bwd(st, H, W, n_exp, _p(b["exposure_rec"]), 0, tab, _p(b["render_colors"]), _p(b["v_render"]),
                                            _p(b["exposure_partials"]), _p(b["v_affine"])), "gs_exposure_bwd")
+            if self.bilagrid is not None:   # v_render: dL/d exposed -> dL/d render in place; the slice's adjoint into the view's slab
+                self._ck(L.gs_bilagrid_bwd(st, H, W, n_bg, gx, gy, gl, _p(b["bilagrid_rec"]), 0, _p(self.bilagrid.grids.data),
+                                           _p(b["render_colors"]), _p(b["v_render"]), _p(b["bilagrid_partials"]), _p(b["v_slab"])),
+                         "gs_bilagrid_bwd")
             if self.scale_reg and self.fuse_adam:   # the value, from the parameters before the in-place update; the gradient: `_enqueue_rest`
                 self._scale_reg(None)
             if self.mcmc is not None and self.fuse_adam:   # likewise the budget regulariser's, behind it in the total
                 self._mcmc_reg(None, None)
+            if self.bilagrid is not None and self.fuse_adam:   # the total variation behind both: the total sums scale, budget, TV
+                self._bilagrid_tv()
             rendering.stage_blend_bwd(L, st, self.lease, 1, W, H, 3, _p(b["render_colors"]), _p(b["render_alphas"]), _p(b["v_render"]), None,
                                       _p(b["unit_cls"]), self._ck)
             self._enqueue_rest(st)
@@ -838,6 +909,8 @@ class TrainStepGraph:
                 self._scale_reg(g["log_scales"])
             if self.mcmc is not None:
                 self._mcmc_reg(g["logit_opacities"], g["log_scales"])
+            if self.bilagrid is not None:
+                self._bilagrid_tv()
             self._ck(L.gs_update_statistics(st, N, float(max(H, W)), _p(b["radii"]), _p(b["v_abs"]), _p(m.max_radii),
                                             _p(m.grad_norm_accum), _p(m.collecting_counts)), "gs_update_statistics")
             ns = len(opt._plist)
@@ -860,6 +933,11 @@ class TrainStepGraph:
             self._ck(L.gs_exposure_adam(st, int(self.exposure.affine.shape[0]), _p(b["exposure_rec"]), _p(self.exposure.affine.data),
                                         _p(es.exp_avg), _p(es.exp_avg_sq), _p(b["v_affine"]), self.exposure_betas[0], self.exposure_betas[1],
                                         self.exposure_eps), "gs_exposure_adam")
+        if self.bilagrid is not None:   # Adam over every grid with the step's dense gradient; a skipped step moves none
+            gs_ = self.bilagrid_state
+            self._ck(L.gs_bilagrid_adam(st, int(self.bilagrid.grids.numel()), _p(b["bilagrid_rec"]), _p(self.bilagrid.grids.data),
+                                        _p(gs_.exp_avg), _p(gs_.exp_avg_sq), _p(b["v_grids"]), self.bilagrid_betas[0], self.bilagrid_betas[1],
+                                        self.bilagrid_eps), "gs_bilagrid_adam")
         self._ck(L.gs_step_status(st, _p(b["info"]), _p(b["applied"]), self.status.data_ptr(), _p(b["loss3"]), _p(b["loss_ring"]),
                                   self.LOSS_RING, _p(b["walk_state"])), "gs_step_status")
 
@@ -870,6 +948,20 @@ class TrainStepGraph:
         v = v_log_scales if (v_log_scales is None or isinstance(v_log_scales, int)) else v_log_scales.data_ptr()
         (check or self._ck)(nat.lib().gs_scale_reg(self._st(), self.N, _p(m.log_scales), self.max_scale_ratio, self.lambda_scale, _p(b["loss3"]),
                                         _p(b["scale_reg"]), v), "gs_scale_reg")
+
+    def _bilagrid_shape(self):
+        """(n_views, grid_x, grid_y, grid_l) as the gs_bilagrid_* entries take them."""
+        n, _, gl, gy, gx = (int(x) for x in self.bilagrid.grids.shape)
+        return n, gx, gy, gl
+
+    def _bilagrid_tv(self):
+        """The grids' total variation on the current stream: bilagrid_tv * tv into loss3[2], tv into buf["bilagrid_tv"], and the
+        step's dense gradient buf["v_grids"] = bilagrid_tv * d tv / d grids + the view's slab -- from the grids before the update."""
+        b = self.buf
+        n_bg, gx, gy, gl = self._bilagrid_shape()
+        self._ck(nat.lib().gs_bilagrid_tv(self._st(), n_bg, gx, gy, gl, _p(self.bilagrid.grids.data), self.bilagrid_tv,
+                                          _p(b["bilagrid_rec"]), 0, _p(b["v_slab"]), _p(b["loss3"]), _p(b["bilagrid_tv"]), _p(b["v_grids"]),
+                                          _p(b["bilagrid_tv_ws"])), "gs_bilagrid_tv")
 
     def _mcmc_reg(self, v_logit: Optional[Tensor], v_log_scales: Optional[Tensor]):
         """The budget regulariser on the current stream: reg into loss3[2] and buf["mcmc_reg"][0], and (gradient tensors given) its
@@ -902,6 +994,8 @@ class TrainStepGraph:
                 pose_live = (self.poses.deltas.data, self.pose_state.exp_avg, self.pose_state.exp_avg_sq) if self.poses is not None else ()
                 if self.exposure is not None:   # (the table and its moments are throw-away state of the warm-up step like the deltas)
                     pose_live += (self.exposure.affine.data, self.exposure_state.exp_avg, self.exposure_state.exp_avg_sq)
+                if self.bilagrid is not None:
+                    pose_live += (self.bilagrid.grids.data, self.bilagrid_state.exp_avg, self.bilagrid_state.exp_avg_sq)
                 pose_saved = [x.clone() for x in pose_live]
                 self._hyper(max(opt._step, 0) + 1, [float(grp["lr"]) for grp, _ in opt._plist])
                 self._enqueue_step()
@@ -936,6 +1030,7 @@ class TrainStepGraph:
         after = entry[8] if len(entry) > 8 else None
         pose = entry[10] if len(entry) > 10 else None   # (view index, pose step count): poses
         expo = entry[11] if len(entry) > 11 else None   # (view index, exposure step count, learning rate): exposure
+        bgrid = entry[12] if len(entry) > 12 else None  # (view index, the grids' step count, learning rate): bilagrid
         # The step waits for the caller's stream on entry: that orders it behind pending WRITERS of the inputs handed in and
         # behind pending READERS of what the replay overwrites -- the static outputs the previous `step()` returned, the
         # parameters and moments (fused Adam), the statistics.  (Round 3 skipped the wait for steps that take no input from
@@ -953,7 +1048,7 @@ class TrainStepGraph:
                 for ev in (after if isinstance(after, (list, tuple)) else (after,)):
                     self.stream.wait_event(ev)
                 entry[8] = None
-            entry[4], entry[5] = self._stage_inputs(t, lrs, w2c, K, gt, mask, pose, expo)   # (the tensors the step reads: kept by the entry)
+            entry[4], entry[5] = self._stage_inputs(t, lrs, w2c, K, gt, mask, pose, expo, bgrid)   # (the tensors the step reads: kept by the entry)
             if self.graph is not None:
                 self.graph.replay()
             else:
@@ -983,8 +1078,8 @@ class TrainStepGraph:
         `view_index`: with `poses`, required -- the row of `poses.deltas` that corrects this step's `data["w2c"]` (data=None: the
         previous step's raw matrix); with `exposure`, required -- the row of `exposure.affine` of this step's target image."""
         _refuse_camera_grads(data)
-        exposure = getattr(self, "exposure", None)
-        view = _pose_view(self.poses, view_index, exposure)
+        exposure, bilagrid = getattr(self, "exposure", None), getattr(self, "bilagrid", None)
+        view = _pose_view(self.poses, view_index, exposure, bilagrid)
         W, H = (self.W, self.H) if data is None else (int(data["width"]), int(data["height"]))
         if self._state_key(W, H) != self._key:
             self.finish()
@@ -1074,6 +1169,10 @@ class TrainStepGraph:
                 self.exposure_state.step += 1
                 self._exposure_cur = (view, self.exposure_state.step, float(self.exposure_lr))
                 entry.append(self._exposure_cur)
+            if bilagrid is not None:   # (entry[12]; entry[11] stays the exposure's place)
+                self.bilagrid_state.step += 1
+                self._bilagrid_cur = (view, self.bilagrid_state.step, float(self.bilagrid_lr))
+                entry.extend([None, self._bilagrid_cur])
         self._issue(entry)
         if self.issued % self.check_every == 0:
             self._poll(block=False)
@@ -1088,6 +1187,10 @@ class TrainStepGraph:
         if exposure is not None:
             outs["exposed"] = b["exposed"]        # the image the loss read: the view's affine of render_img
             outs["v_affine"] = b["v_affine"]      # dL / d exposure.affine[view_index], 12 floats row-major [3][4]
+        if bilagrid is not None:
+            outs["exposed"] = b["exposed"]          # the image the loss read: the slice of the view's grid applied to render_img
+            outs["v_grids"] = b["v_grids"]          # dL / d bilagrid.grids of the step, dense: the view's slab + the TV gradient
+            outs["bilagrid_tv"] = b["bilagrid_tv"]  # the total variation of all grids (the loss total holds bilagrid_tv times it)
         return TrainStepGraph._StepOutputs(self, outs, lazy=self.handback == "lazy")
 
     def _poll(self, block: bool):
@@ -1139,6 +1242,8 @@ class TrainStepGraph:
             self._pose_cur = first[10]   # (the probe of the re-build runs on the first skipped step's own view)
         if self.exposure is not None:
             self._exposure_cur = first[11]
+        if self.bilagrid is not None:
+            self._bilagrid_cur = first[12]
         # (min_cap >= 1 forces a fresh probe even when only a coarse-bin capacity was exceeded and the list sizes read 0)
         self._build({"w2c": first[2], "K": first[3]}, first[4], first[5], min_cap=max(n_isects, 1), min_cap_tile=max_tile, min_walk=walk)
         for e in redo:
@@ -1168,6 +1273,8 @@ class TrainStepGraph:
             extra.update(poses=True, pose_lr=self.pose_lr, pose_steps=self.pose_state.step)
         if self.exposure is not None:
             extra.update(exposure=True, exposure_lr=self.exposure_lr, exposure_steps=self.exposure_state.step)
+        if self.bilagrid is not None:
+            extra.update(bilagrid=True, bilagrid_lr=self.bilagrid_lr, bilagrid_tv=self.bilagrid_tv, bilagrid_steps=self.bilagrid_state.step)
         return dict(self.stats, **extra, binning=self.binning, probed_isects=self.probed[0], probed_longest_list=self.probed[1],
                     probed_coarse_entries=getattr(self, "probed_coarse", (0, 0))[0] if self.binning == "bins" else 0,
                     capacity_isects=self.cap, capacity_tile_list=self.cap_tile, capacity_work_units=self.cap_units,
@@ -1202,6 +1309,9 @@ class ViewParallelGraphStep(TrainStepGraph):
         if kw.get("exposure") is not None:
             raise ValueError("ViewParallelGraphStep: no `exposure` -- exposure compensation inside the captured step is single-GPU "
                              "(TrainStepGraph(exposure=...)): the view-parallel step's loss reads each rank's raw render")
+        if kw.get("bilagrid") is not None:
+            raise ValueError("ViewParallelGraphStep: no `bilagrid` -- bilateral grids inside the captured step are single-GPU "
+                             "(TrainStepGraph(bilagrid=...)): the view-parallel step's loss reads each rank's raw render")
         if kw.get("mcmc") is not None:
             raise ValueError("ViewParallelGraphStep: no `mcmc` -- MCMCStrategy refuses torch.distributed (the replicas would need "
                              "broadcast draws)")
@@ -1356,8 +1466,8 @@ class HostFeed:
                 self.mask[j].copy_(batch["mask"], non_blocking=True)
             ev = torch.cuda.Event()
             ev.record(cs)
-        per_view = getattr(r, "poses", None) is not None or getattr(r, "exposure", None) is not None
-        view = batch.get("view_index") if per_view else None   # (poses / exposure: the batch names its row of the tables)
+        per_view = any(getattr(r, what, None) is not None for what in ("poses", "exposure", "bilagrid"))
+        view = batch.get("view_index") if per_view else None   # (poses / exposure / bilagrid: the batch names its row of the tables)
         out = r.step({"w2c": self.w2c[j], "K": self.K[j], "width": r.W, "height": r.H}, self.gt[j], self.mask[j] if r.has_mask else None,
                      inputs_ready=self.inputs_ready, ready_event=ev, host_src=batch, view_index=view)
         self.done[j] = torch.cuda.Event()

@@ -921,6 +921,58 @@ int gs_exposure_bwd(void* stream, int height, int width, int n_views, const floa
 int gs_exposure_adam(void* stream, int n_views, const float* rec_dev, float* table, float* exp_avg, float* exp_avg_sq,
                      const float* v_affine12, float beta1, float beta2, float eps);
 
+/* ---- Per-view bilateral grids (DESIGN.md "Bilateral grids in the captured step"): bilagrid.BilateralGrids' learnable low-resolution
+ * 3-D grid of 3x4 colour affines per training image, grids[n_views][12][grid_l][grid_y][grid_x] f32 (channel k = 4 i + j is entry
+ * (i, j) of [A | b]), sliced at each pixel's position and at the luminance of the UN-clamped render's own colour c and applied to it:
+ *     luma = fma(0.114, c_2, fma(0.587, c_1, 0.299 c_0))
+ *     (gx, gy, gz) = ((x + 0.5) / width * (grid_x - 1), (y + 0.5) / height * (grid_y - 1), clamp(luma, 0, 1) * (grid_l - 1))
+ *     M = the trilinear interpolation of the 12 channels at (gx, gy, gz),   out = M[:, :3] c + M[:, 3]
+ * -- torch's grid_sample(mode="bilinear", align_corners=True, padding_mode="border").  The math is csrc/gs_bilagrid.h (shared with
+ * the host tests): the cell is min(floor(g), n - 2) per axis, never outside the slab whatever the render holds; the interpolation
+ * is lerps fma(t, b - a, a) along x, then y, then z (equal nodes interpolate to themselves); the apply is gs_exposure_apply's chain.
+ * At [I | 0] in every node the input comes back exactly (a -0 as +0).  Images are [height][width][3] f32; images, grids and v_slab
+ * 16-byte aligned.  2 <= grid_x, grid_y <= GS_BILAGRID_MAX_XY, 2 <= grid_l <= GS_BILAGRID_MAX_L, 1 <= n_views <=
+ * GS_BILAGRID_MAX_VIEWS, n_views * 12 * grid_l * grid_y * grid_x < 2^31, 3 * height * width < 2^31: anything else is GS_ERR_ARG before
+ * any launch.
+ * gs_bilagrid_step_inputs: gs_exposure_step_inputs for the grids' own Adam: rec_dev[GS_BILAGRID_REC_FLOATS] f32, 16-byte aligned =
+ *   {lr / (1 - beta1^step), 1 / sqrt(1 - beta2^step), the bits of the int32 view index, 0}.
+ * gs_bilagrid_apply: out = the slice of a view's slab applied to render.  The view: the record's when rec_dev is non-NULL (the
+ *   captured step), else `view` (eager).  out may not alias render.
+ * gs_bilagrid_bwd: v_image holds dL/d out on entry and dL/d render on exit, in place:
+ *     M[:, :3]^T v + (0.299, 0.587, 0.114) v_luma,   v_luma = (grid_l - 1) sum_i v_i ((M_z1 - M_z0)_i . [c; 1]) for 0 < luma < 1, else 0
+ *   (M_z0, M_z1: the bilinear interpolants on the cell's two luminance planes); v_slab[12][grid_l][grid_y][grid_x], fully written =
+ *   the adjoint of the interpolation applied to v_out [c; 1]^T, summed over the pixels.  No atomics: a block owns (spatial cell,
+ *   chunk of its pixels, luminance node) and sums its pixels' terms -- exact fp64 products of the fp32 factors times fp64 weights --
+ *   per thread, over the wave, over the block's waves in order into partials[gs_bilagrid_partials_doubles(...)]; a second kernel
+ *   adds, per node, the partials of the at most four cells that touch it (cell rows, then columns, then chunks ascending) and
+ *   rounds to fp32 once.  Two runs give the same bits.
+ * gs_bilagrid_tv: tv = (1 / n_views) sum over the axes a in {l, y, x} of sum((forward difference along a)^2) / count_a, count_a
+ *   the differences along a in one view's slab; the sum in fp64 in a fixed order (tv_ws[GS_BILAGRID_TV_DOUBLES] doubles of scratch).
+ *   tv_out (optional): tv_out[0] = tv; loss3 (optional): loss3[2] += tv_weight * tv, the product rounded on its own (as gs_scale_reg
+ *   enters the total); v_grids (optional) [n_views][12][grid_l][grid_y][grid_x], fully written = fl32(tv_weight * d tv / d grids),
+ *   plus v_slab (optional) on the view's slab (the record's view, else `view`).  Reads the grids only.  Honours the step guard.
+ * gs_bilagrid_adam: Adam (gs_adam_step's arithmetic per element) over ALL numel = n_views * 12 * grid_l * grid_y * grid_x elements
+ *   with the gradient v_grids -- torch.optim.Adam over the whole parameter: idle views decay their moments and move.  Honours the
+ *   step guard: a voided step leaves the grids and the moments untouched. */
+#define GS_BILAGRID_REC_FLOATS 4
+#define GS_BILAGRID_REC_SS 0
+#define GS_BILAGRID_REC_ISBC2 1
+#define GS_BILAGRID_REC_VIEW 2
+#define GS_BILAGRID_MAX_VIEWS 1048576
+#define GS_BILAGRID_MAX_XY 64
+#define GS_BILAGRID_MAX_L 16
+#define GS_BILAGRID_TV_DOUBLES 1024
+int gs_bilagrid_step_inputs(void* stream, int view, int n_views, float lr, float beta1, float beta2, int64_t step, float* rec_dev);
+int gs_bilagrid_apply(void* stream, int height, int width, int n_views, int grid_x, int grid_y, int grid_l, const float* rec_dev,
+                      int view, const float* grids, const float* render, float* out);
+size_t gs_bilagrid_partials_doubles(int height, int width, int grid_x, int grid_y, int grid_l);
+int gs_bilagrid_bwd(void* stream, int height, int width, int n_views, int grid_x, int grid_y, int grid_l, const float* rec_dev,
+                    int view, const float* grids, const float* render, float* v_image, double* partials, float* v_slab);
+int gs_bilagrid_tv(void* stream, int n_views, int grid_x, int grid_y, int grid_l, const float* grids, float tv_weight,
+                   const float* rec_dev, int view, const float* v_slab, float* loss3, float* tv_out, float* v_grids, double* tv_ws);
+int gs_bilagrid_adam(void* stream, int64_t numel, const float* rec_dev, float* grids, float* exp_avg, float* exp_avg_sq,
+                     const float* v_grids, float beta1, float beta2, float eps);
+
 #ifdef __cplusplus
 }
 #endif
