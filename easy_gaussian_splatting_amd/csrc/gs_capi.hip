@@ -140,7 +140,7 @@ extern "C" int gs_step_applied(void* stream, const int64_t* info_dev, int64_t* a
     return GS_OK;
 }
 
-extern "C" int gs_version(void) { return 390; }
+extern "C" int gs_version(void) { return 400; }
 // The preprocessor flags beyond the Makefile's own this library was built with ("" = the product build): a -DGS_BWD_CHECK,
 // -DGS_BWD_ACC64, -DGS_EXACT_MATH or -DGS_CLOCK_PROBE diagnostic variant names itself, and the Python binding refuses to load
 // one unless it is asked to (easy_gaussian_splatting_amd/_native.py).

@@ -39,6 +39,17 @@ struct DepthGradArgs {
     const int64_t* guard;
 };
 
+// v_z of (camera, Gaussian) f: lane a.lane of the sum of the colour quads of its gradient rows (0 for culled Gaussians and rows nobody
+// took) -- the one gather of depth_grads_kernel and depth_grads_z_kernel.  Every lane of the wave calls it.
+__device__ __forceinline__ float depth_row_vz(const DepthGradArgs& a, int64_t f, bool in_range, float4* item) {
+    const bool vis = in_range && a.radii[f] > 0;
+    const int cnt = vis ? a.tiles_per_gauss[f] : 0;
+    const int base = vis ? a.cum_tiles[f] : 0;
+    int r0 = 0, nr = 0;
+    if (cnt > 0) { r0 = rows_before(a.row_base, a.qmask, base); nr = rows_before(a.row_base, a.qmask, base + cnt) - r0; }
+    return quad_lane(quad_sums_wave(a.rows, nr, r0, item), a.lane);
+}
+
 // One thread per Gaussian n, the cameras in order (v_means accumulates in camera order, like gs_project_bwd's launches).
 __global__ __launch_bounds__(kDepthThreads) void depth_grads_kernel(const DepthGradArgs a) {
     __shared__ float4 items[kDepthThreads / 64][64];
@@ -55,12 +66,7 @@ __global__ __launch_bounds__(kDepthThreads) void depth_grads_kernel(const DepthG
     }
     for (int c = 0; c < a.C; ++c) {
         const int64_t f = (int64_t)c * a.N + n;
-        const bool vis = in_range && a.radii[f] > 0;
-        const int cnt = vis ? a.tiles_per_gauss[f] : 0;
-        const int base = vis ? a.cum_tiles[f] : 0;
-        int r0 = 0, nr = 0;
-        if (cnt > 0) { r0 = rows_before(a.row_base, a.qmask, base); nr = rows_before(a.row_base, a.qmask, base + cnt) - r0; }
-        const float v_z = quad_lane(quad_sums_wave(a.rows, nr, r0, item), a.lane);   // (0 for culled Gaussians and rows nobody took)
+        const float v_z = depth_row_vz(a, f, in_range, item);
         const float* V = a.viewmats + 16 * c;
         const float row2[3] = {V[8], V[9], V[10]};
         depth_vjp_mean(v_z, row2, v_mean);
@@ -84,6 +90,21 @@ __global__ __launch_bounds__(kDepthThreads) void depth_grads_kernel(const DepthG
         }
     }
     if (in_range) { a.v_means[3 * n] = v_mean[0]; a.v_means[3 * n + 1] = v_mean[1]; a.v_means[3 * n + 2] = v_mean[2]; }
+}
+
+// The gather of depth_grads_kernel alone: v_depths[f] = v_z, the same depth_row_vz over the same rows (hence the same bits), no
+// gradient touched -- what gs_project_bwd_adam_depth adds to the means gradient it forms in registers.
+__global__ __launch_bounds__(kDepthThreads) void depth_grads_z_kernel(const DepthGradArgs a) {
+    __shared__ float4 items[kDepthThreads / 64][64];
+    if (guard_tripped(a.guard)) return;
+    const int64_t n = (int64_t)blockIdx.x * kDepthThreads + threadIdx.x;
+    const bool in_range = n < a.N;
+    float4* item = items[threadIdx.x >> 6];
+    for (int c = 0; c < a.C; ++c) {
+        const int64_t f = (int64_t)c * a.N + n;
+        const float v_z = depth_row_vz(a, f, in_range, item);
+        if (in_range) a.v_depths[f] = v_z;
+    }
 }
 
 // One block per camera: each of the 4 values is walked by 64 threads over the camera's partials at a stride of 64 blocks, and the
@@ -208,6 +229,23 @@ extern "C" int gs_depth_grads(void* stream, int C, int64_t N, int lane, const fl
                            v_viewmats, a.guard);
         GS_LAUNCH_CHECK("depth_cam_sum_kernel");
     }
+    return GS_OK;
+}
+
+extern "C" int gs_depth_grads_z(void* stream, int C, int64_t N, int lane, const int32_t* radii, const int32_t* tiles_per_gauss,
+                                const int32_t* cum_tiles, const float* rows, const int32_t* row_base, const uint8_t* qmask, float* v_depths) {
+    GS_REQUIRE(lane >= 0 && lane <= 3, "lane must be 0, 1, 2 or 3");
+    GS_REQUIRE(C >= 1 && N >= 0, "C>=1, N>=0");
+    GS_REQUIRE(current_rounds().phase == 0, "the rows of depth rounds are two ranges: depth gradients are one-round only");
+    if (N == 0) return GS_OK;
+    GS_REQUIRE(radii && tiles_per_gauss && cum_tiles && rows && row_base && qmask && v_depths, "null pointer");
+    GS_REQUIRE(((uintptr_t)rows & 15) == 0 && ((uintptr_t)qmask & 15) == 0, "rows / qmask 16-byte aligned");
+    DepthGradArgs a = {};
+    a.C = C; a.lane = lane; a.N = N; a.radii = radii; a.tiles_per_gauss = tiles_per_gauss; a.cum_tiles = cum_tiles; a.row_base = row_base;
+    a.qmask = qmask; a.rows = reinterpret_cast<const float4*>(rows); a.v_depths = v_depths; a.guard = current_guard().info;
+    hipLaunchKernelGGL(depth_grads_z_kernel, dim3((unsigned)((N + kDepthThreads - 1) / kDepthThreads)), dim3(kDepthThreads), 0,
+                       (hipStream_t)stream, a);
+    GS_LAUNCH_CHECK("depth_grads_z_kernel");
     return GS_OK;
 }
 

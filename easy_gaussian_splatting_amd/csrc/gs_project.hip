@@ -408,6 +408,9 @@ struct ProjBwdArgs {
     // Budget regulariser (gs_project_bwd_adam_mcmc; REG & 2 only): fl32(a / N) and fl32(b / (3 N)), the upstream gradients of one
     // opacity and of one scale -- its gradients join v_opacity and v_scale the same way (gs_common.h budget_reg_term)
     float bud_ga, bud_gb;
+    // Depth supervision (gs_project_bwd_adam_depth; REG & 4 only): v_z per Gaussian from gs_depth_grads_z -- v_z times row 2 of the view
+    // matrix joins v_mean behind the projection's VJP, as gs_depth_grads adds it to the gradient gs_project_bwd wrote
+    const float* v_depths;
 };
 
 __device__ __forceinline__ float* adam_p(const ProjBwdArgs& a, int t) { return a.ad_pbase + a.ad_off[t]; }
@@ -753,6 +756,13 @@ __global__ __launch_bounds__(kProjThreads) void project_bwd_kernel(const ProjBwd
 template <int DEG, int REG, bool SUMS = false>
 __global__ __launch_bounds__(kProjThreads) void project_bwd_budget_kernel(const ProjBwdArgs a) {
     constexpr bool ADAM = true;
+#include "gs_project_bwd_body.h"
+}
+
+// the fused form with a depth gradient (gs_project_bwd_adam_depth): REG = 4 | the two regularisers' bits
+template <int DEG, int REG>
+__global__ __launch_bounds__(kProjThreads) void project_bwd_depth_kernel(const ProjBwdArgs a) {
+    constexpr bool ADAM = true, SUMS = false;
 #include "gs_project_bwd_body.h"
 }
 
@@ -1360,7 +1370,7 @@ static int project_bwd_adam(void* stream, int64_t N, int K, int sh_degree, float
                             float* v_means2d_abs, float beta1, float beta2, float eps, const float* hyper_dev,
                             int64_t* applied_dev, float* max_radii, float* grad_norm_accum, float* counts,
                             const float* sh_jac, int reg, float max_ratio, float lambda, double bud_a, double bud_b,
-                            const float* row_sums = nullptr) {
+                            const float* row_sums = nullptr, const float* v_depths = nullptr) {
     GS_REQUIRE(N >= 0 && width > 0 && height > 0, "N>=0, positive image size");
     GS_REQUIRE(sh_degree >= 0 && sh_degree <= 4 && K >= (sh_degree + 1) * (sh_degree + 1) && K <= 25, "SH colours: 0 <= degree <= 4, (degree+1)^2 <= K <= 25");
     if (N == 0) return GS_OK;
@@ -1393,6 +1403,7 @@ static int project_bwd_adam(void* stream, int64_t N, int K, int sh_degree, float
     a.cam = 0; a.accumulate = 0;
     a.reg_ratio = max_ratio; a.reg_grad = (reg & 1) ? scale_reg_upstream(lambda, N) : 0.f;
     a.bud_ga = (reg & 2) ? budget_reg_upstream(bud_a, N) : 0.f; a.bud_gb = (reg & 2) ? budget_reg_upstream(bud_b, 3 * N) : 0.f;
+    a.v_depths = v_depths;
     dim3 grid((unsigned)((N + kProjThreads - 1) / kProjThreads));
     const size_t lds = proj_bwd_lds_bytes(K, sh_degree);
     hipStream_t st = (hipStream_t)stream;
@@ -1400,7 +1411,10 @@ static int project_bwd_adam(void* stream, int64_t N, int K, int sh_degree, float
     //  none of them with scratch: a kernel that declares it makes the runtime provision it -- gs_blend.hip, GS_FWD_TRAIN_WAVES_PER_EU)
 #define GS_PBK(...) { GS_LDS((__VA_ARGS__)); hipLaunchKernelGGL((__VA_ARGS__), grid, dim3(kProjThreads), lds, st, a); }
 #define GS_PB(D)                                                                                                        \
-    if (row_sums) {                                                                                                     \
+    if (v_depths) {                                                                                                     \
+        if (reg == 3) GS_PBK(project_bwd_depth_kernel<D, 7>) else if (reg == 2) GS_PBK(project_bwd_depth_kernel<D, 6>)                  \
+        else if (reg == 1) GS_PBK(project_bwd_depth_kernel<D, 5>) else GS_PBK(project_bwd_depth_kernel<D, 4>)                           \
+    } else if (row_sums) {                                                                                                     \
         if (reg == 3) GS_PBK(project_bwd_budget_kernel<D, 3, true>) else if (reg == 2) GS_PBK(project_bwd_budget_kernel<D, 2, true>)    \
         else if (reg == 1) GS_PBK(project_bwd_kernel<D, true, true, true>) else GS_PBK(project_bwd_kernel<D, true, true>)               \
     } else if (reg == 3) GS_PBK(project_bwd_budget_kernel<D, 3>) else if (reg == 2) GS_PBK(project_bwd_budget_kernel<D, 2>)             \
@@ -1480,4 +1494,27 @@ extern "C" int gs_project_bwd_adam_sums(void* stream, int64_t N, int K, int sh_d
                             near_plane, far_plane, radii, colors_post, tiles_per_gauss, cum_tiles, nullptr, nullptr, nullptr, v_means2d_abs,
                             beta1, beta2, eps, hyper_dev, applied_dev, max_radii, grad_norm_accum, counts, sh_jac, (budget ? 2 : 0) | scale_reg,
                             max_ratio, lambda, a, b, row_sums);
+}
+
+// ... with the depth channel's gradient in v_mean: v_depths[N] (gs_depth_grads_z on the step's gradient rows, just before) times row 2 of
+// the view matrix, behind the projection's VJP and in front of the regularisers -- the order of gs_project_bwd, gs_depth_grads,
+// gs_scale_reg / gs_mcmc_reg, gs_adam_step_dev, hence the same update bit for bit.  An instantiation of its own per (degree, regulariser
+// mask): the existing kernels compile as they did.
+extern "C" int gs_project_bwd_adam_depth(void* stream, int64_t N, int K, int sh_degree, float* params, float* exp_avg, float* exp_avg_sq,
+                                         const int64_t* offsets_host, const float* viewmats, const float* Ks, int width, int height,
+                                         float eps2d, float near_plane, float far_plane, const int32_t* radii, const float* colors_post,
+                                         const int32_t* tiles_per_gauss, const int32_t* cum_tiles, const float* rows, const int32_t* row_base,
+                                         const uint8_t* qmask, float* v_means2d_abs, float beta1, float beta2, float eps, const float* hyper_dev,
+                                         int64_t* applied_dev, float* max_radii, float* grad_norm_accum, float* counts,
+                                         const float* sh_jac, int scale_reg, float max_ratio, float lambda, int budget, double a, double b,
+                                         const float* v_depths) {
+    GS_REQUIRE(((uintptr_t)params & 3) == 0, "params must be 4-byte aligned");
+    GS_REQUIRE((scale_reg == 0 || scale_reg == 1) && (budget == 0 || budget == 1), "scale_reg and budget are 0 or 1");
+    GS_REQUIRE(a == a && b == b, "a or b is NaN");
+    GS_REQUIRE(N == 0 || (v_depths && ((uintptr_t)v_depths & 3) == 0), "v_depths: gs_depth_grads_z' per-Gaussian depth gradients");
+    GS_REQUIRE(current_rounds().phase == 0, "depth gradients are one-round only");
+    return project_bwd_adam(stream, N, K, sh_degree, params, exp_avg, exp_avg_sq, offsets_host, viewmats, Ks, width, height, eps2d,
+                            near_plane, far_plane, radii, colors_post, tiles_per_gauss, cum_tiles, rows, row_base, qmask, v_means2d_abs,
+                            beta1, beta2, eps, hyper_dev, applied_dev, max_radii, grad_norm_accum, counts, sh_jac, (budget ? 2 : 0) | scale_reg,
+                            max_ratio, lambda, a, b, nullptr, v_depths);
 }

@@ -50,6 +50,13 @@ colour affines is sliced and applied to the render in front of the loss (gs_bila
 raw render in place -- through the luminance guide too -- while the slice's adjoint fills the view's slab (gs_bilagrid_bwd), the
 total variation of all grids enters the loss and the gradient (gs_bilagrid_tv), and one launch applies dense Adam to every grid
 under the step guard (gs_bilagrid_adam).  DESIGN.md "Bilateral grids in the captured step".
+
+Supervising depth (`depth=depth_loss.DepthSupervision(lambda_depth, mode)`, `gt_depth=t`, `step(..., gt_depth=t)`): the projection's
+depth rides the blend as a fourth channel (gs_rec_depth, gs_blend_fwd_ch), one pass splits the [H,W,4] buffer into the image the loss
+kernels read and the expected-depth map while it forms the depth term's sums (gs_depth_loss_split / _finish), one pass behind the
+image loss's backward joins v_render and the depth term's gradient into the 4-channel blend backward's inputs (gs_depth_loss_join),
+and the depth lane's gradient reaches the means through gs_depth_grads (gs_depth_grads_z + gs_project_bwd_adam_depth with fuse_adam).
+DESIGN.md "Depth supervision in the captured step".
 """
 from __future__ import annotations
 
@@ -130,7 +137,7 @@ class TrainStepGraph:
                  pose_lr: float = 1e-3, pose_betas: Tuple[float, float] = (0.9, 0.999), pose_eps: float = 1e-15, exposure=None,
                  exposure_lr: float = 1e-2, exposure_betas: Tuple[float, float] = (0.9, 0.999), exposure_eps: float = 1e-15, bilagrid=None,
                  bilagrid_lr: float = 2e-3, bilagrid_betas: Tuple[float, float] = (0.9, 0.999), bilagrid_eps: float = 1e-15,
-                 bilagrid_tv: float = 10.0):
+                 bilagrid_tv: float = 10.0, depth=None, gt_depth: Optional[Tensor] = None):
         """`mcmc`: an `mcmc.MCMCStrategy(model, ..., noise="counter")` -- the step then trains under its Gaussian budget: `mcmc_reg` =
         (opacity_reg, scale_reg) of `strategy.regularization()` enters the loss (out["mcmc_reg"]) and the update, and the strategy's
         noise runs behind Adam inside the step, at noise_lr x the means learning rate of that step.  None (default): nothing changes.
@@ -169,7 +176,36 @@ class TrainStepGraph:
         `runner.bilagrid_lr` is a plain attribute, staged every step outside the graph.  The moments and the step count:
         `runner.bilagrid_state` (`bilagrid.BilagridAdamState`).  `bilagrid.grids` must keep its storage while the runner lives.  Not
         together with `exposure` (`ValueError`): two colour models in front of one loss.  None (default): nothing changes, launch
-        for launch."""
+        for launch.
+        `depth`: a `depth_loss.DepthSupervision(lambda_depth, mode)` -- the step then supervises the expected depth of its render
+        (gsplat's RGB+ED) against `gt_depth`, a float32 [H, W] map on the runner's device in which zero, negative, NaN and inf pixels
+        mean "no measurement": `lambda_depth * depth_loss` joins the loss total (out["depth_loss"]: the unweighted value;
+        out["render_depth"]: the expected-depth map [H, W]), under the step's mask when it has one, and its gradient reaches the means,
+        the opacities and the 2-D geometry through a 4-channel blend backward.  `step(..., gt_depth=t)` hands a step its target: read
+        in place, defaulting to the previous step's, cloned under `copy_targets=True`, and kept by the pending entry so that an
+        overflow recovery replays a skipped step with its own -- the rules of `gt_img`.  `runner.lambda_depth` is a plain attribute,
+        staged every step outside the graph.  Works with a mask, the scale regulariser, `mcmc`, `exposure` and `bilagrid` (which read
+        and write the 3-channel image and its gradient as always).  Refused before any device work: a missing `gt_depth` or one of
+        another shape (`ValueError`); `rounds="on"` (`ValueError`: the depth lane's gather is one-round only; "auto" resolves to off);
+        `poses` (`ValueError`: the camera gradient of the depth term is not formed); `ViewParallelGraphStep` (`ValueError`);
+        `HostFeed` on such a runner (`NotImplementedError`).  None (default): nothing changes, launch for launch."""
+        self.depth = depth
+        if depth is not None:
+            from .depth_loss import MODES, DepthSupervision
+            if not isinstance(depth, DepthSupervision):
+                raise TypeError("TrainStepGraph(depth=...): a depth_loss.DepthSupervision")
+            if poses is not None:
+                raise ValueError("TrainStepGraph: `depth` with `poses` -- the camera gradient of the depth term is not formed inside the "
+                                 "captured step; supervise depth on fixed cameras, or refine poses in the eager loop")
+            if __import__("os").environ.get("GS_TG_ROUNDS", rounds) == "on":
+                raise ValueError("TrainStepGraph: `depth` with rounds='on' -- the depth lane's gradient gather is one-round only "
+                                 "(gs_rec_depth / gs_depth_grads); leave rounds at 'auto' (it resolves to off) or 'off'")
+            if gt_depth is None:
+                raise ValueError("TrainStepGraph(depth=...): the runner needs its first target, gt_depth=[H, W] float32")
+            if tuple(gt_depth.shape) != (int(data["height"]), int(data["width"])):
+                raise ValueError(f"TrainStepGraph(depth=...): gt_depth of shape {tuple(gt_depth.shape)}, expected "
+                                 f"{(int(data['height']), int(data['width']))}")
+            self.lambda_depth, self._depth_mode = float(depth.lambda_depth), MODES.index(depth.mode)
         if bilagrid is not None:
             from .bilagrid import BilagridAdamState, BilateralGrids
             if exposure is not None:
@@ -255,6 +291,8 @@ class TrainStepGraph:
         if rounds not in ("auto", "on", "off"):
             raise ValueError("rounds: 'auto', 'on' or 'off'")
         self.rounds_mode, self.round_fraction = rounds, float(__import__("os").environ.get("GS_TG_ROUND_FRACTION", round_fraction))
+        if depth is not None and rounds == "auto":
+            rounds = self.rounds_mode = "off"   # (one round: see `depth`)
         self.rounds_on = rounds == "on"
         self._live_sum = self._live_n = 0   # tiles the front round left live, summed over the polled steps since the last build
         # "auto" only: the captured step holds the FRONT round alone (gs_rounds_set phase 4), speculating that it finishes every
@@ -318,6 +356,11 @@ class TrainStepGraph:
         self._key = None
         self.confirmed_at_build = 0
         self._last_inputs = (data["w2c"], data["K"], gt_img, mask)
+        if depth is not None:
+            # runner-owned, alive across re-builds: the record {lambda, mode, target address, value, 1 / sum(w)}; the target and the
+            # weight of the step about to be staged: the build's own
+            self._depth_bufs = {"depth_rec": torch.zeros((nat.GS_DEPTH_REC_FLOATS,), dtype=torch.float32, device=self.dev)}
+            self._depth_cur = (self._depth_image(gt_depth, (self.H, self.W)), self.lambda_depth)
         self._build(data, gt_img, mask)
 
     # ------------------------------------------------------------------------------------------ workspace
@@ -393,6 +436,18 @@ class TrainStepGraph:
                 gb["exposed"] = torch.empty((H, W, 3), **f32)
                 gb["bilagrid_partials"] = torch.empty((int(L.gs_bilagrid_partials_doubles(H, W, gx, gy, gl)),), dtype=torch.float64, device=dev)
             b.update(gb)
+        if self.depth is not None:
+            db = self._depth_bufs
+            if "render_colors4" not in db or tuple(db["render_colors4"].shape) != (1, H, W, 4):   # (the first build, or another frame size)
+                db["render_colors4"] = torch.empty((1, H, W, 4), **f32)   # the blend's output; render_colors: its split image
+                db["render_depth"] = torch.empty((H, W), **f32)
+                db["v_colors4"] = torch.empty((H, W, 4), **f32)
+                db["v_alphas"] = torch.empty((H, W), **f32)
+                db["depth_partials"] = torch.empty((int(L.gs_depth_loss_partials_doubles(H, W)),), dtype=torch.float64, device=dev)
+            b.update(db)
+            b["bg4"] = torch.cat([b["bg"], torch.zeros((1, 1), **f32)], dim=1).contiguous()   # background [bg, 0]
+            if self.fuse_adam:   # v_z per Gaussian: gs_depth_grads_z -> gs_project_bwd_adam_depth
+                b["v_depths"] = self._take("v_depths", (N,), torch.float32)
         # {reg, -, fp64 block partials}: the regulariser's value and its reduction scratch (gs_scale_reg)
         b["scale_reg"] = self._take("scale_reg", (int(L.gs_scale_reg_workspace_floats(N)),), torch.float32) if self.scale_reg else None
         if self.mcmc is not None:
@@ -522,6 +577,8 @@ class TrainStepGraph:
         """What is sized by what the forward WALKS: a checkpoint, a sublist block and a descriptor per work unit, the gradient rows."""
         self.cap_units, self.cap_rows = max(int(self.cap_units), 256), max(int(self.cap_rows), 1)
         self._lay(2)
+        if self.depth is not None:
+            self.lease.ckpt_ext()   # (the fourth channel's checkpoint plane follows the walk: allocated here, never inside a capture)
         n_cls = int(nat.lib().gs_unit_classes_ints(self.cap_units, 1, self.W, self.H))   # (gs_blend_bwd's fill classes; GS_BWD_CLASSES=0: off)
         self.buf["unit_cls"] = self._take("unit_cls", (n_cls,), torch.int32, shrink=True) if rendering._BWD_CLASSES else None
 
@@ -591,12 +648,18 @@ class TrainStepGraph:
             t = t.to(device=self.dev, dtype=torch.float32).contiguous()
         return t
 
+    def _depth_image(self, t: Tensor, shape) -> Tensor:
+        """The caller's depth target as the depth kernels read it: `_image`'s conversions, and a 16-byte aligned address (a view
+        into the middle of a buffer is copied once)."""
+        t = self._image(t, shape)
+        return t if t.data_ptr() % 16 == 0 else t.clone()
+
     def _static_w2c(self) -> Tensor:
         """The step's static camera INPUT [1,4,4]: the view matrix the projection reads, or (poses) the raw matrix in the pose record."""
         return self.buf["w2c_raw"] if self.poses is not None else self.buf["viewmats"]
 
     def _stage_inputs(self, t: int, lrs, w2c: Tensor, K: Tensor, gt: Tensor, mask: Optional[Tensor], pose=None, exposure=None,
-                      bilagrid=None):
+                      bilagrid=None, depth=None):
         """Everything that differs from the previous step, in ONE launch on the current stream (gs_step_inputs): Adam's bias
         corrections / learning rates, the camera into the static buffers, and the POINTERS to the target image and mask.
         Returns the (gt, mask) tensors whose pointers went in -- the caller keeps them alive until the step is applied."""
@@ -640,6 +703,9 @@ class TrainStepGraph:
             view, bg_t, bg_lr = bilagrid if bilagrid is not None else self._bilagrid_cur
             nat.check(L.gs_bilagrid_step_inputs(self._st(), int(view), int(self.bilagrid.grids.shape[0]), float(bg_lr), self.bilagrid_betas[0],
                                                 self.bilagrid_betas[1], int(bg_t), _p(b["bilagrid_rec"])), "gs_bilagrid_step_inputs")
+        if self.depth is not None:   # the step's depth target (its address: read in place) and the weight as it stood at the call
+            gd, lam = depth if depth is not None else self._depth_cur
+            nat.check(L.gs_depth_step_inputs(self._st(), float(lam), self._depth_mode, _p(gd), _p(b["depth_rec"])), "gs_depth_step_inputs")
         if self.mcmc is not None:   # the step's noise: its strength at the means learning rate this step's Adam uses, its counter, the seed
             nat.check(L.gs_mcmc_step_inputs(self._st(), self.mcmc.noise_lr * float(lrs[self._means_seg]), int(t), self.mcmc.seed,
                                             _p(b["mcmc_rec"])), "gs_mcmc_step_inputs")
@@ -780,6 +846,8 @@ class TrainStepGraph:
         left at "behind both" for the backward (the caller clears it)."""
         L, b = nat.lib(), self.buf
         self._project()
+        if self.depth is not None:   # the depth into lane 3 of the records' colour quad: the blend's fourth channel
+            self._ck(L.gs_rec_depth(self._st(), 1, self.N, 3, _p(b["depths"]), _p(b["radii"]), _p(b["rec"])), "gs_rec_depth")
         if not self.rounds_on:
             self._lists_and_blend("bbox")
             return
@@ -798,6 +866,9 @@ class TrainStepGraph:
         rendering.stage_lists(L, st, lease, (1, self.N, self.tw, self.th), _p(b[bbox]), _p(b["depths"]), self.cap, self.cap_tile, self._ck)
         # (the blend, forward and backward, walks at the LAYOUT's capacities: `_alloc_walk` laid it for the runner's as they stand)
         assert (lease.layout.cap_units, lease.layout.cap_rows) == (self.cap_units, self.cap_rows)
+        if self.depth is not None:
+            rendering.stage_blend_fwd(L, st, lease, 1, self.W, self.H, 4, _p(b["bg4"]), self.cap, _p(b["render_colors4"]), _p(b["render_alphas"]), self._ck)
+            return
         rendering.stage_blend_fwd(L, st, lease, 1, self.W, self.H, 3, _p(b["bg"]), self.cap, _p(b["render_colors"]), _p(b["render_alphas"]), self._ck)
 
     def _guarded(self, enqueue):
@@ -822,6 +893,13 @@ class TrainStepGraph:
         def enqueue():
             self._enqueue_forward()
             lam = float(self.lc.lambda_ssim)
+            slots = _p(b["img_slots"]) if self.has_mask else None
+            if self.depth is not None:
+                # ONE pass over the 4-channel blend: the image the kernels below read (render_colors), the expected-depth map and the
+                # depth term's partials; target, mode and weight come from the record (gs_depth_step_inputs), the mask from its slot
+                self._ck(L.gs_depth_loss_split(st, H, W, _p(b["depth_rec"]), 0.0, 0, None, None, slots, _p(b["render_colors4"]),
+                                               _p(b["render_alphas"]), _p(b["render_colors"]), _p(b["render_depth"]), _p(b["depth_partials"])),
+                         "gs_depth_loss_split")
             img = b["render_colors"]
             if self.exposure is not None:   # the loss reads the view's affine of the render; the blend backward keeps the raw render
                 n_exp, tab, img = int(self.exposure.affine.shape[0]), _p(self.exposure.affine.data), b["exposed"]
@@ -833,6 +911,9 @@ class TrainStepGraph:
                                              _p(b["render_colors"]), _p(img)), "gs_bilagrid_apply")
             self._ck(L.gs_l1_ssim_fwd_slots(st, H, W, lam, _p(img), _p(b["img_slots"]), int(self.has_mask), 1, _p(b["loss_ws"]),
                                              _p(b["loss3"])), "gs_l1_ssim_fwd_slots")
+            if self.depth is not None:   # value and 1 / sum(w) into the record; lambda_depth * value behind the image loss in the total
+                self._ck(L.gs_depth_loss_finish(st, H, W, _p(b["depth_rec"]), 0.0, 1, _p(b["depth_partials"]), _p(b["loss3"])),
+                         "gs_depth_loss_finish")
             self._ck(L.gs_l1_ssim_bwd_slots(st, H, W, lam, _p(img), _p(b["img_slots"]), 1, _p(b["loss_ws"]),
                                              _p(b["one"]), _p(b["v_render"])), "gs_l1_ssim_bwd_slots")
             if self.exposure is not None:   # v_render: dL/d exposed -> dL/d render in place; the 12 sums of the view's row
@@ -848,8 +929,17 @@ class TrainStepGraph:
                 self._mcmc_reg(None, None)
             if self.bilagrid is not None and self.fuse_adam:   # the total variation behind both: the total sums scale, budget, TV
                 self._bilagrid_tv()
-            rendering.stage_blend_bwd(L, st, self.lease, 1, W, H, 3, _p(b["render_colors"]), _p(b["render_alphas"]), _p(b["v_render"]), None,
-                                      _p(b["unit_cls"]), self._ck)
+            if self.depth is not None:
+                # ONE pass: v_render and the depth term's gradient (through the expected depth's quotient) into the 4-channel blend
+                # backward's v_colors and v_alphas
+                self._ck(L.gs_depth_loss_join(st, H, W, _p(b["depth_rec"]), 0.0, 0, None, None, slots, _p(b["render_colors4"]),
+                                              _p(b["render_alphas"]), _p(b["render_depth"]), _p(b["v_render"]), _p(b["v_colors4"]),
+                                              _p(b["v_alphas"])), "gs_depth_loss_join")
+                rendering.stage_blend_bwd(L, st, self.lease, 1, W, H, 4, _p(b["render_colors4"]), _p(b["render_alphas"]), _p(b["v_colors4"]),
+                                          _p(b["v_alphas"]), _p(b["unit_cls"]), self._ck)
+            else:
+                rendering.stage_blend_bwd(L, st, self.lease, 1, W, H, 3, _p(b["render_colors"]), _p(b["render_alphas"]), _p(b["v_render"]), None,
+                                          _p(b["unit_cls"]), self._ck)
             self._enqueue_rest(st)
         self._guarded(enqueue)
 
@@ -879,7 +969,22 @@ class TrainStepGraph:
                     float(opt.defaults["eps"]), _p(b["hyper"]), _p(b["applied"]), _p(m.max_radii),
                     _p(m.grad_norm_accum), _p(m.collecting_counts), _p(b["sh_jac"]))
             args = head + (_p(b["rows"]), _p(b["row_base"]), _p(b["qmask"])) + tail
-            if poses:   # (the sums in place of rows, row_base, qmask; one entry for the three variants)
+            if self.depth is not None:
+                # v_z per Gaussian from lane 3 of its gradient rows (gs_depth_grads' gather), then the fused kernel adds v_z times row 2
+                # of the view matrix to the means gradient where gs_depth_grads would: the same update bit for bit
+                self._ck(L.gs_depth_grads_z(st, 1, N, 3, _p(b["radii"]), self._tpg(), _p(b["cum_tiles"]), _p(b["rows"]), _p(b["row_base"]),
+                                             _p(b["qmask"]), _p(b["v_depths"])), "gs_depth_grads_z")
+                bud_a, bud_b = self.mcmc_reg if self.mcmc is not None else (0.0, 0.0)
+                self._ck(L.gs_project_bwd_adam_depth(st, N, self.K, int(m.active_sh_degree), _p(opt.flat_param), _p(opt.exp_avg),
+                                                      _p(opt.exp_avg_sq), offs, _p(b["viewmats"]), _p(b["Ks"]), W, H, EPS2D, NEAR_PLANE,
+                                                      FAR_PLANE, _p(b["radii"]), _p(b["colors_post"]), self._tpg(), _p(b["cum_tiles"]),
+                                                      _p(b["rows"]), _p(b["row_base"]), _p(b["qmask"]), _p(b["v_abs"]), float(b1), float(b2),
+                                                      float(opt.defaults["eps"]), _p(b["hyper"]), _p(b["applied"]), _p(m.max_radii),
+                                                      _p(m.grad_norm_accum), _p(m.collecting_counts), _p(b["sh_jac"]), int(self.scale_reg),
+                                                      self.max_scale_ratio if self.scale_reg else 0.0,
+                                                      self.lambda_scale if self.scale_reg else 0.0, int(self.mcmc is not None), bud_a, bud_b,
+                                                      _p(b["v_depths"])), "gs_project_bwd_adam_depth")
+            elif poses:   # (the sums in place of rows, row_base, qmask; one entry for the three variants)
                 self._ck(L.gs_project_bwd_adam_sums(*head, _p(b["pose_row_sums"]), *tail, int(self.scale_reg),
                                                      self.max_scale_ratio if self.scale_reg else 0.0, self.lambda_scale if self.scale_reg else 0.0,
                                                      int(self.mcmc is not None), *(self.mcmc_reg if self.mcmc is not None else (0.0, 0.0))),
@@ -905,6 +1010,9 @@ class TrainStepGraph:
             else:
                 self._ck(L.gs_project_bwd(*bwd_args, None, None, None, None, _p(m.logit_opacities), 1, _p(b["sh_jac"]), None, None, None),
                          "gs_project_bwd")
+            if self.depth is not None:   # the depth lane's gradient onto the means', in front of the regularisers
+                self._ck(L.gs_depth_grads(st, 1, N, 3, _p(m.means), _p(b["viewmats"]), _p(b["radii"]), self._tpg(), _p(b["cum_tiles"]),
+                                           _p(b["rows"]), _p(b["row_base"]), _p(b["qmask"]), _p(g["means"]), None, None, None), "gs_depth_grads")
             if self.scale_reg:   # value into the loss total, gradient onto the render's
                 self._scale_reg(g["log_scales"])
             if self.mcmc is not None:
@@ -1024,6 +1132,8 @@ class TrainStepGraph:
         self.confirmed_at_build = self.confirmed
 
     # ------------------------------------------------------------------------------------------ stepping
+    _ENTRY_DEPTH = 13   # where a pending entry keeps (depth target, lambda_depth): behind pose [10], exposure [11], bilagrid [12]
+
     def _issue(self, entry):
         t, lrs, w2c, K, gt, mask, ready = entry[:7]
         conv = entry[7] if len(entry) > 7 else None
@@ -1031,6 +1141,7 @@ class TrainStepGraph:
         pose = entry[10] if len(entry) > 10 else None   # (view index, pose step count): poses
         expo = entry[11] if len(entry) > 11 else None   # (view index, exposure step count, learning rate): exposure
         bgrid = entry[12] if len(entry) > 12 else None  # (view index, the grids' step count, learning rate): bilagrid
+        dep = entry[self._ENTRY_DEPTH] if len(entry) > self._ENTRY_DEPTH else None   # (target, lambda_depth): depth
         # The step waits for the caller's stream on entry: that orders it behind pending WRITERS of the inputs handed in and
         # behind pending READERS of what the replay overwrites -- the static outputs the previous `step()` returned, the
         # parameters and moments (fused Adam), the statistics.  (Round 3 skipped the wait for steps that take no input from
@@ -1048,7 +1159,7 @@ class TrainStepGraph:
                 for ev in (after if isinstance(after, (list, tuple)) else (after,)):
                     self.stream.wait_event(ev)
                 entry[8] = None
-            entry[4], entry[5] = self._stage_inputs(t, lrs, w2c, K, gt, mask, pose, expo, bgrid)   # (the tensors the step reads: kept by the entry)
+            entry[4], entry[5] = self._stage_inputs(t, lrs, w2c, K, gt, mask, pose, expo, bgrid, dep)   # (the tensors the step reads: kept by the entry)
             if self.graph is not None:
                 self.graph.replay()
             else:
@@ -1059,7 +1170,7 @@ class TrainStepGraph:
 
     def step(self, data: Optional[Dict[str, Any]] = None, gt_img: Optional[Tensor] = None, mask: Optional[Tensor] = None,
              inputs_ready: bool = False, ready_event: Optional["torch.cuda.Event"] = None, host_src=None,
-             view_index: Optional[int] = None):
+             view_index: Optional[int] = None, gt_depth: Optional[Tensor] = None):
         """One training iteration.  `data` / `gt_img` / `mask` default to the previous step's (the camera's static buffers are
         re-used as they are; the target image and the mask are the previous step's own tensors, read in place).  Returns the
         runner's static output tensors (valid until the next `step()` is CALLED: reads
@@ -1076,8 +1187,12 @@ class TrainStepGraph:
         recycles its device slots hands them in, and an overflow recovery replays the step from a FRESH upload of those instead
         of from slots that have been refilled since.  A `data["w2c"]` that requires grad raises `ValueError` (see `__init__`).
         `view_index`: with `poses`, required -- the row of `poses.deltas` that corrects this step's `data["w2c"]` (data=None: the
-        previous step's raw matrix); with `exposure`, required -- the row of `exposure.affine` of this step's target image."""
+        previous step's raw matrix); with `exposure`, required -- the row of `exposure.affine` of this step's target image.
+        `gt_depth`: with `depth`, this step's depth target [H, W] (default: the previous step's; `gt_img`'s lifetime rules)."""
         _refuse_camera_grads(data)
+        depth_on = getattr(self, "depth", None) is not None
+        if gt_depth is not None and not depth_on:
+            raise ValueError("TrainStepGraph.step: gt_depth given, but the runner was built without `depth`")
         exposure, bilagrid = getattr(self, "exposure", None), getattr(self, "bilagrid", None)
         view = _pose_view(self.poses, view_index, exposure, bilagrid)
         W, H = (self.W, self.H) if data is None else (int(data["width"]), int(data["height"]))
@@ -1086,9 +1201,11 @@ class TrainStepGraph:
             size_changed = (W, H) != (self.W, self.H)
             if size_changed:
                 # another frame size: the static image buffers are re-allocated, so the frame must bring its own target
-                if gt_img is None or (self.has_mask and mask is None):
-                    raise ValueError("TrainStepGraph.step: a change of image size needs gt_img (and mask) of the new size")
+                if gt_img is None or (self.has_mask and mask is None) or (depth_on and gt_depth is None):
+                    raise ValueError("TrainStepGraph.step: a change of image size needs gt_img (and mask, and gt_depth) of the new size")
                 cur = (data["w2c"], data["K"], gt_img, mask)
+                if depth_on:   # (validated against the new size before anything is re-built)
+                    self._depth_cur = (self._depth_image(gt_depth, (H, W)), float(self.lambda_depth))
                 self.W, self.H = W, H
             else:
                 cur = self._last_inputs if data is None else (data["w2c"], data["K"], gt_img if gt_img is not None else self._last_inputs[2],
@@ -1145,8 +1262,14 @@ class TrainStepGraph:
         if self.copy_targets and gt_img is not None:   # (a step that re-uses the previous step's tensors re-uses its private copies)
             gt = gt.clone() if gt is gt_in else gt
             mk = (mk.clone() if mk is mk_in else mk) if mk is not None else None
+        gd = gd_in = None
+        if depth_on:
+            gd_in = self._depth_cur[0] if gt_depth is None else gt_depth   # (the previous step's own tensor, by reference)
+            gd = self._depth_image(gd_in, (self.H, self.W))
+            if self.copy_targets and gt_depth is not None and gd is gd_in:
+                gd = gd.clone()
         conv = None
-        if gt is not gt_in or mk is not mk_in:
+        if gt is not gt_in or mk is not mk_in or gd is not gd_in:
             # a conversion (dtype / device / layout) or a private copy ran on the CALLER's stream just now: the runner's stream
             # waits for exactly that, whatever `inputs_ready` promises about the caller's own work
             conv = torch.cuda.Event()
@@ -1173,6 +1296,10 @@ class TrainStepGraph:
                 self.bilagrid_state.step += 1
                 self._bilagrid_cur = (view, self.bilagrid_state.step, float(self.bilagrid_lr))
                 entry.extend([None, self._bilagrid_cur])
+        if depth_on:   # the target and the weight as it stands at this call travel with the step: entry[13]
+            self._depth_cur = (gd, float(self.lambda_depth))
+            assert len(entry) <= self._ENTRY_DEPTH, len(entry)   # (a later optional slot goes behind this one, never in front)
+            entry.extend([None] * (self._ENTRY_DEPTH - len(entry)) + [self._depth_cur])
         self._issue(entry)
         if self.issued % self.check_every == 0:
             self._poll(block=False)
@@ -1191,6 +1318,9 @@ class TrainStepGraph:
             outs["exposed"] = b["exposed"]          # the image the loss read: the slice of the view's grid applied to render_img
             outs["v_grids"] = b["v_grids"]          # dL / d bilagrid.grids of the step, dense: the view's slab + the TV gradient
             outs["bilagrid_tv"] = b["bilagrid_tv"]  # the total variation of all grids (the loss total holds bilagrid_tv times it)
+        if depth_on:
+            outs["render_depth"] = b["render_depth"]                       # [H, W]: the expected depth of the step's render
+            outs["depth_loss"] = b["depth_rec"][nat.GS_DEPTH_REC_VALUE]    # 0-d, unweighted (the loss total holds lambda_depth times it)
         return TrainStepGraph._StepOutputs(self, outs, lazy=self.handback == "lazy")
 
     def _poll(self, block: bool):
@@ -1244,6 +1374,8 @@ class TrainStepGraph:
             self._exposure_cur = first[11]
         if self.bilagrid is not None:
             self._bilagrid_cur = first[12]
+        if self.depth is not None:
+            self._depth_cur = first[self._ENTRY_DEPTH]   # (the probe and the warm-up of the re-build read the first skipped step's own target)
         # (min_cap >= 1 forces a fresh probe even when only a coarse-bin capacity was exceeded and the list sizes read 0)
         self._build({"w2c": first[2], "K": first[3]}, first[4], first[5], min_cap=max(n_isects, 1), min_cap_tile=max_tile, min_walk=walk)
         for e in redo:
@@ -1275,6 +1407,8 @@ class TrainStepGraph:
             extra.update(exposure=True, exposure_lr=self.exposure_lr, exposure_steps=self.exposure_state.step)
         if self.bilagrid is not None:
             extra.update(bilagrid=True, bilagrid_lr=self.bilagrid_lr, bilagrid_tv=self.bilagrid_tv, bilagrid_steps=self.bilagrid_state.step)
+        if self.depth is not None:
+            extra.update(depth=True, lambda_depth=self.lambda_depth, depth_mode=self.depth.mode)
         return dict(self.stats, **extra, binning=self.binning, probed_isects=self.probed[0], probed_longest_list=self.probed[1],
                     probed_coarse_entries=getattr(self, "probed_coarse", (0, 0))[0] if self.binning == "bins" else 0,
                     capacity_isects=self.cap, capacity_tile_list=self.cap_tile, capacity_work_units=self.cap_units,
@@ -1312,6 +1446,9 @@ class ViewParallelGraphStep(TrainStepGraph):
         if kw.get("bilagrid") is not None:
             raise ValueError("ViewParallelGraphStep: no `bilagrid` -- bilateral grids inside the captured step are single-GPU "
                              "(TrainStepGraph(bilagrid=...)): the view-parallel step's loss reads each rank's raw render")
+        if kw.get("depth") is not None:
+            raise ValueError("ViewParallelGraphStep: no `depth` -- depth supervision inside the captured step is single-GPU "
+                             "(TrainStepGraph(depth=...)): the view-parallel exchange carries three colour channels")
         if kw.get("mcmc") is not None:
             raise ValueError("ViewParallelGraphStep: no `mcmc` -- MCMCStrategy refuses torch.distributed (the replicas would need "
                              "broadcast draws)")
@@ -1419,6 +1556,9 @@ class HostFeed:
     def __init__(self, runner: "TrainStepGraph", n_slots: int = 2, inputs_ready: bool = False):
         """`inputs_ready`: the caller's promise of `TrainStepGraph.step` (its stream holds no pending reader of the outputs, the
         parameters or the statistics) -- the uploads themselves are ordered by events either way."""
+        if getattr(runner, "depth", None) is not None:
+            raise NotImplementedError("HostFeed: a runner built with `depth` -- the feed uploads image, mask and camera, not a depth "
+                                      "target; hand device depth maps to runner.step(..., gt_depth=...)")
         self.r, self.n = runner, max(2, int(n_slots))
         self.inputs_ready = bool(inputs_ready)
         dev = runner.dev

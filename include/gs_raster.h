@@ -973,6 +973,79 @@ int gs_bilagrid_tv(void* stream, int n_views, int grid_x, int grid_y, int grid_l
 int gs_bilagrid_adam(void* stream, int64_t numel, const float* rec_dev, float* grids, float* exp_avg, float* exp_avg_sq,
                      const float* v_grids, float beta1, float beta2, float eps);
 
+/* ---- Depth supervision (DESIGN.md "Depth supervision in the captured step"): depth_loss.depth_loss / DepthSupervision -- gsplat's
+ * trainer's depth term on the expected depth of the RGB+ED render.  For a frame of P = height * width pixels, the math of
+ * csrc/gs_depth_loss.h (shared with the host tests):
+ *     d = acc_z / max(alpha, 1e-10)                               the prediction (gs_math.h expected_depth)
+ *     valid = t > 0 and t finite                                  the target t[height][width] f32: NaN, inf, 0 and negatives = none
+ *     w = valid * (1 - m)                                         m: the mask at the pixel (1 excludes it), 0 without a mask
+ *     e = d - t  (GS_DEPTH_MODE_DEPTH)   or   disp(d) - 1 / t  (GS_DEPTH_MODE_DISPARITY),   disp(d) = d > 0 ? 1 / d : 0
+ *     value = sum(w |e|) / sum(w),   exactly 0 when sum(w) == 0
+ *     d value / d d = w sign(e) / sum(w) * {depth: 1; disparity: d > 0 ? -1 / d^2 : 0},   sign(0) = 0
+ * Every product w |e| is formed exactly in fp64 from its fp32 factors; the two sums are fp64 in a fixed order -- per thread over
+ * its grid-stride pixels, over the wave, over the block's waves, then one pass over the per-block
+ * partials[gs_depth_loss_partials_doubles(height, width)] -- and value and 1 / sum(w) are rounded to fp32 once.  No atomics: two
+ * runs give the same bits.  A frame without a valid pixel gives value 0 and gradients 0, never a NaN.
+ * rec_dev[GS_DEPTH_REC_FLOATS] f32, 16-byte aligned: {lambda_depth, the bits of the int32 mode, the target's 64-bit address (two
+ * words), value, 1 / sum(w), 0, 0}.  Images, the target and the depth maps are 16-byte aligned, the mask 4-byte; anything else, a
+ * null pointer, an output that aliases an input or an unknown mode is GS_ERR_ARG before any launch.  Every kernel that runs INSIDE
+ * a step -- split, finish, join, fwd, bwd, gs_depth_grads_z, gs_project_bwd_adam_depth -- honours the step guard: a voided step
+ * leaves value and 1 / sum(w), the images and the gradients as they were.
+ * gs_depth_step_inputs: a one-wave launch in front of a step, outside its guarded sequence (as gs_exposure_step_inputs: the values
+ *   travel as kernel arguments; four lanes write), that writes words 0-3 of the record.  It does NOT look at the guard: a voided
+ *   step is replayed behind a staging launch of its own.  The target is read IN PLACE by the kernels below: it stays alive until
+ *   they have run.
+ * gs_depth_loss_split / _fwd / _join / _bwd take {lambda_depth, mode, target} from the record when `target` is NULL (the captured
+ *   step) and from their arguments otherwise; the mask is slot 1 of img_slots (gs_step_inputs' {gt, mask} addresses) when img_slots
+ *   is non-NULL, else `mask` (NULL: none).
+ * gs_depth_loss_split: ONE pass over the 4-channel blend colors4[height][width][4] = {r, g, b, acc_z} and alphas: image3 = the
+ *   first three channels bit for bit, depth = d, and the partials.
+ * gs_depth_loss_finish: a one-block launch behind it -- in the step behind gs_l1_ssim_fwd*, which writes loss3 -- that writes value
+ *   and 1 / sum(w) into the record and (loss3 non-NULL) loss3[2] += lambda_depth * value, the product rounded on its own (as
+ *   gs_scale_reg enters the total); lambda_depth from the record when `staged` is 1.
+ * gs_depth_loss_fwd: the same sums and the finish from a depth map (the eager form: depth = what gs_expected_depth_fwd returned), mode and target
+ *   by value; the same pixel-to-thread assignment, hence the same bits.
+ * gs_depth_loss_join: ONE pass behind the image loss's backward: v_colors4[p] = {v_render[p], v_acc} and v_alphas[p] = v_alpha with
+ *   (v_acc, v_alpha) = expected_depth_vjp(lambda_depth / sum(w) * d value / d d ...), the gradients gs_blend_bwd_ch takes at 4
+ *   channels.  Reads value's 1 / sum(w) from the record.
+ * gs_depth_loss_bwd: v_depth[p] = v_loss[0] * d value / d d (v_loss: the upstream gradient, one float on the device).
+ * gs_depth_grads_z: gs_depth_grads' fixed-order gather alone: v_depths[C][N] = the sum of lane `lane` of the colour quad of each
+ *   Gaussian's gradient rows, 0 for culled ones; no gradient is touched.  One round only, like gs_depth_grads.
+ * gs_project_bwd_adam_depth: gs_project_bwd_adam / _reg / _mcmc (scale_reg, budget: 0 or 1, with their parameters) with
+ *   v_depths[N] * viewmats[0][2][0:3] added to the means gradient behind the projection's VJP (gs_math.h depth_vjp_mean) -- the
+ *   same update, bit for bit, as gs_project_bwd, gs_depth_grads onto its v_means, the regularisers, gs_adam_step_dev. */
+#define GS_DEPTH_MODE_DEPTH 0
+#define GS_DEPTH_MODE_DISPARITY 1
+#define GS_DEPTH_REC_FLOATS 8
+#define GS_DEPTH_REC_LAMBDA 0
+#define GS_DEPTH_REC_MODE 1
+#define GS_DEPTH_REC_TARGET 2
+#define GS_DEPTH_REC_VALUE 4
+#define GS_DEPTH_REC_INV_W 5
+int gs_depth_step_inputs(void* stream, float lambda_depth, int mode, const float* target, float* rec_dev);
+size_t gs_depth_loss_partials_doubles(int height, int width);
+int gs_depth_loss_split(void* stream, int height, int width, float* rec_dev, float lambda_depth, int mode, const float* target,
+                        const float* mask, const int64_t* img_slots, const float* colors4, const float* alphas, float* image3,
+                        float* depth, double* partials);
+int gs_depth_loss_finish(void* stream, int height, int width, float* rec_dev, float lambda_depth, int staged, const double* partials,
+                         float* loss3);
+int gs_depth_loss_fwd(void* stream, int height, int width, float* rec_dev, int mode, const float* target, const float* mask,
+                      const float* depth, double* partials);
+int gs_depth_loss_join(void* stream, int height, int width, const float* rec_dev, float lambda_depth, int mode, const float* target,
+                       const float* mask, const int64_t* img_slots, const float* colors4, const float* alphas, const float* depth,
+                       const float* v_render, float* v_colors4, float* v_alphas);
+int gs_depth_loss_bwd(void* stream, int height, int width, const float* rec_dev, int mode, const float* target, const float* mask,
+                      const float* depth, const float* v_loss, float* v_depth);
+int gs_depth_grads_z(void* stream, int C, int64_t N, int lane, const int32_t* radii, const int32_t* tiles_per_gauss,
+                     const int32_t* cum_tiles, const float* rows, const int32_t* row_base, const uint8_t* qmask, float* v_depths);
+int gs_project_bwd_adam_depth(void* stream, int64_t N, int K, int sh_degree, float* params, float* exp_avg, float* exp_avg_sq,
+                              const int64_t* offsets_host, const float* viewmats, const float* Ks, int width, int height, float eps2d,
+                              float near_plane, float far_plane, const int32_t* radii, const float* colors_post,
+                              const int32_t* tiles_per_gauss, const int32_t* cum_tiles, const float* rows, const int32_t* row_base,
+                              const uint8_t* qmask, float* v_means2d_abs, float beta1, float beta2, float eps, const float* hyper_dev,
+                              int64_t* applied_dev, float* max_radii, float* grad_norm_accum, float* counts, const float* sh_jac,
+                              int scale_reg, float max_ratio, float lambda, int budget, double a, double b, const float* v_depths);
+
 #ifdef __cplusplus
 }
 #endif
