@@ -80,6 +80,59 @@ GS_HD float r_max(float x, float y) { return fmaxf(x, y); }
 GS_HD double r_max(double x, double y) { return fmax(x, y); }
 GS_HD float r_min(float x, float y) { return fminf(x, y); }
 GS_HD double r_min(double x, double y) { return fmin(x, y); }
+GS_HD float r_atan2(float y, float x) { return atan2f(y, x); }
+GS_HD double r_atan2(double y, double x) { return atan2(y, x); }
+
+// Camera models (include/gs_raster.h: GS_CAMERA_*), a compile-time parameter of the projection chain and its VJP.  Only the map
+// camera space -> pixel and its Jacobian J differ: the mean's way to camera space, the near/far cull on z, cov2 = J cov_c J^T +
+// eps2d I and everything behind cov2 are the same for all three (DESIGN.md "Camera models").
+//   pinhole: (fx x / z + cx, fy y / z + cy), J with the FOV clamp (the code below, operation for operation what it was)
+//   ortho:   (fx x + cx, fy y + cy), J = [[fx, 0, 0], [0, fy, 0]] constant, no clamp
+//   fisheye: ideal equidistant, (fx x k + cx, fy y k + cy) with k = theta / r, theta = atan2(r, z), r^2 = x^2 + y^2; no clamp
+constexpr int kCamPinhole = 0, kCamOrtho = 1, kCamFisheye = 2;
+// The fisheye again, its radial terms selected instead of branched to (fisheye_terms<T, true>: the same formulas, both evaluated).
+// Not a model of the ABI: the form of ONE kernel instantiation, for which the compiler otherwise reserves a stack object it never
+// accesses (gs_project.hip: project_bwd_cm_kernel).
+constexpr int kCamFisheyeSelect = 3;
+
+// The radial terms of the equidistant fisheye at the camera-space point (x, y, z), d^2 = r^2 + z^2:
+//   k = theta / r            (the mean map's factor;  dk/dx = g x, dk/dy = g y, dk/dz = -e)
+//   e = 1 / d^2              (de/d(x, y, z) = -2 e^2 (x, y, z))
+//   g = (z e - k) / r^2      (J's second-order factor;  dg/dx = h x, dg/dy = h y, dg/dz = 2 e^2)
+//   h = -(2 z e^2 + 3 g) / r^2   (only the VJP needs it)
+// k, g and h are differences of nearly equal numbers when rho = r / z is small -- the closed forms lose eps / rho^2 (g) and
+// eps / rho^4 (h) of their value -- and 0 / 0 on the optical axis.  Below rho^2 < kFisheyeSeriesRho2 (z > 0) g comes from its
+// series in u = rho^2,
+//   g z^3 = G(u) = sum_{n>=0} (-1)^(n+1) 2(n+1)/(2n+3) u^n = -2/3 + 4/5 u - 6/7 u^2 + ...,
+// h from the same coefficients, h = (1/r) dg/dr = 2 G'(u) / z^5 (one Horner pass yields G and G'), and k = z e - g r^2, which
+// cancels nothing there.  Cut after u^7: at the threshold u = 1/256 (rho = 1/16) the first dropped term of G' is 8 (18/19) u^7 =
+// 1e-16, an eps of the sum, and the closed form of h, the worst of the three, is good to 1.25 eps / u^2 = 9e-12 there (fp64).
+// (Eight constants in all: each is an fp64 constant in an SGPR pair of the SGPR-bound fused backward.)
+// A Gaussian ON the axis (u = 0) is an ordinary one: k = 1 / z, g = -2 / (3 z^3), h = 8 / (5 z^5), every gradient finite.
+constexpr double kFisheyeSeriesRho2 = 1.0 / 256;
+template <typename T, bool SELECT = false>
+GS_HD void fisheye_terms(T x, T y, T z, T& k, T& e, T& g, T& h) {
+    const T r2 = x * x + y * y;
+    e = T(1) / (r2 + z * z);
+    const bool series = z > T(0) && r2 < (T)kFisheyeSeriesRho2 * (z * z);
+    T ks = T(0), gs = T(0), hs = T(0);
+    if (SELECT || series) {
+        const T rz = T(1) / z, rz2 = rz * rz, u = series ? r2 * rz2 : T(0);
+        const T c[8] = {T(-2.0 / 3), T(4.0 / 5), T(-6.0 / 7), T(8.0 / 9), T(-10.0 / 11), T(12.0 / 13), T(-14.0 / 15), T(16.0 / 17)};
+        T G = c[7], dG = T(0);
+        for (int i = 6; i >= 0; --i) { dG = dG * u + G; G = G * u + c[i]; }
+        gs = rz * rz2 * G;
+        hs = T(2) * rz * rz2 * rz2 * dG;
+        ks = z * e - gs * r2;
+    }
+    if (SELECT || !series) {   // (SELECT: its 0 / 0 on the axis is computed and never taken)
+        const T r = r_sqrt(r2), rr2 = T(1) / r2;
+        k = r_atan2(r, z) / r;
+        g = (z * e - k) * rr2;
+        h = -(T(2) * z * e * e + T(3) * g) * rr2;
+    }
+    if (series) { k = ks; g = gs; h = hs; }
+}
 
 // Intermediates the VJP needs again; recomputed in backward rather than stored.
 template <typename T>
@@ -92,11 +145,13 @@ struct ProjChainT {
     T tx, ty;                         // clamped x, y used inside J
     int clampx, clampy;               // -1 / 0 / +1
     T j00, j02, j11, j12;
+    T j01, j10;                       // the rest of the 2x3 Jacobian (fisheye; pinhole and ortho: zero, and not touched)
+    T fk;                             // fisheye: k = theta / r of the mean map
     T a, b, c, det;                   // blurred 2-D covariance and determinant
 };
 typedef ProjChainT<preal> ProjChain;
 
-template <typename T>
+template <typename T, int CAM = kCamPinhole>
 GS_HD bool project_chain(const float* mean, const float* quat, const float* scale,
                          const Camera& cam, float eps2d, float near_p, float far_p,
                          ProjChainT<T>& o) {
@@ -141,6 +196,32 @@ GS_HD bool project_chain(const float* mean, const float* quat, const float* scal
     o.cc22 = t20 * V[6] + t21 * V[7] + t22 * V[8];
 
     const T fx = cam.fx, fy = cam.fy;
+    if (CAM != kCamPinhole) {
+        // cov2 = J cov_c J^T + eps2d I with the model's J: constant (ortho), or the full 2x3 one (fisheye)
+        o.clampx = o.clampy = 0; o.tx = o.x; o.ty = o.y;
+        if (CAM == kCamOrtho) {
+            o.j00 = fx; o.j11 = fy; o.j01 = o.j10 = o.j02 = o.j12 = T(0); o.fk = T(1);
+            o.a = fx * fx * o.cc00 + (T)eps2d;
+            o.b = fx * fy * o.cc01;
+            o.c = fy * fy * o.cc11 + (T)eps2d;
+        } else {
+            T e, g, h;
+            fisheye_terms<T, CAM == kCamFisheyeSelect>(o.x, o.y, o.z, o.fk, e, g, h);
+            const T xyg = o.x * o.y * g;
+            o.j00 = fx * (o.fk + o.x * o.x * g); o.j01 = fx * xyg; o.j02 = -fx * o.x * e;
+            o.j10 = fy * xyg; o.j11 = fy * (o.fk + o.y * o.y * g); o.j12 = -fy * o.y * e;
+            // J cov_c (2x3), then its products with J's rows
+            const T m00 = o.j00 * o.cc00 + o.j01 * o.cc01 + o.j02 * o.cc02, m01 = o.j00 * o.cc01 + o.j01 * o.cc11 + o.j02 * o.cc12,
+                    m02 = o.j00 * o.cc02 + o.j01 * o.cc12 + o.j02 * o.cc22;
+            const T m10 = o.j10 * o.cc00 + o.j11 * o.cc01 + o.j12 * o.cc02, m11 = o.j10 * o.cc01 + o.j11 * o.cc11 + o.j12 * o.cc12,
+                    m12 = o.j10 * o.cc02 + o.j11 * o.cc12 + o.j12 * o.cc22;
+            o.a = m00 * o.j00 + m01 * o.j01 + m02 * o.j02 + (T)eps2d;
+            o.b = m00 * o.j10 + m01 * o.j11 + m02 * o.j12;
+            o.c = m10 * o.j10 + m11 * o.j11 + m12 * o.j12 + (T)eps2d;
+        }
+        o.det = o.a * o.c - o.b * o.b;
+        return true;
+    }
     T limx, limy;
     fov_limits<T>(cam, limx, limy);
     const T rz = T(1) / o.z;
@@ -172,7 +253,7 @@ GS_HD void tile_rect(T mx, T my, int radius, int tile, int tw, int th, int& x0, 
 
 // Appendix A.1: full forward projection of one Gaussian for one camera.  With tile > 0 the tile rectangle of the
 // 3-sigma square is taken from the unrounded centre as well (s.x0..s.y1).
-template <typename T>
+template <typename T, int CAM = kCamPinhole>
 GS_HD Splat2D project_gaussian_t(const float* mean, const float* quat, const float* scale,
                                  const Camera& cam, int W, int H, float eps2d, float near_p,
                                  float far_p, float radius_clip, int tile, int tw, int th) {
@@ -180,13 +261,16 @@ GS_HD Splat2D project_gaussian_t(const float* mean, const float* quat, const flo
     s.mx = s.my = s.depth = s.A = s.B = s.C = s.cxx = s.cyy = 0.f;
     s.radius = 0; s.x0 = s.x1 = s.y0 = s.y1 = 0;
     ProjChainT<T> p;
-    if (!project_chain<T>(mean, quat, scale, cam, eps2d, near_p, far_p, p)) return s;
+    if (!project_chain<T, CAM>(mean, quat, scale, cam, eps2d, near_p, far_p, p)) return s;
     if (!(p.det > T(0))) return s;
     const T mid = T(0.5) * (p.a + p.c);
     const T lam = mid + r_sqrt(r_max((T)kRadiusDiscFloor, mid * mid - p.det));
     const T radius = r_ceil(T(3) * r_sqrt(lam));
     if (radius <= (T)radius_clip) return s;
-    const T mx = (T)cam.fx * p.x / p.z + (T)cam.cx, my = (T)cam.fy * p.y / p.z + (T)cam.cy;
+    T mx, my;
+    if (CAM == kCamPinhole) { mx = (T)cam.fx * p.x / p.z + (T)cam.cx; my = (T)cam.fy * p.y / p.z + (T)cam.cy; }
+    else if (CAM == kCamOrtho) { mx = (T)cam.fx * p.x + (T)cam.cx; my = (T)cam.fy * p.y + (T)cam.cy; }
+    else { mx = (T)cam.fx * p.x * p.fk + (T)cam.cx; my = (T)cam.fy * p.y * p.fk + (T)cam.cy; }
     if (mx + radius <= T(0) || mx - radius >= (T)W || my + radius <= T(0) || my - radius >= (T)H) return s;
     const T rdet = T(1) / p.det;
     s.mx = (float)mx; s.my = (float)my; s.depth = (float)p.z;
@@ -201,6 +285,13 @@ GS_HD Splat2D project_gaussian(const float* mean, const float* quat, const float
                                const Camera& cam, int W, int H, float eps2d, float near_p,
                                float far_p, float radius_clip, int tile = 0, int tw = 0, int th = 0) {
     return project_gaussian_t<preal>(mean, quat, scale, cam, W, H, eps2d, near_p, far_p, radius_clip, tile, tw, th);
+}
+// ... under the camera model CAM (CAM = kCamPinhole is project_gaussian itself)
+template <int CAM>
+GS_HD Splat2D project_gaussian_cm(const float* mean, const float* quat, const float* scale,
+                                  const Camera& cam, int W, int H, float eps2d, float near_p,
+                                  float far_p, float radius_clip, int tile = 0, int tw = 0, int th = 0) {
+    return project_gaussian_t<preal, CAM>(mean, quat, scale, cam, W, H, eps2d, near_p, far_p, radius_clip, tile, tw, th);
 }
 
 // Minimum of the positive-definite form a dx^2 + b dx dy + c dy^2 over the axis-aligned
@@ -439,7 +530,9 @@ GS_HD void sh_dir_term_jac(int degree, const float* G, const float* rgb, const f
 // type -- v_t = v_pc (the camera-space gradient of the mean, formed here and otherwise only rotated back to world space) and
 // v_A = v_pc mean^T + 2 v_covc A Sigma, Sigma = M M^T (U = v_covc A is formed for v_cov anyway) -- SET, not added: the caller
 // sums them over the Gaussians of a camera.
-template <typename T, bool CAMG>
+// CAM: the camera model.  Everything but the step from (v_means2d, G = v_cov2) to the camera-space gradient of the mean v_pc = (vx, vy, vz)
+// and to v_covc = J^T G J is the same for all models -- in particular v_t = v_pc and v_A = v_pc mean^T + 2 v_covc A Sigma.
+template <typename T, bool CAMG, int CAM = kCamPinhole>
 GS_HD void project_vjp_impl(const float* mean, const float* scale, const Camera& cam, const ProjChainT<T>& p, float v_mx_f,
                             float v_my_f, float vA_f, float vB_f, float vC_f, float v_depth_f, float* v_mean,
                             float* v_quat, float* v_scale, T* v_A, T* v_t) {
@@ -458,26 +551,60 @@ GS_HD void project_vjp_impl(const float* mean, const float* scale, const Camera&
     const T g00 = -(xv00 * X00 + xv01 * X01);
     const T g01 = -(xv00 * X01 + xv01 * X11);
     const T g11 = -(xv10 * X01 + xv11 * X11);
-    const T j00 = p.j00, j02 = p.j02, j11 = p.j11, j12 = p.j12;
-    // GJ (2x3)
-    const T a0 = g00 * j00, a1 = g01 * j11, a2 = g00 * j02 + g01 * j12;
-    const T b0 = g01 * j00, b1 = g11 * j11, b2 = g01 * j02 + g11 * j12;
-    // v_covc = J^T G J (symmetric)
-    const T vc00 = j00 * a0, vc01 = j00 * a1, vc02 = j00 * a2;
-    const T vc11 = j11 * b1, vc12 = j11 * b2, vc22 = j02 * a2 + j12 * b2;
-    // v_J = 2 (GJ) covc ; only the four non-constant entries
-    const T vJ00 = T(2) * (a0 * p.cc00 + a1 * p.cc01 + a2 * p.cc02);
-    const T vJ02 = T(2) * (a0 * p.cc02 + a1 * p.cc12 + a2 * p.cc22);
-    const T vJ11 = T(2) * (b0 * p.cc01 + b1 * p.cc11 + b2 * p.cc12);
-    const T vJ12 = T(2) * (b0 * p.cc02 + b1 * p.cc12 + b2 * p.cc22);
-    const T rz = T(1) / p.z, rz2 = rz * rz, rz3 = rz2 * rz;
-    T vx = T(0), vy = T(0);
-    T vz = -vJ00 * fx * rz2 - vJ11 * fy * rz2 + T(2) * vJ02 * fx * p.tx * rz3 + T(2) * vJ12 * fy * p.ty * rz3;
-    const T v_tx = -vJ02 * fx * rz2, v_ty = -vJ12 * fy * rz2;
-    if (p.clampx == 0) vx += v_tx; else vz += v_tx * (p.clampx > 0 ? limx : -limx);
-    if (p.clampy == 0) vy += v_ty; else vz += v_ty * (p.clampy > 0 ? limy : -limy);
-    vx += v_mx * fx * rz; vy += v_my * fy * rz;
-    vz += -(v_mx * fx * p.x + v_my * fy * p.y) * rz2 + v_depth;
+    T vc00, vc01, vc02, vc11, vc12, vc22, vx, vy, vz;
+    if (CAM == kCamPinhole) {
+        const T j00 = p.j00, j02 = p.j02, j11 = p.j11, j12 = p.j12;
+        // GJ (2x3)
+        const T a0 = g00 * j00, a1 = g01 * j11, a2 = g00 * j02 + g01 * j12;
+        const T b0 = g01 * j00, b1 = g11 * j11, b2 = g01 * j02 + g11 * j12;
+        // v_covc = J^T G J (symmetric)
+        vc00 = j00 * a0; vc01 = j00 * a1; vc02 = j00 * a2;
+        vc11 = j11 * b1; vc12 = j11 * b2; vc22 = j02 * a2 + j12 * b2;
+        // v_J = 2 (GJ) covc ; only the four non-constant entries
+        const T vJ00 = T(2) * (a0 * p.cc00 + a1 * p.cc01 + a2 * p.cc02);
+        const T vJ02 = T(2) * (a0 * p.cc02 + a1 * p.cc12 + a2 * p.cc22);
+        const T vJ11 = T(2) * (b0 * p.cc01 + b1 * p.cc11 + b2 * p.cc12);
+        const T vJ12 = T(2) * (b0 * p.cc02 + b1 * p.cc12 + b2 * p.cc22);
+        const T rz = T(1) / p.z, rz2 = rz * rz, rz3 = rz2 * rz;
+        vx = T(0); vy = T(0);
+        vz = -vJ00 * fx * rz2 - vJ11 * fy * rz2 + T(2) * vJ02 * fx * p.tx * rz3 + T(2) * vJ12 * fy * p.ty * rz3;
+        const T v_tx = -vJ02 * fx * rz2, v_ty = -vJ12 * fy * rz2;
+        if (p.clampx == 0) vx += v_tx; else vz += v_tx * (p.clampx > 0 ? limx : -limx);
+        if (p.clampy == 0) vy += v_ty; else vz += v_ty * (p.clampy > 0 ? limy : -limy);
+        vx += v_mx * fx * rz; vy += v_my * fy * rz;
+        vz += -(v_mx * fx * p.x + v_my * fy * p.y) * rz2 + v_depth;
+    } else if (CAM == kCamOrtho) {
+        // J = [[fx, 0, 0], [0, fy, 0]] is constant: the conic's gradient reaches the covariance (v_covc = J^T G J) and nothing else
+        vc00 = fx * fx * g00; vc01 = fx * fy * g01; vc11 = fy * fy * g11;
+        vc02 = vc12 = vc22 = T(0);
+        vx = v_mx * fx; vy = v_my * fy; vz = v_depth;
+    } else {
+        const T j00 = p.j00, j01 = p.j01, j02 = p.j02, j10 = p.j10, j11 = p.j11, j12 = p.j12;
+        // GJ (2x3)
+        const T a0 = g00 * j00 + g01 * j10, a1 = g00 * j01 + g01 * j11, a2 = g00 * j02 + g01 * j12;
+        const T b0 = g01 * j00 + g11 * j10, b1 = g01 * j01 + g11 * j11, b2 = g01 * j02 + g11 * j12;
+        // v_covc = J^T G J (symmetric)
+        vc00 = j00 * a0 + j10 * b0; vc01 = j00 * a1 + j10 * b1; vc02 = j00 * a2 + j10 * b2;
+        vc11 = j01 * a1 + j11 * b1; vc12 = j01 * a2 + j11 * b2; vc22 = j02 * a2 + j12 * b2;
+        // v_J = 2 (GJ) covc, all six entries, each times its row's focal length: w = d L / d (J / f)
+        const T w00 = T(2) * fx * (a0 * p.cc00 + a1 * p.cc01 + a2 * p.cc02), w01 = T(2) * fx * (a0 * p.cc01 + a1 * p.cc11 + a2 * p.cc12),
+                w02 = T(2) * fx * (a0 * p.cc02 + a1 * p.cc12 + a2 * p.cc22);
+        const T w10 = T(2) * fy * (b0 * p.cc00 + b1 * p.cc01 + b2 * p.cc02), w11 = T(2) * fy * (b0 * p.cc01 + b1 * p.cc11 + b2 * p.cc12),
+                w12 = T(2) * fy * (b0 * p.cc02 + b1 * p.cc12 + b2 * p.cc22);
+        // sum_ij w_ij (J / f)_ij = k S + g Q - e Lz   with  S = w00 + w11, Q = x^2 w00 + x y (w01 + w10) + y^2 w11, Lz = x w02 + y w12;
+        // the derivatives of k, g, e: fisheye_terms
+        T k, e, g, h;
+        fisheye_terms<T, CAM == kCamFisheyeSelect>(p.x, p.y, p.z, k, e, g, h);
+        const T x = p.x, y = p.y, z = p.z, e2 = e * e;
+        const T S = w00 + w11, wxy = w01 + w10, Q = x * x * w00 + x * y * wxy + y * y * w11, Lz = x * w02 + y * w12;
+        const T radial = g * S + h * Q + T(2) * e2 * Lz;   // the common factor of x and y
+        vx = x * radial + g * (T(2) * x * w00 + y * wxy) - e * w02;
+        vy = y * radial + g * (x * wxy + T(2) * y * w11) - e * w12;
+        vz = -e * S + T(2) * e2 * Q + T(2) * z * e2 * Lz;
+        // + J^T v_means2d, + the depth's gradient
+        vx += v_mx * j00 + v_my * j10; vy += v_mx * j01 + v_my * j11;
+        vz += v_mx * j02 + v_my * j12 + v_depth;
+    }
     v_mean[0] += (float)(V[0] * vx + V[3] * vy + V[6] * vz);
     v_mean[1] += (float)(V[1] * vx + V[4] * vy + V[7] * vz);
     v_mean[2] += (float)(V[2] * vx + V[5] * vy + V[8] * vz);
@@ -527,22 +654,22 @@ GS_HD void project_vjp_impl(const float* mean, const float* scale, const Camera&
     v_quat[2] += (float)((vq2 - y * dot) * p.qinv); v_quat[3] += (float)((vq3 - z * dot) * p.qinv);
 }
 
-template <typename T>
+template <typename T, int CAM = kCamPinhole>
 GS_HD void project_vjp(const float* scale, const Camera& cam, const ProjChainT<T>& p, float v_mx_f,
                        float v_my_f, float vA_f, float vB_f, float vC_f, float v_depth_f, float* v_mean,
                        float* v_quat, float* v_scale) {
-    project_vjp_impl<T, false>(nullptr, scale, cam, p, v_mx_f, v_my_f, vA_f, vB_f, vC_f, v_depth_f, v_mean, v_quat, v_scale,
+    project_vjp_impl<T, false, CAM>(nullptr, scale, cam, p, v_mx_f, v_my_f, vA_f, vB_f, vC_f, v_depth_f, v_mean, v_quat, v_scale,
                                (T*)nullptr, (T*)nullptr);
 }
 
 // The camera-gradient form: project_vjp (same v_mean / v_quat / v_scale, bit for bit) plus v_A[9] (row-major) and v_t[3] of
 // this (camera, Gaussian) in T -- fp64 in the product, not rounded to fp32 per Gaussian: the sum over a camera's Gaussians
 // cancels heavily (DESIGN.md "Camera gradients").  `mean`: the Gaussian's world-space mean.
-template <typename T>
+template <typename T, int CAM = kCamPinhole>
 GS_HD void project_vjp_cam(const float* mean, const float* scale, const Camera& cam, const ProjChainT<T>& p, float v_mx_f,
                            float v_my_f, float vA_f, float vB_f, float vC_f, float v_depth_f, float* v_mean,
                            float* v_quat, float* v_scale, T* v_A, T* v_t) {
-    project_vjp_impl<T, true>(mean, scale, cam, p, v_mx_f, v_my_f, vA_f, vB_f, vC_f, v_depth_f, v_mean, v_quat, v_scale, v_A, v_t);
+    project_vjp_impl<T, true, CAM>(mean, scale, cam, p, v_mx_f, v_my_f, vA_f, vB_f, vC_f, v_depth_f, v_mean, v_quat, v_scale, v_A, v_t);
 }
 
 // Camera constants from raw viewmat[16] / K[9] (row-major), incl. the general 3x3 inverse for the

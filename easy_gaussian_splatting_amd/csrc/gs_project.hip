@@ -233,136 +233,15 @@ __device__ __forceinline__ void sh_rows_commit(const ShPrefetch& pf, const float
 // lists) then overlaps ~0.1 ms of SH streaming instead of leaving the GPU idle.
 template <int DEG, int STAGE>
 __global__ __launch_bounds__(kProjThreads) void project_fwd_kernel(const ProjFwdArgs a) {
-    extern __shared__ __attribute__((aligned(16))) float smem[];
-    float* lds_cam = smem;
-    int* vis_s = reinterpret_cast<int*>(smem + 32);
-    float* tile = smem + 32 + kProjThreads;
-
-    const int c = blockIdx.y;
-    const int64_t n0 = (int64_t)blockIdx.x * kProjThreads;
-    const int64_t n = n0 + threadIdx.x;
-    const int64_t f = (int64_t)c * a.N + n;
-    const bool in_range = n < a.N;
-    Camera cam;
-    load_camera(a.viewmats, a.Ks, c, a.W, a.H, lds_cam, cam);
-
-    // one-launch forward, full SH3 rows in the split layout (what the reference model trains with): the block's SH slice is
-    // requested now and consumed after the projection chain (sh_rows_issue)
-    const bool prefetch_sh = STAGE == 0 && DEG == 3 && a.sh_rest != nullptr && a.K == 16 && (((uintptr_t)a.sh_rest & 15) == 0);
-    // (vector memory loads return in issue order: the geometry inputs are requested FIRST, so that the chain below waits
-    //  for them only and runs while the SH slice is still in flight)
-    float mean[3] = {0.f, 0.f, 0.f};
-    if (in_range) { mean[0] = a.means[3 * n]; mean[1] = a.means[3 * n + 1]; mean[2] = a.means[3 * n + 2]; }
-    float4 q4 = make_float4(1.f, 0.f, 0.f, 0.f);
-    float sc_raw[3] = {0.f, 0.f, 0.f}, op_raw = 0.f;
-    if (STAGE != 2 && in_range) {
-        q4 = reinterpret_cast<const float4*>(a.quats)[n];
-        sc_raw[0] = a.scales[3 * n]; sc_raw[1] = a.scales[3 * n + 1]; sc_raw[2] = a.scales[3 * n + 2];
-        op_raw = a.opacities[n];
-    }
-    ShPrefetch pf;
-    if (STAGE == 0 && DEG == 3 && prefetch_sh)
-        sh_rows_issue(a.colors_in, a.sh_rest, n0, (int)min((int64_t)kProjThreads, a.N - n0), pf);
-
-    bool vis = false;
-    if (STAGE != 2) {
-        Splat2D s;
-        s.radius = 0; s.mx = s.my = s.depth = s.A = s.B = s.C = s.cxx = s.cyy = 0.f; s.x0 = s.x1 = s.y0 = s.y1 = 0;
-        if (in_range) {
-            const float quat[4] = {q4.x, q4.y, q4.z, q4.w};
-            const float scale[3] = {act_scale(sc_raw[0], a.activations), act_scale(sc_raw[1], a.activations),
-                                    act_scale(sc_raw[2], a.activations)};
-            s = project_gaussian(mean, quat, scale, cam, a.W, a.H, a.eps2d, a.near_p, a.far_p, a.radius_clip, GS_TILE, a.tw, a.th);
-        }
-        vis = s.radius > 0;
-        if (!vis && in_range && a.rect_ref) a.rect_ref[f] = make_uint2(0u, 0u);
-        int x0 = 0, x1 = 0, y0 = 0, y1 = 0;
-        float op = 0.f, ex = -1.f, ey = -1.f;
-        if (vis) {
-            x0 = s.x0; x1 = s.x1; y0 = s.y0; y1 = s.y1;   // from the unrounded centre (gs_math.h: preal)
-            if (a.rect_ref) a.rect_ref[f] = make_uint2(fp_span(x0, x1), fp_span(y0, y1));
-            op = act_opacity(op_raw, a.activations);
-            alpha_extent(op, s.cxx, s.cyy, ex, ey);
-            // tight mode: keep only the tiles of the 3-sigma rectangle that hold a pixel centre where
-            // alpha can reach 1/255 (the blend skips every other pixel anyway: identical image)
-            if (a.tight) tile_rect_tight(s.mx, s.my, ex, ey, a.W, a.H, GS_TILE, x0, x1, y0, y1);
-        }
-        // tile footprint (gs_common.h: the footprint record): rectangle + (up to kMaskTiles tiles) a row-major bit per tile
-        const int rw = x1 - x0, rect_tiles = rw * (y1 - y0);
-        uint32_t tmask = fp_full_mask(rect_tiles);
-        if (a.tight && rect_tiles > 0 && rect_tiles <= kMaskTiles) {
-            // exact test per tile: some pixel centre of the tile must allow alpha >= 1/255
-            const float tau = __log2f(255.f * op) + 0.02f, lim = tau + 1e-4f * fabsf(tau);
-            const float qa = 0.5f * kLog2e * s.A, qb = kLog2e * s.B, qc = 0.5f * kLog2e * s.C;
-            tmask = 0u;
-            const float inv_rw = 1.0f / (float)rw;
-            for (int i = 0; i < rect_tiles; ++i) {
-                const int row = div_by_width(i, inv_rw), ty = y0 + row, tx = x0 + (i - row * rw);
-                const float dx0 = (float)(tx * GS_TILE) + 0.5f - s.mx, dy0 = (float)(ty * GS_TILE) + 0.5f - s.my;
-                if (quad_min_on_rect(qa, qb, qc, dx0, dx0 + (float)(GS_TILE - 1), dy0, dy0 + (float)(GS_TILE - 1)) <= lim) tmask |= 1u << i;
-            }
-        }
-        const int cnt = rect_tiles <= kMaskTiles ? __popc(tmask) : rect_tiles;
-        if (in_range) {
-            a.radii[f] = s.radius;
-            reinterpret_cast<float2*>(a.means2d)[f] = make_float2(s.mx, s.my);
-            a.depths[f] = s.depth;
-            a.conics[3 * f] = s.A; a.conics[3 * f + 1] = s.B; a.conics[3 * f + 2] = s.C;
-            a.bbox[f] = fp_pack(x0, x1, y0, y1, tmask, (uint32_t)cnt);
-            a.tiles_per_gauss[f] = cnt;
-            if (vis) {
-                // blend record: conic pre-scaled so the kernels evaluate exp2(-(hA dx^2 + B dx dy + hC dy^2))
-                float4* r = a.rec + 3 * f;
-                r[0] = make_float4(s.mx, s.my, 0.5f * kLog2e * s.A, kLog2e * s.B);
-                r[1] = make_float4(0.5f * kLog2e * s.C, op, ex, ey);
-            }
-        }
-    } else {
-        vis = in_range && a.radii[f] > 0;
-    }
-    if (STAGE == 1) return;
-
-    float rgb[3] = {0.5f, 0.5f, 0.5f};
-    if (DEG >= 0) {
-        vis_s[threadIdx.x] = vis ? 1 : 0;
-        const int any_vis = __syncthreads_or(vis ? 1 : 0);
-        if (any_vis) {
-            const int rows = (int)min((int64_t)kProjThreads, a.N - n0);
-            constexpr int ka3 = 3 * (DEG + 1) * (DEG + 1);
-            if (STAGE == 0 && DEG == 3 && prefetch_sh) {
-                sh_rows_commit(pf, a.sh_rest, n0, rows, tile);
-            } else if (a.sh_rest) {
-                if (DEG == 4) stage_sh_rows_split<25>(a.colors_in, a.sh_rest, n0, rows, 25, ka3, vis_s, tile);   // (SH4: K = 25)
-                else if (a.K == 16) stage_sh_rows_split<16>(a.colors_in, a.sh_rest, n0, rows, 16, ka3, vis_s, tile);
-                else stage_sh_rows_split<0>(a.colors_in, a.sh_rest, n0, rows, a.K, ka3, vis_s, tile);
-            } else {
-                if (DEG == 4) stage_sh_rows<25>(a.colors_in, n0, rows, 25, ka3, vis_s, tile);
-                else if (a.K == 16) stage_sh_rows<16>(a.colors_in, n0, rows, 16, ka3, vis_s, tile);
-                else stage_sh_rows<0>(a.colors_in, n0, rows, a.K, ka3, vis_s, tile);
-            }
-            __syncthreads();
-            if (vis) {
-                float ux, uy, uz;
-                view_dir(mean, cam, ux, uy, uz);
-                sh_to_rgb(DEG < 0 ? 0 : DEG, tile + threadIdx.x * (3 * a.K + 1), ux, uy, uz, rgb);
-                if (DEG >= 1 && a.sh_jac) {
-                    float G[12];
-                    sh_dir_jacobian(DEG, tile + threadIdx.x * (3 * a.K + 1), ux, uy, uz, G);
-                    // nine floats per Gaussian: eight as two aligned quads [C*N][8], the ninth in a plane of its own behind them
-                    float4* jp = a.sh_jac + 2 * f;
-                    jp[0] = make_float4(G[0], G[1], G[2], G[4]); jp[1] = make_float4(G[5], G[6], G[8], G[9]);
-                    reinterpret_cast<float*>(a.sh_jac + 2 * (int64_t)a.C * a.N)[f] = G[10];
-                }
-            }
-        }
-    } else if (in_range) {
-        const float* src = a.colors_in + 3 * (a.colors_per_camera ? f : n);
-        rgb[0] = src[0]; rgb[1] = src[1]; rgb[2] = src[2];
-    }
-    if (in_range) {
-        a.colors_out[3 * f] = rgb[0]; a.colors_out[3 * f + 1] = rgb[1]; a.colors_out[3 * f + 2] = rgb[2];
-        if (vis) a.rec[3 * f + 2] = make_float4(rgb[0], rgb[1], rgb[2], 0.f);
-    }
+    constexpr int CAM = kCamPinhole;
+#include "gs_project_fwd_body.h"
+}
+// ... under another camera model (gs_project_fwd_cm: CAM = kCamOrtho, kCamFisheye): the same text around project_gaussian_cm<CAM>.  A kernel
+// template of its own: the pinhole kernel above keeps its symbol and its code.  STAGE 2 (colour only) has no camera model in it.
+template <int DEG, int STAGE, int CAM>
+__global__ __launch_bounds__(kProjThreads) void project_fwd_cm_kernel(const ProjFwdArgs a) {
+    static_assert(CAM != kCamPinhole && STAGE != 2, "the pinhole model and the colour stage are project_fwd_kernel's");
+#include "gs_project_fwd_body.h"
 }
 
 // ------------------------------------------------------------------------------------------------
@@ -749,13 +628,14 @@ __device__ __forceinline__ void row_sum_wave(const A& a, int nr, int r0, int bas
 // SH4 instantiation of the existing form 68 bytes of scratch.
 template <int DEG, bool ADAM, bool SUMS = false, bool SCALE_REG = false>
 __global__ __launch_bounds__(kProjThreads) void project_bwd_kernel(const ProjBwdArgs a) {
-    constexpr int REG = SCALE_REG ? 1 : 0;
+    constexpr int REG = SCALE_REG ? 1 : 0, CAM = kCamPinhole;
 #include "gs_project_bwd_body.h"
 }
 // the fused form under a Gaussian budget (gs_project_bwd_adam_mcmc): REG = 2 the budget term alone, 3 behind the scale-ratio term
 template <int DEG, int REG, bool SUMS = false>
 __global__ __launch_bounds__(kProjThreads) void project_bwd_budget_kernel(const ProjBwdArgs a) {
     constexpr bool ADAM = true;
+    constexpr int CAM = kCamPinhole;
 #include "gs_project_bwd_body.h"
 }
 
@@ -763,6 +643,17 @@ __global__ __launch_bounds__(kProjThreads) void project_bwd_budget_kernel(const 
 template <int DEG, int REG>
 __global__ __launch_bounds__(kProjThreads) void project_bwd_depth_kernel(const ProjBwdArgs a) {
     constexpr bool ADAM = true, SUMS = false;
+    constexpr int CAM = kCamPinhole;
+#include "gs_project_bwd_body.h"
+}
+
+// the eager (ADAM = false) and the fused (ADAM = true; REG = 0, or 1: the scale-ratio regulariser) form under another camera model
+// (gs_project_bwd_cm, gs_project_bwd_adam_cm, gs_project_bwd_adam_reg_cm): the gradient rows are walked (no SUMS form), and the budget
+// and depth variants of the fused form do not exist for these models
+template <int DEG, bool ADAM, int REG, int CAM>
+__global__ __launch_bounds__(kProjThreads) void project_bwd_cm_kernel(const ProjBwdArgs a) {
+    static_assert(CAM != kCamPinhole && (REG == 0 || (ADAM && REG == 1)), "pinhole: project_bwd_kernel; REG: the scale-ratio term, fused form only");
+    constexpr bool SUMS = false;
 #include "gs_project_bwd_body.h"
 }
 
@@ -945,71 +836,16 @@ constexpr int kCamTerms = 15;
 // 0-1, 4-6 and 8-10, as project_bwd_kernel hands them out -- and the gradient tensors do not exist.
 template <int DEG, bool SUMS = false>
 __global__ __launch_bounds__(kProjThreads) void project_cam_kernel(const ProjCamArgs a) {
-    __shared__ float lds_cam[32];
-    __shared__ double wave_sums[kProjThreads / 64][16];
-    if (guard_tripped(a.guard)) return;
-    const int c = blockIdx.y;
-    const int64_t n = (int64_t)blockIdx.x * kProjThreads + threadIdx.x;
-    const int64_t f = (int64_t)c * a.N + n;
-    Camera cam;
-    load_camera(a.viewmats, a.Ks, c, a.W, a.H, lds_cam, cam);
-    double acc[kCamTerms];
-#pragma unroll
-    for (int i = 0; i < kCamTerms; ++i) acc[i] = 0.0;
-    if (n < a.N && a.radii[f] > 0) {
-        const float mean[3] = {a.means[3 * n], a.means[3 * n + 1], a.means[3 * n + 2]};
-        const float4 q4 = reinterpret_cast<const float4*>(a.quats)[n];
-        const float quat[4] = {q4.x, q4.y, q4.z, q4.w};
-        const float scale[3] = {act_scale(a.scales[3 * n], a.activations), act_scale(a.scales[3 * n + 1], a.activations),
-                                act_scale(a.scales[3 * n + 2], a.activations)};
-        if (DEG >= 1) {   // the SH colour's dependence on the camera centre: minus the direction term of v_mean
-            const float rgb[3] = {a.colors_post[3 * f], a.colors_post[3 * f + 1], a.colors_post[3 * f + 2]};
-            float v_rgb[3];
-            if (SUMS) { const float4 z = a.row_sums[3 * f + 2]; v_rgb[0] = z.x; v_rgb[1] = z.y; v_rgb[2] = z.z; }
-            else { v_rgb[0] = a.v_colors_post[3 * f]; v_rgb[1] = a.v_colors_post[3 * f + 1]; v_rgb[2] = a.v_colors_post[3 * f + 2]; }
-            float ux, uy, uz, term[3];
-            const float dn = view_dir(mean, cam, ux, uy, uz);
-            if (a.sh_jac) {   // (project_bwd_kernel's layout)
-                float G[12];
-                const float4 j0 = a.sh_jac[2 * f], j1 = a.sh_jac[2 * f + 1];
-                G[10] = reinterpret_cast<const float*>(a.sh_jac + 2 * (int64_t)gridDim.y * a.N)[f];
-                G[0] = j0.x; G[1] = j0.y; G[2] = j0.z; G[4] = j0.w; G[5] = j1.x; G[6] = j1.y; G[8] = j1.z; G[9] = j1.w;
-                sh_dir_term_jac(DEG, G, rgb, v_rgb, ux, uy, uz, dn, term);
-            } else {
-                sh_dir_term(DEG, a.sh_from_1 + a.sh_stride * n, rgb, v_rgb, ux, uy, uz, dn, term);
-            }
-            acc[12] = -(double)term[0]; acc[13] = -(double)term[1]; acc[14] = -(double)term[2];
-        }
-        ProjChainT<preal> p;
-        if (project_chain<preal>(mean, quat, scale, cam, a.eps2d, a.near_p, a.far_p, p)) {
-            float v_mean[3] = {0.f, 0.f, 0.f}, v_quat[4] = {0.f, 0.f, 0.f, 0.f}, v_scale[3] = {0.f, 0.f, 0.f};   // (not used here)
-            float2 vm;
-            float vc[3];
-            if (SUMS) {
-                const float4 x = a.row_sums[3 * f], y = a.row_sums[3 * f + 1];
-                vm = make_float2(x.x, x.y); vc[0] = y.x; vc[1] = y.y; vc[2] = y.z;
-            } else {
-                vm = reinterpret_cast<const float2*>(a.v_means2d)[f];
-                vc[0] = a.v_conics[3 * f]; vc[1] = a.v_conics[3 * f + 1]; vc[2] = a.v_conics[3 * f + 2];
-            }
-            project_vjp_cam<preal>(mean, scale, cam, p, vm.x, vm.y, vc[0], vc[1], vc[2], 0.f, v_mean, v_quat, v_scale, acc, acc + 9);
-        }
-    }
-    const int lane = lane_id(), wave = threadIdx.x >> 6;
-#pragma unroll
-    for (int i = 0; i < kCamTerms; ++i) {
-        const double t = wave_reduce_add(acc[i]);
-        if (lane == 0) wave_sums[wave][i] = t;
-    }
-    __syncthreads();
-    if (threadIdx.x < 16) {
-        double t = 0.0;
-        if (threadIdx.x < kCamTerms) {
-#pragma unroll
-            for (int w = 0; w < kProjThreads / 64; ++w) t += wave_sums[w][threadIdx.x];
-        }
-        a.cam_partials[((int64_t)c * gridDim.x + blockIdx.x) * 16 + threadIdx.x] = t;
-    }
+    constexpr int CAM = kCamPinhole;
+#include "gs_project_cam_body.h"
+}
+// ... under another camera model (gs_project_bwd_cam_cm): v_t = v_pc and v_A = v_pc mean^T + 2 v_covc A Sigma hold for any model once the
+// VJP has formed v_pc and v_covc with the model's Jacobian (gs_math.h: project_vjp_impl)
+template <int DEG, int CAM>
+__global__ __launch_bounds__(kProjThreads) void project_cam_cm_kernel(const ProjCamArgs a) {
+    static_assert(CAM != kCamPinhole, "the pinhole model is project_cam_kernel's");
+    constexpr bool SUMS = false;
+#include "gs_project_cam_body.h"
 }
 
 // One block per camera: every one of the 16 values is walked by 64 threads, each over the camera's partials at a stride of 64
@@ -1132,14 +968,18 @@ extern "C" int gs_row_sums(void* stream, int C, int64_t N, const int32_t* radii,
     return GS_OK;
 }
 
-extern "C" int gs_project_fwd(void* stream, int C, int64_t N, int K, int sh_degree, const float* means,
-                              const float* quats, const float* scales, const float* opacities,
-                              const float* colors_in, const float* sh_rest, int colors_per_camera,
-                              const float* viewmats, const float* Ks, int width, int height,
-                              float eps2d, float near_plane, float far_plane, float radius_clip,
-                              int tile_culling, int stage, int activations, int32_t* radii,
-                              float* means2d, float* depths, float* conics, float* colors_out, float* rec,
-                              uint32_t* bbox, int32_t* tiles_per_gauss, uint32_t* rect_ref, float* sh_jac) {
+#define GS_REQUIRE_CAMERA(m) GS_REQUIRE((m) == GS_CAMERA_PINHOLE || (m) == GS_CAMERA_ORTHO || (m) == GS_CAMERA_FISHEYE, \
+                                        "camera_model: GS_CAMERA_PINHOLE, GS_CAMERA_ORTHO or GS_CAMERA_FISHEYE")
+
+static int project_fwd(void* stream, int C, int64_t N, int K, int sh_degree, const float* means,
+                       const float* quats, const float* scales, const float* opacities,
+                       const float* colors_in, const float* sh_rest, int colors_per_camera,
+                       const float* viewmats, const float* Ks, int width, int height,
+                       float eps2d, float near_plane, float far_plane, float radius_clip,
+                       int tile_culling, int stage, int activations, int32_t* radii,
+                       float* means2d, float* depths, float* conics, float* colors_out, float* rec,
+                       uint32_t* bbox, int32_t* tiles_per_gauss, uint32_t* rect_ref, float* sh_jac, int camera_model) {
+    GS_REQUIRE_CAMERA(camera_model);
     GS_REQUIRE(C >= 1 && N >= 0 && width > 0 && height > 0, "C>=1, N>=0, positive image size");
     GS_REQUIRE(sh_degree <= 4, "sh_degree must be <= 4");
     GS_REQUIRE(sh_degree < 0 || (K >= (sh_degree + 1) * (sh_degree + 1) && K <= 25), "K must hold (sh_degree+1)^2 coefficients and be <= 25");
@@ -1175,14 +1015,59 @@ extern "C" int gs_project_fwd(void* stream, int C, int64_t N, int K, int sh_degr
         case 4: GS_PF((S) == 1 ? -1 : 4, S); break;   /* (stage 1: no SH) */ \
         default: GS_PF(-1, S); break;                                     \
     }
-    if (stage == 0) { GS_PF_DEG(0) } else if (stage == 1) { GS_PF_DEG(1) } else { GS_PF_DEG(2) }
+    // another camera model: a kernel per (model, degree) for the one-launch form, one per model for the geometry stage (which evaluates no
+    // colour); the colour stage has no camera model in it and stays the pinhole path's kernel
+#define GS_PFC(D, S, M)                                                                                          \
+    { if ((S) != 1) GS_LDS((project_fwd_cm_kernel<D, S, M>));                                                    \
+      hipLaunchKernelGGL((project_fwd_cm_kernel<D, S, M>), grid, dim3(kProjThreads), (S) == 1 ? proj_lds_bytes(K, -1) : lds, st, a); }
+#define GS_PFC_DEG(M)                                                     \
+    if (stage == 1) GS_PFC(-1, 1, M) else switch (sh_degree) {            \
+        case 0: GS_PFC(0, 0, M); break;                                   \
+        case 1: GS_PFC(1, 0, M); break;                                   \
+        case 2: GS_PFC(2, 0, M); break;                                   \
+        case 3: GS_PFC(3, 0, M); break;                                   \
+        case 4: GS_PFC(4, 0, M); break;                                   \
+        default: GS_PFC(-1, 0, M); break;                                 \
+    }
+    if (camera_model == GS_CAMERA_ORTHO && stage != 2) { GS_PFC_DEG(kCamOrtho) }
+    else if (camera_model == GS_CAMERA_FISHEYE && stage != 2) { GS_PFC_DEG(kCamFisheye) }
+    else if (stage == 0) { GS_PF_DEG(0) } else if (stage == 1) { GS_PF_DEG(1) } else { GS_PF_DEG(2) }
+#undef GS_PFC_DEG
+#undef GS_PFC
 #undef GS_PF_DEG
 #undef GS_PF
     GS_LAUNCH_CHECK("project_fwd_kernel");
     return GS_OK;
 }
 
-extern "C" int gs_project_bwd(void* stream, int C, int64_t N, int K, int sh_degree, const float* means,
+extern "C" int gs_project_fwd(void* stream, int C, int64_t N, int K, int sh_degree, const float* means,
+                              const float* quats, const float* scales, const float* opacities,
+                              const float* colors_in, const float* sh_rest, int colors_per_camera,
+                              const float* viewmats, const float* Ks, int width, int height,
+                              float eps2d, float near_plane, float far_plane, float radius_clip,
+                              int tile_culling, int stage, int activations, int32_t* radii,
+                              float* means2d, float* depths, float* conics, float* colors_out, float* rec,
+                              uint32_t* bbox, int32_t* tiles_per_gauss, uint32_t* rect_ref, float* sh_jac) {
+    return project_fwd(stream, C, N, K, sh_degree, means, quats, scales, opacities, colors_in, sh_rest, colors_per_camera, viewmats, Ks,
+                       width, height, eps2d, near_plane, far_plane, radius_clip, tile_culling, stage, activations, radii, means2d, depths,
+                       conics, colors_out, rec, bbox, tiles_per_gauss, rect_ref, sh_jac, GS_CAMERA_PINHOLE);
+}
+
+// gs_project_fwd under the camera model `camera_model` (GS_CAMERA_PINHOLE: that very call)
+extern "C" int gs_project_fwd_cm(void* stream, int C, int64_t N, int K, int sh_degree, const float* means,
+                                 const float* quats, const float* scales, const float* opacities,
+                                 const float* colors_in, const float* sh_rest, int colors_per_camera,
+                                 const float* viewmats, const float* Ks, int width, int height,
+                                 float eps2d, float near_plane, float far_plane, float radius_clip,
+                                 int tile_culling, int stage, int activations, int32_t* radii,
+                                 float* means2d, float* depths, float* conics, float* colors_out, float* rec,
+                                 uint32_t* bbox, int32_t* tiles_per_gauss, uint32_t* rect_ref, float* sh_jac, int camera_model) {
+    return project_fwd(stream, C, N, K, sh_degree, means, quats, scales, opacities, colors_in, sh_rest, colors_per_camera, viewmats, Ks,
+                       width, height, eps2d, near_plane, far_plane, radius_clip, tile_culling, stage, activations, radii, means2d, depths,
+                       conics, colors_out, rec, bbox, tiles_per_gauss, rect_ref, sh_jac, camera_model);
+}
+
+static int project_bwd(void* stream, int C, int64_t N, int K, int sh_degree, const float* means,
                               const float* quats, const float* scales, const float* colors_in,
                               const float* sh_rest, int colors_per_camera, const float* viewmats,
                               const float* Ks, int width,
@@ -1193,7 +1078,9 @@ extern "C" int gs_project_bwd(void* stream, int C, int64_t N, int K, int sh_degr
                               float* v_opacities, float* v_colors, float* v_sh_rest, float* v_means2d_abs,
                               float* v_means2d, float* v_conics, float* v_colors_post, float* v_colors_pre,
                               const float* opacities, int activations, const float* sh_jac, const float* row_sums,
-                              float* stat_grad_norm, float* stat_count) {
+                              float* stat_grad_norm, float* stat_count, int camera_model) {
+    GS_REQUIRE_CAMERA(camera_model);
+    GS_REQUIRE(camera_model == GS_CAMERA_PINHOLE || !row_sums, "row_sums (the view-parallel step's form) exist for the pinhole model only");
     GS_REQUIRE(C >= 1 && N >= 0 && width > 0 && height > 0, "C>=1, N>=0, positive image size");
     GS_REQUIRE((stat_grad_norm == nullptr) == (stat_count == nullptr) && (!stat_count || (C == 1 && row_sums)),
                "stat_grad_norm / stat_count: both or neither, single camera, together with row_sums");
@@ -1232,7 +1119,9 @@ extern "C" int gs_project_bwd(void* stream, int C, int64_t N, int K, int sh_degr
     // every launch, stream order serialises them) -> deterministic sum over cameras, no atomics.
     for (int c = 0; c < C; ++c) {
         a.cam = c; a.accumulate = c > 0;
+#define GS_PBC(D, M) { GS_LDS((project_bwd_cm_kernel<D, false, 0, M>)); hipLaunchKernelGGL((project_bwd_cm_kernel<D, false, 0, M>), grid, dim3(kProjThreads), lds, st, a); }
 #define GS_PB(D)                                                                                                        \
+        if (camera_model == GS_CAMERA_ORTHO) GS_PBC(D, kCamOrtho) else if (camera_model == GS_CAMERA_FISHEYE) GS_PBC(D, kCamFisheye) else \
         if (row_sums) { GS_LDS((project_bwd_kernel<D, false, true>)); hipLaunchKernelGGL((project_bwd_kernel<D, false, true>), grid, dim3(kProjThreads), lds, st, a); } \
         else { GS_LDS((project_bwd_kernel<D, false, false>)); hipLaunchKernelGGL((project_bwd_kernel<D, false, false>), grid, dim3(kProjThreads), lds, st, a); }
         switch (sh_degree) {
@@ -1244,9 +1133,49 @@ extern "C" int gs_project_bwd(void* stream, int C, int64_t N, int K, int sh_degr
             default: GS_PB(-1); break;
         }
 #undef GS_PB
+#undef GS_PBC
         GS_LAUNCH_CHECK("project_bwd_kernel");
     }
     return GS_OK;
+}
+
+extern "C" int gs_project_bwd(void* stream, int C, int64_t N, int K, int sh_degree, const float* means,
+                              const float* quats, const float* scales, const float* colors_in,
+                              const float* sh_rest, int colors_per_camera, const float* viewmats,
+                              const float* Ks, int width,
+                              int height, float eps2d, float near_plane, float far_plane,
+                              const int32_t* radii, const float* colors_post,
+                              const int32_t* tiles_per_gauss, const int32_t* cum_tiles,
+                              const float* rows, const int32_t* row_base, const uint8_t* qmask, float* v_means, float* v_quats, float* v_scales,
+                              float* v_opacities, float* v_colors, float* v_sh_rest, float* v_means2d_abs,
+                              float* v_means2d, float* v_conics, float* v_colors_post, float* v_colors_pre,
+                              const float* opacities, int activations, const float* sh_jac, const float* row_sums,
+                              float* stat_grad_norm, float* stat_count) {
+    return project_bwd(stream, C, N, K, sh_degree, means, quats, scales, colors_in, sh_rest, colors_per_camera, viewmats, Ks,
+                       width, height, eps2d, near_plane, far_plane, radii, colors_post, tiles_per_gauss, cum_tiles, rows,
+                       row_base, qmask, v_means, v_quats, v_scales, v_opacities, v_colors, v_sh_rest, v_means2d_abs,
+                       v_means2d, v_conics, v_colors_post, v_colors_pre, opacities, activations, sh_jac, row_sums,
+                       stat_grad_norm, stat_count, GS_CAMERA_PINHOLE);
+}
+
+// gs_project_bwd under the camera model `camera_model` (GS_CAMERA_PINHOLE: that very call; the others walk the gradient rows: row_sums NULL)
+extern "C" int gs_project_bwd_cm(void* stream, int C, int64_t N, int K, int sh_degree, const float* means,
+                              const float* quats, const float* scales, const float* colors_in,
+                              const float* sh_rest, int colors_per_camera, const float* viewmats,
+                              const float* Ks, int width,
+                              int height, float eps2d, float near_plane, float far_plane,
+                              const int32_t* radii, const float* colors_post,
+                              const int32_t* tiles_per_gauss, const int32_t* cum_tiles,
+                              const float* rows, const int32_t* row_base, const uint8_t* qmask, float* v_means, float* v_quats, float* v_scales,
+                              float* v_opacities, float* v_colors, float* v_sh_rest, float* v_means2d_abs,
+                              float* v_means2d, float* v_conics, float* v_colors_post, float* v_colors_pre,
+                              const float* opacities, int activations, const float* sh_jac, const float* row_sums,
+                              float* stat_grad_norm, float* stat_count, int camera_model) {
+    return project_bwd(stream, C, N, K, sh_degree, means, quats, scales, colors_in, sh_rest, colors_per_camera, viewmats, Ks,
+                       width, height, eps2d, near_plane, far_plane, radii, colors_post, tiles_per_gauss, cum_tiles, rows,
+                       row_base, qmask, v_means, v_quats, v_scales, v_opacities, v_colors, v_sh_rest, v_means2d_abs,
+                       v_means2d, v_conics, v_colors_post, v_colors_pre, opacities, activations, sh_jac, row_sums,
+                       stat_grad_norm, stat_count, camera_model);
 }
 
 
@@ -1255,7 +1184,7 @@ extern "C" size_t gs_cam_partials_doubles(int C, int64_t N) {
     return (size_t)C * (size_t)((N + kProjThreads - 1) / kProjThreads) * 16;
 }
 
-extern "C" int gs_project_bwd_cam(void* stream, int C, int64_t N, int K, int sh_degree, const float* means,
+static int project_bwd_cam(int camera_model, void* stream, int C, int64_t N, int K, int sh_degree, const float* means,
                                   const float* quats, const float* scales, const float* colors_in,
                                   const float* sh_rest, int colors_per_camera, const float* viewmats,
                                   const float* Ks, int width,
@@ -1268,6 +1197,7 @@ extern "C" int gs_project_bwd_cam(void* stream, int C, int64_t N, int K, int sh_
                                   const float* opacities, int activations, const float* sh_jac, const float* row_sums,
                                   float* stat_grad_norm, float* stat_count, double* cam_partials, float* v_viewmats,
                                   float* v_campos) {
+    GS_REQUIRE_CAMERA(camera_model);
     GS_REQUIRE(C >= 1 && N >= 0, "C>=1, N>=0");
     GS_REQUIRE(v_viewmats && v_campos && (N == 0 || cam_partials), "null camera-gradient pointer");
     GS_REQUIRE(N == 0 || (v_means2d && v_conics && (sh_degree < 1 || v_colors_post)),
@@ -1280,11 +1210,11 @@ extern "C" int gs_project_bwd_cam(void* stream, int C, int64_t N, int K, int sh_
     }
     GS_REQUIRE(((uintptr_t)quats & 15) == 0 && ((uintptr_t)v_means2d & 7) == 0 && ((uintptr_t)cam_partials & 7) == 0,
                "quats 16-byte, v_means2d and cam_partials 8-byte aligned");
-    if (int rc = gs_project_bwd(stream, C, N, K, sh_degree, means, quats, scales, colors_in, sh_rest, colors_per_camera, viewmats, Ks,
-                                width, height, eps2d, near_plane, far_plane, radii, colors_post, tiles_per_gauss, cum_tiles, rows,
-                                row_base, qmask, v_means, v_quats, v_scales, v_opacities, v_colors, v_sh_rest, v_means2d_abs,
-                                v_means2d, v_conics, v_colors_post, v_colors_pre, opacities, activations, sh_jac, row_sums,
-                                stat_grad_norm, stat_count))
+    if (int rc = project_bwd(stream, C, N, K, sh_degree, means, quats, scales, colors_in, sh_rest, colors_per_camera, viewmats, Ks,
+                             width, height, eps2d, near_plane, far_plane, radii, colors_post, tiles_per_gauss, cum_tiles, rows,
+                             row_base, qmask, v_means, v_quats, v_scales, v_opacities, v_colors, v_sh_rest, v_means2d_abs,
+                             v_means2d, v_conics, v_colors_post, v_colors_pre, opacities, activations, sh_jac, row_sums,
+                             stat_grad_norm, stat_count, camera_model))
         return rc;
     ProjCamArgs a;
     a.K = K; a.W = width; a.H = height; a.activations = activations != 0; a.N = N;
@@ -1298,7 +1228,10 @@ extern "C" int gs_project_bwd_cam(void* stream, int C, int64_t N, int K, int sh_
     a.cam_partials = cam_partials; a.guard = current_guard().info;
     const int n_blocks = (int)((N + kProjThreads - 1) / kProjThreads);
     dim3 grid((unsigned)n_blocks, (unsigned)C);
-#define GS_PC(D) hipLaunchKernelGGL((project_cam_kernel<D>), grid, dim3(kProjThreads), 0, st, a)
+#define GS_PC(D)                                                                                                                         \
+    if (camera_model == GS_CAMERA_ORTHO) hipLaunchKernelGGL((project_cam_cm_kernel<D, kCamOrtho>), grid, dim3(kProjThreads), 0, st, a);          \
+    else if (camera_model == GS_CAMERA_FISHEYE) hipLaunchKernelGGL((project_cam_cm_kernel<D, kCamFisheye>), grid, dim3(kProjThreads), 0, st, a); \
+    else hipLaunchKernelGGL((project_cam_kernel<D>), grid, dim3(kProjThreads), 0, st, a)
     switch (sh_degree) {
         case 1: GS_PC(1); break;
         case 2: GS_PC(2); break;
@@ -1311,6 +1244,45 @@ extern "C" int gs_project_bwd_cam(void* stream, int C, int64_t N, int K, int sh_
     hipLaunchKernelGGL(cam_sum_kernel, dim3((unsigned)C), dim3(16 * kCamSumChains), 0, st, (const double*)cam_partials, n_blocks, v_viewmats, v_campos, a.guard);
     GS_LAUNCH_CHECK("cam_sum_kernel");
     return GS_OK;
+}
+
+extern "C" int gs_project_bwd_cam(void* stream, int C, int64_t N, int K, int sh_degree, const float* means,
+                              const float* quats, const float* scales, const float* colors_in,
+                              const float* sh_rest, int colors_per_camera, const float* viewmats,
+                              const float* Ks, int width,
+                              int height, float eps2d, float near_plane, float far_plane,
+                              const int32_t* radii, const float* colors_post,
+                              const int32_t* tiles_per_gauss, const int32_t* cum_tiles,
+                              const float* rows, const int32_t* row_base, const uint8_t* qmask, float* v_means, float* v_quats, float* v_scales,
+                              float* v_opacities, float* v_colors, float* v_sh_rest, float* v_means2d_abs,
+                              float* v_means2d, float* v_conics, float* v_colors_post, float* v_colors_pre,
+                              const float* opacities, int activations, const float* sh_jac, const float* row_sums,
+                              float* stat_grad_norm, float* stat_count, double* cam_partials, float* v_viewmats, float* v_campos) {
+    return project_bwd_cam(GS_CAMERA_PINHOLE, stream, C, N, K, sh_degree, means, quats, scales, colors_in, sh_rest, colors_per_camera, viewmats, Ks,
+                       width, height, eps2d, near_plane, far_plane, radii, colors_post, tiles_per_gauss, cum_tiles, rows,
+                       row_base, qmask, v_means, v_quats, v_scales, v_opacities, v_colors, v_sh_rest, v_means2d_abs,
+                       v_means2d, v_conics, v_colors_post, v_colors_pre, opacities, activations, sh_jac, row_sums,
+                       stat_grad_norm, stat_count, cam_partials, v_viewmats, v_campos);
+}
+
+// gs_project_bwd_cam under the camera model `camera_model` (GS_CAMERA_PINHOLE: that very call)
+extern "C" int gs_project_bwd_cam_cm(void* stream, int C, int64_t N, int K, int sh_degree, const float* means,
+                              const float* quats, const float* scales, const float* colors_in,
+                              const float* sh_rest, int colors_per_camera, const float* viewmats,
+                              const float* Ks, int width,
+                              int height, float eps2d, float near_plane, float far_plane,
+                              const int32_t* radii, const float* colors_post,
+                              const int32_t* tiles_per_gauss, const int32_t* cum_tiles,
+                              const float* rows, const int32_t* row_base, const uint8_t* qmask, float* v_means, float* v_quats, float* v_scales,
+                              float* v_opacities, float* v_colors, float* v_sh_rest, float* v_means2d_abs,
+                              float* v_means2d, float* v_conics, float* v_colors_post, float* v_colors_pre,
+                              const float* opacities, int activations, const float* sh_jac, const float* row_sums,
+                              float* stat_grad_norm, float* stat_count, double* cam_partials, float* v_viewmats, float* v_campos, int camera_model) {
+    return project_bwd_cam(camera_model, stream, C, N, K, sh_degree, means, quats, scales, colors_in, sh_rest, colors_per_camera, viewmats, Ks,
+                       width, height, eps2d, near_plane, far_plane, radii, colors_post, tiles_per_gauss, cum_tiles, rows,
+                       row_base, qmask, v_means, v_quats, v_scales, v_opacities, v_colors, v_sh_rest, v_means2d_abs,
+                       v_means2d, v_conics, v_colors_post, v_colors_pre, opacities, activations, sh_jac, row_sums,
+                       stat_grad_norm, stat_count, cam_partials, v_viewmats, v_campos);
 }
 
 // The camera gradients of the single-camera step from gs_row_sums' per-Gaussian sums (the captured step with poses): the kernels and
@@ -1370,7 +1342,10 @@ static int project_bwd_adam(void* stream, int64_t N, int K, int sh_degree, float
                             float* v_means2d_abs, float beta1, float beta2, float eps, const float* hyper_dev,
                             int64_t* applied_dev, float* max_radii, float* grad_norm_accum, float* counts,
                             const float* sh_jac, int reg, float max_ratio, float lambda, double bud_a, double bud_b,
-                            const float* row_sums = nullptr, const float* v_depths = nullptr) {
+                            const float* row_sums = nullptr, const float* v_depths = nullptr, int camera_model = GS_CAMERA_PINHOLE) {
+    GS_REQUIRE_CAMERA(camera_model);
+    GS_REQUIRE(camera_model == GS_CAMERA_PINHOLE || (!(reg & 2) && !row_sums && !v_depths),
+               "the budget, row-sums and depth variants of the fused backward exist for the pinhole model only");
     GS_REQUIRE(N >= 0 && width > 0 && height > 0, "N>=0, positive image size");
     GS_REQUIRE(sh_degree >= 0 && sh_degree <= 4 && K >= (sh_degree + 1) * (sh_degree + 1) && K <= 25, "SH colours: 0 <= degree <= 4, (degree+1)^2 <= K <= 25");
     if (N == 0) return GS_OK;
@@ -1410,7 +1385,13 @@ static int project_bwd_adam(void* stream, int64_t N, int K, int sh_degree, float
     // (the row_sums forms -- gs_project_bwd_adam_sums -- are instantiations of their own; the compiler's resource report shows
     //  none of them with scratch: a kernel that declares it makes the runtime provision it -- gs_blend.hip, GS_FWD_TRAIN_WAVES_PER_EU)
 #define GS_PBK(...) { GS_LDS((__VA_ARGS__)); hipLaunchKernelGGL((__VA_ARGS__), grid, dim3(kProjThreads), lds, st, a); }
+    // (degree 4 with the regulariser under the fisheye: the branch-free form of its radial terms, kCamFisheyeSelect -- with the branch the
+    //  compiler reserves 36 bytes of scratch per lane for this one instantiation, which no instruction of it touches)
+#define GS_PBC(D, M)                                                                                                                     \
+    if (reg == 1) GS_PBK(project_bwd_cm_kernel<D, true, 1, ((D) == 4 && (M) == kCamFisheye) ? kCamFisheyeSelect : (M)>)                   \
+    else GS_PBK(project_bwd_cm_kernel<D, true, 0, M>)
 #define GS_PB(D)                                                                                                        \
+    if (camera_model == GS_CAMERA_ORTHO) { GS_PBC(D, kCamOrtho) } else if (camera_model == GS_CAMERA_FISHEYE) { GS_PBC(D, kCamFisheye) } else \
     if (v_depths) {                                                                                                     \
         if (reg == 3) GS_PBK(project_bwd_depth_kernel<D, 7>) else if (reg == 2) GS_PBK(project_bwd_depth_kernel<D, 6>)                  \
         else if (reg == 1) GS_PBK(project_bwd_depth_kernel<D, 5>) else GS_PBK(project_bwd_depth_kernel<D, 4>)                           \
@@ -1427,6 +1408,7 @@ static int project_bwd_adam(void* stream, int64_t N, int K, int sh_degree, float
         default: GS_PB(4); break;
     }
 #undef GS_PB
+#undef GS_PBC
 #undef GS_PBK
     GS_LAUNCH_CHECK("project_bwd_kernel (fused Adam)");
     return GS_OK;
@@ -1456,6 +1438,33 @@ extern "C" int gs_project_bwd_adam_reg(void* stream, int64_t N, int K, int sh_de
     return project_bwd_adam(stream, N, K, sh_degree, params, exp_avg, exp_avg_sq, offsets_host, viewmats, Ks, width, height, eps2d,
                             near_plane, far_plane, radii, colors_post, tiles_per_gauss, cum_tiles, rows, row_base, qmask, v_means2d_abs,
                             beta1, beta2, eps, hyper_dev, applied_dev, max_radii, grad_norm_accum, counts, sh_jac, 1, max_ratio, lambda, 0.0, 0.0);
+}
+
+// gs_project_bwd_adam / gs_project_bwd_adam_reg under the camera model `camera_model` (GS_CAMERA_PINHOLE: those very calls)
+extern "C" int gs_project_bwd_adam_cm(void* stream, int64_t N, int K, int sh_degree, float* params, float* exp_avg, float* exp_avg_sq,
+                                   const int64_t* offsets_host, const float* viewmats, const float* Ks, int width, int height,
+                                   float eps2d, float near_plane, float far_plane, const int32_t* radii, const float* colors_post,
+                                   const int32_t* tiles_per_gauss, const int32_t* cum_tiles, const float* rows, const int32_t* row_base, const uint8_t* qmask,
+                                   float* v_means2d_abs, float beta1, float beta2, float eps, const float* hyper_dev,
+                                   int64_t* applied_dev, float* max_radii, float* grad_norm_accum, float* counts,
+                                   const float* sh_jac, int camera_model) {
+    return project_bwd_adam(stream, N, K, sh_degree, params, exp_avg, exp_avg_sq, offsets_host, viewmats, Ks, width, height, eps2d,
+                            near_plane, far_plane, radii, colors_post, tiles_per_gauss, cum_tiles, rows, row_base, qmask, v_means2d_abs,
+                            beta1, beta2, eps, hyper_dev, applied_dev, max_radii, grad_norm_accum, counts, sh_jac, 0, 0.f, 0.f, 0.0, 0.0,
+                            nullptr, nullptr, camera_model);
+}
+extern "C" int gs_project_bwd_adam_reg_cm(void* stream, int64_t N, int K, int sh_degree, float* params, float* exp_avg, float* exp_avg_sq,
+                                   const int64_t* offsets_host, const float* viewmats, const float* Ks, int width, int height,
+                                   float eps2d, float near_plane, float far_plane, const int32_t* radii, const float* colors_post,
+                                   const int32_t* tiles_per_gauss, const int32_t* cum_tiles, const float* rows, const int32_t* row_base, const uint8_t* qmask,
+                                   float* v_means2d_abs, float beta1, float beta2, float eps, const float* hyper_dev,
+                                   int64_t* applied_dev, float* max_radii, float* grad_norm_accum, float* counts,
+                                   const float* sh_jac, float max_ratio, float lambda, int camera_model) {
+    GS_REQUIRE(((uintptr_t)params & 3) == 0, "params must be 4-byte aligned");
+    return project_bwd_adam(stream, N, K, sh_degree, params, exp_avg, exp_avg_sq, offsets_host, viewmats, Ks, width, height, eps2d,
+                            near_plane, far_plane, radii, colors_post, tiles_per_gauss, cum_tiles, rows, row_base, qmask, v_means2d_abs,
+                            beta1, beta2, eps, hyper_dev, applied_dev, max_radii, grad_norm_accum, counts, sh_jac, 1, max_ratio, lambda, 0.0, 0.0,
+                            nullptr, nullptr, camera_model);
 }
 
 // ... with the budget regulariser's gradients in v_opacity and v_scale (its value: gs_mcmc_reg in front of this call), behind the

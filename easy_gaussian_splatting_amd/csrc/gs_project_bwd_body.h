@@ -1,4 +1,5 @@
-// The body of project_bwd_kernel / project_bwd_budget_kernel / project_bwd_depth_kernel (gs_project.hip), which define DEG, ADAM, SUMS and the mask REG around it.
+// The body of project_bwd_kernel / project_bwd_budget_kernel / project_bwd_depth_kernel / project_bwd_cm_kernel (gs_project.hip), which define DEG, ADAM,
+// SUMS, the mask REG and the camera model CAM around it.
 // Included once per kernel template, inside its braces: no include guard, nothing but the body.
     extern __shared__ __attribute__((aligned(16))) float smem[];
     if (guard_tripped(a.guard)) return;
@@ -122,8 +123,8 @@
                                 act_scale(p_scales[3 * n + 2], a.activations)};
         if (a.activations) { sc_fac[0] = scale[0]; sc_fac[1] = scale[1]; sc_fac[2] = scale[2]; }
         ProjChainT<preal> p;
-        if (project_chain<preal>(mean, quat, scale, cam, a.eps2d, a.near_p, a.far_p, p))
-            project_vjp<preal>(scale, cam, p, s.v[0], s.v[1], s.v[4], s.v[5], s.v[6], 0.f, v_mean, v_quat, v_scale);
+        if (project_chain<preal, CAM>(mean, quat, scale, cam, a.eps2d, a.near_p, a.far_p, p))
+            project_vjp<preal, CAM>(scale, cam, p, s.v[0], s.v[1], s.v[4], s.v[5], s.v[6], 0.f, v_mean, v_quat, v_scale);
     }
     if ((REG & 4) && in_range) {   // + the depth channel's gradient (culled Gaussians: v_z = 0), onto the rounded v_mean as gs_depth_grads adds it
         const float row2[3] = {lds_cam[6], lds_cam[7], lds_cam[8]};   // (make_camera: R[6..8] = row 2 of the view matrix, as it lies there)

@@ -425,8 +425,11 @@ class GaussianModel(nn.Module):
         the reference drops) -- what `viewer.FrameRenderer` masks a depth frame with.
         A `data["w2c"]` that requires grad (e.g. from `pose.CameraDeltas`) receives its gradient: the render is then asked for
         camera gradients (`rasterization(_camera_grads=True)`).  Eager loop only: `TrainStepGraph` refuses such a `w2c`, and a
-        model with `sh_grads = "colors_pre"` (`ViewParallelStep` with its exchange on) is refused by `rasterization()`."""
+        model with `sh_grads = "colors_pre"` (`ViewParallelStep` with its exchange on) is refused by `rasterization()`.
+        `data.get("camera_model", "pinhole")` ("pinhole" | "ortho" | "fisheye", what `scene.Frame` carries) goes to
+        `rasterization(camera_model=...)`."""
         w2c = data["w2c"]
+        camera_model = data.get("camera_model", "pinhole")
         if depth not in (None, "D", "ED"):
             raise ValueError(f"depth: None, 'D' or 'ED', got {depth!r}")
         # on the GPU the raw parameters go in and exp / sigmoid happen inside the projection kernels
@@ -456,6 +459,7 @@ class GaussianModel(nn.Module):
             _view_payload=self.view_payload() if callable(getattr(self, "view_payload", None)) else None,
             _camera_grads=bool(w2c.requires_grad),
             **({} if depth is None else {"render_mode": "RGB+" + depth}),
+            **({} if camera_model == "pinhole" else {"camera_model": camera_model}),   # (pinhole: the call as it was)
         )
         render_img = batch_render_imgs.squeeze(0)   # (a view both ways: `[0]` would cost a zero-fill + copy in backward)
         render_depth = None

@@ -572,6 +572,7 @@ def _forward_stages(means, quats, scales, opacities, colors, colors_rest, viewma
         deg, K, per_cam, dc = -1, 0, 0, 0
     if dmode:
         ch = dc + 1
+    cam_model = int(cfg.get("camera_model", nat.GS_CAMERA_PINHOLE))   # (another model: the `_cm` entry points, one depth round)
     split_project = _SPLIT_PROJECT and not dmode
 
     # what escapes to the caller through `meta` is allocated per call; everything else is workspace
@@ -595,7 +596,7 @@ def _forward_stages(means, quats, scales, opacities, colors, colors_rest, viewma
     # depth rounds: inference, one camera, long lists (see ROUNDS_MIN_LISTED above); the decision of a call shape is taken from
     # what its one-round calls listed and kept (a two-round call reports the short total of its two rounds)
     rmode = cfg.get("rounds") or rounds_mode()
-    rounds = (not need_grad) and C == 1 and N > 0 and ch == 3 and not dmode and rmode != "off" and (rmode == "on" or (
+    rounds = (not need_grad) and C == 1 and N > 0 and ch == 3 and not dmode and cam_model == nat.GS_CAMERA_PINHOLE and rmode != "off" and (rmode == "on" or (
         two_level and int(hint.get("n", -1)) == N and int(hint.get("listed_one_round", 0)) >= ROUNDS_MIN_LISTED and not hint.get("rounds_off")))
     rb = _round_buffers(dev, st, N, tiles) if rounds else None
     eager_ids = os.environ.get("GS_EAGER_ISECT_IDS") == "1"   # (default: meta builds isect_ids on first access, _LazyMeta)
@@ -629,12 +630,15 @@ def _forward_stages(means, quats, scales, opacities, colors, colors_rest, viewma
     use_jac = bool(need_grad and _SH_JAC and deg >= 1)
 
     def project(stage: int, tag: str):
-        _stage(tag, dev, lambda: nat.check(L.gs_project_fwd(
-            st, C, N, K, deg, _ptr(means), _ptr(quats), _ptr(scales), _ptr(opacities), _ptr(colors), _ptr(colors_rest),
-            per_cam, _ptr(viewmats), _ptr(Ks), W, H, cfg["eps2d"], cfg["near_plane"], cfg["far_plane"],
-            cfg["radius_clip"], cfg["tile_culling"], stage, cfg.get("activations", 0), _ptr(radii), _ptr(means2d), _ptr(depths), _ptr(conics),
-            P(WS.COLORS_POST), P(WS.REC), P(WS.BBOX), P(WS.TILES_PER_GAUSS), _ptr(rect_ref),
-            P(WS.SH_JAC) if use_jac else None), "gs_project_fwd"))
+        args = (st, C, N, K, deg, _ptr(means), _ptr(quats), _ptr(scales), _ptr(opacities), _ptr(colors), _ptr(colors_rest),
+                per_cam, _ptr(viewmats), _ptr(Ks), W, H, cfg["eps2d"], cfg["near_plane"], cfg["far_plane"],
+                cfg["radius_clip"], cfg["tile_culling"], stage, cfg.get("activations", 0), _ptr(radii), _ptr(means2d), _ptr(depths), _ptr(conics),
+                P(WS.COLORS_POST), P(WS.REC), P(WS.BBOX), P(WS.TILES_PER_GAUSS), _ptr(rect_ref),
+                P(WS.SH_JAC) if use_jac else None)
+        if cam_model == nat.GS_CAMERA_PINHOLE:   # (today's call, untouched)
+            _stage(tag, dev, lambda: nat.check(L.gs_project_fwd(*args), "gs_project_fwd"))
+        else:
+            _stage(tag, dev, lambda: nat.check(L.gs_project_fwd_cm(*args, cam_model), "gs_project_fwd_cm"))
 
     def bbox_ptr():   # the footprints the list stages read: the projection's, or (depth rounds) those of the round at hand
         return rb["bbox"].data_ptr() if rounds else P(WS.BBOX)
@@ -1058,6 +1062,7 @@ class _Rasterize(torch.autograd.Function):
                             _ptr(v_pc), _ptr(v_rest), _ptr(v_abs), _ptr(v_m2), _ptr(v_cn), _ptr(v_cp), None,
                             _ptr(opacities), cfg.get("activations", 0), P(WS.SH_JAC) if s.get("sh_jac") else None,
                             _ptr(row_sums), _ptr(go.get("grad_norm")), _ptr(go.get("count")))
+        cam_model = int(cfg.get("camera_model", nat.GS_CAMERA_PINHOLE))
         if ctx.camera_grads:
             # gs_project_bwd_cam: the same projection backward (same bits), then the camera terms from the per-(camera, Gaussian)
             # sums it hands out -- which are therefore written -- reduced per camera in fp64 without atomics.  The partials are
@@ -1067,10 +1072,16 @@ class _Rasterize(torch.autograd.Function):
             v_cp = torch.empty((C, N, 3), **f32) if v_cp is None else v_cp
             partials = torch.empty((int(L.gs_cam_partials_doubles(C, N)),), dtype=torch.float64, device=dev)
             v_viewmats, v_campos = torch.empty((C, 4, 4), **f32), torch.empty((C, 3), **f32)
-            _stage("gs_project_bwd", dev, lambda: nat.check(L.gs_project_bwd_cam(*bwd_args(), _ptr(partials), _ptr(v_viewmats), _ptr(v_campos)),
-                                                            "gs_project_bwd_cam"))
-        else:
+            if cam_model == nat.GS_CAMERA_PINHOLE:
+                _stage("gs_project_bwd", dev, lambda: nat.check(L.gs_project_bwd_cam(*bwd_args(), _ptr(partials), _ptr(v_viewmats), _ptr(v_campos)),
+                                                                "gs_project_bwd_cam"))
+            else:
+                _stage("gs_project_bwd", dev, lambda: nat.check(L.gs_project_bwd_cam_cm(*bwd_args(), _ptr(partials), _ptr(v_viewmats), _ptr(v_campos),
+                                                                                        cam_model), "gs_project_bwd_cam_cm"))
+        elif cam_model == nat.GS_CAMERA_PINHOLE:
             _stage("gs_project_bwd", dev, lambda: nat.check(L.gs_project_bwd(*bwd_args()), "gs_project_bwd"))
+        else:
+            _stage("gs_project_bwd", dev, lambda: nat.check(L.gs_project_bwd_cm(*bwd_args(), cam_model), "gs_project_bwd_cm"))
         if dc != 3 and dc > 0:
             _stage("gs_channel_grads", dev, lambda: nat.check(L.gs_channel_grads(
                 st, C, N, dc, s["per_cam"], _ptr(s["radii"]), P(WS.TILES_PER_GAUSS), P(WS.CUM_TILES), P(WS.ROWS), P(WS.ROW_BASE),
@@ -1156,6 +1167,10 @@ def quat_to_rotmat_torch(quats: Tensor) -> Tensor:
     return R.reshape(quats.shape[:-1] + (3, 3))
 
 
+# rasterization(camera_model=...): gsplat's names -> the C ABI's GS_CAMERA_* (include/gs_raster.h "Camera models")
+CAMERA_MODELS = {"pinhole": nat.GS_CAMERA_PINHOLE, "ortho": nat.GS_CAMERA_ORTHO, "fisheye": nat.GS_CAMERA_FISHEYE}
+
+
 def rasterization(
     means: Tensor,  # [N, 3]
     quats: Tensor,  # [N, 4]  wxyz, need not be normalised
@@ -1189,9 +1204,10 @@ def rasterization(
     _grad_out: Optional[Dict[str, Tensor]] = None,
     _view_payload: Optional[Tensor] = None,
     _camera_grads: bool = False,
+    camera_model: str = "pinhole",
 ) -> Tuple[Tensor, Tensor, Dict]:
     """Rasterize 3D Gaussians to images; same tensor signature and return value as
-    `gsplat.rendering.rasterization` (gsplat 1.0.0).
+    `gsplat.rendering.rasterization` (gsplat 1.0.0), plus `camera_model` as gsplat 1.4 added it.
 
     Returns `(render_colors [C,H,W,D], render_alphas [C,H,W,1], meta)`; D = 3 with SH colours.
 
@@ -1255,6 +1271,16 @@ def rasterization(
     `v_Ks`).  Not together with `_sh_grads="colors_pre"`, `_grad_out` or `_view_payload` (`ValueError`): the view-parallel step has
     no place for a camera gradient.  INTEGRATION.md "Refining camera poses".
 
+    `camera_model` (gsplat's keyword since 1.4): "pinhole" (default: the call without the keyword, bit for bit), "ortho" or "fisheye".
+    The definitions are this project's own (DESIGN.md "Camera models"; parity with gsplat's kernels is not checked): the mean goes to
+    camera space (x, y, z) and is culled on z as for the pinhole -- a fisheye therefore sees strictly less than 180 degrees -- and
+    "ortho" maps it to (fx x + cx, fy y + cy), "fisheye" (ideal equidistant, no distortion terms) to (fx x k + cx, fy y k + cy) with
+    k = atan2(r, z) / r; the 2-D covariance is J cov_c J^T + eps2d I with that map's Jacobian, without the pinhole's FOV clamp.  A
+    Gaussian on the fisheye's optical axis is an ordinary visible one.  SH degrees 0-4, 1-4 feature channels, C >= 1, every
+    `_tile_culling`, `absgrad`, the depth render modes, `_camera_grads` and `_activations` work as for the pinhole; always one depth
+    round; not together with `_sh_grads="colors_pre"`, `_grad_out` or `_view_payload` (`ValueError`), an unknown name raises
+    `ValueError`.  INTEGRATION.md "Cameras other than pinhole".
+
     `_rounds` ("auto" | "on" | "off"; default: env GS_ROUNDS or "auto"): depth rounds of the list stages for INFERENCE calls with
     one camera -- the front slab by depth is listed, sorted and blended first, the rest only into tiles it has not finished
     (include/gs_raster.h "Depth rounds"; same image bit for bit).  "auto": on for a call shape whose one-round call listed
@@ -1309,6 +1335,11 @@ def rasterization(
     if depth and (_sh_grads == "colors_pre" or _grad_out is not None or _view_payload is not None):
         raise ValueError(f"render_mode={render_mode!r} cannot be combined with _sh_grads='colors_pre', _grad_out or _view_payload "
                          "(the view-parallel record has no place for a depth gradient)")
+    if camera_model not in CAMERA_MODELS:
+        raise ValueError(f"camera_model: one of {sorted(CAMERA_MODELS)} (got {camera_model!r})")
+    if camera_model != "pinhole" and (_sh_grads == "colors_pre" or _grad_out is not None or _view_payload is not None):
+        raise ValueError(f"camera_model={camera_model!r} cannot be combined with _sh_grads='colors_pre', _grad_out or _view_payload "
+                         "(the view-parallel step's projection backward exists for the pinhole model only)")
     if rasterize_mode != "classic":
         raise NotImplementedError("only rasterize_mode='classic' is implemented")
     if tile_size != _TILE:
@@ -1362,6 +1393,8 @@ def rasterization(
                activations={"none": 0, "exp_sigmoid": 1}[_activations], grad_enabled=torch.is_grad_enabled(),
                defer_size_check=size_check == "deferred" and not expected, rounds=_rounds, depth=depth, expected_depth=expected,
                camera_grads=bool(_camera_grads and viewmats.requires_grad and torch.is_grad_enabled()))
+    if camera_model != "pinhole":   # (the pinhole call's cfg is today's, key for key)
+        cfg["camera_model"] = CAMERA_MODELS[camera_model]
     if _sh_grads not in ("dense", "colors_pre") or (_sh_grads == "colors_pre" and sh_degree is None):
         raise ValueError("_sh_grads: 'dense', or 'colors_pre' together with sh_degree")
     holder = _Holder(absgrad)

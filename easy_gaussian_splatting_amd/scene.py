@@ -96,7 +96,10 @@ def get_mask_arr(mask_path: Path, expand_pixels: int) -> np.ndarray:
 
 class Frame:
     def __init__(self, image_path: Path, mask_path: Optional[Path], mask_expand_pixels: int, width: int, height: int,
-                 fx: float, fy: float, cx: float, cy: float, w2c: np.ndarray, white_background: bool):
+                 fx: float, fy: float, cx: float, cy: float, w2c: np.ndarray, white_background: bool, camera_model: str = "pinhole"):
+        if camera_model not in ("pinhole", "ortho", "fisheye"):
+            raise ValueError(f"camera_model: 'pinhole', 'ortho' or 'fisheye' (got {camera_model!r})")
+        self.camera_model = camera_model   # what `rasterization(camera_model=...)` renders this frame with
         self.image_path, self.mask_path, self.mask_expand_pixels = image_path, mask_path, mask_expand_pixels
         self.width, self.height = width, height
         self.fx, self.fy, self.cx, self.cy = fx, fy, cx, cy
@@ -123,7 +126,10 @@ class Frame:
             mask_tensor = torch.zeros((height, width), dtype=torch.float32)
         f = get_downscale_factor(self.height, self.width, height, width)
         K = torch.tensor([[self.fx * f, 0, self.cx * f], [0, self.fy * f, self.cy * f], [0, 0, 1]], dtype=torch.float32)
-        return {"K": K, "height": height, "width": width, "w2c": w2c, "image": image_tensor, "mask": mask_tensor}
+        data = {"K": K, "height": height, "width": width, "w2c": w2c, "image": image_tensor, "mask": mask_tensor}
+        if self.camera_model != "pinhole":   # (a pinhole frame's dict is the reference's, key for key)
+            data["camera_model"] = self.camera_model
+        return data
 
 
 def data_to_device(data: Dict[str, Any], non_blocking: bool = True, device="cuda"):
@@ -133,9 +139,19 @@ def data_to_device(data: Dict[str, Any], non_blocking: bool = True, device="cuda
 
 # ------------------------------------------------------------------------------------------------ COLMAP binary model
 class Camera:
-    def __init__(self, id: int, model_name: Literal["SIMPLE_PINHOLE", "PINHOLE"], width: int, height: int, params: Sequence[float]):
+    def __init__(self, id: int, model_name: Literal["SIMPLE_PINHOLE", "PINHOLE", "OPENCV_FISHEYE"], width: int, height: int,
+                 params: Sequence[float]):
         self.id, self.model_name, self.width, self.height = id, model_name, width, height
-        if model_name == "SIMPLE_PINHOLE":
+        self.camera_model = "pinhole"   # rasterization()'s name of the projection
+        if model_name == "OPENCV_FISHEYE":
+            # fx, fy, cx, cy, k1..k4: the ideal equidistant fisheye when the four distortion terms vanish -- the only fisheye the
+            # rasterizer projects (`rasterization(camera_model="fisheye")`)
+            if any(float(k) != 0.0 for k in params[4:8]):
+                raise ValueError(f"camera {id}: OPENCV_FISHEYE with distortion terms k1..k4 = {tuple(params[4:8])}: the rasterizer's fisheye "
+                                 "is the ideal equidistant one -- the images must be undistorted first (to zero distortion terms)")
+            self.fx, self.fy, self.cx, self.cy = params[0], params[1], params[2], params[3]
+            self.camera_model = "fisheye"
+        elif model_name == "SIMPLE_PINHOLE":
             self.fx = self.fy = params[0]
             self.cx, self.cy = params[1], params[2]
         elif model_name == "PINHOLE":
@@ -154,7 +170,7 @@ def read_next_bytes(f: BinaryIO, num_bytes: int, format_char_sequence: str, endi
     return struct.unpack(endian_character + format_char_sequence, f.read(num_bytes))
 
 
-_CAM_MAP = {0: ("SIMPLE_PINHOLE", 3), 1: ("PINHOLE", 4)}   # {cam_model_id: (name, num_params)}
+_CAM_MAP = {0: ("SIMPLE_PINHOLE", 3), 1: ("PINHOLE", 4), 8: ("OPENCV_FISHEYE", 8)}   # {cam_model_id: (name, num_params)}
 
 
 def load_intrinsics_binary(path: Path) -> Dict[int, Camera]:
@@ -239,7 +255,7 @@ def load_colmap_data(path: str, use_masks: bool, mask_expand_pixels: int, eval: 
         mask_path = (root / "masks" / image.image_file_name).with_suffix(".png")
         frames.append(Frame(root / "images" / image.image_file_name, mask_path if mask_path.exists() and use_masks else None,
                             mask_expand_pixels, camera.width, camera.height, camera.fx, camera.fy, camera.cx, camera.cy, w2c,
-                            white_background))
+                            white_background, camera_model=camera.camera_model))
     frames.sort(key=lambda frame: frame.image_path)
     indexes = list(range(len(frames)))
     random.shuffle(indexes)

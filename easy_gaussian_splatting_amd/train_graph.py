@@ -129,6 +129,29 @@ def _pose_view(poses, view_index, exposure=None, bilagrid=None) -> Optional[int]
     return i
 
 
+def _refuse_camera_model_combinations(camera_model, mcmc, poses, depth, rounds) -> None:
+    """TrainStepGraph(camera_model=...): what the non-pinhole models cannot be combined with, before any device work."""
+    if camera_model not in rendering.CAMERA_MODELS:
+        raise ValueError(f"TrainStepGraph: camera_model: one of {sorted(rendering.CAMERA_MODELS)} (got {camera_model!r})")
+    if camera_model == "pinhole":
+        return
+    what = f"TrainStepGraph(camera_model={camera_model!r})"
+    if mcmc is not None:
+        raise ValueError(f"{what} with `mcmc` -- the fused projection backward + Adam with the budget regulariser "
+                         "(gs_project_bwd_adam_mcmc: project_bwd_budget_kernel) does not exist for this camera model yet")
+    if poses is not None:
+        raise ValueError(f"{what} with `poses` -- the fused projection backward + Adam from the row sums and the camera gradient from "
+                         "them (gs_project_bwd_adam_sums, gs_cam_grad_sums: project_cam_kernel<DEG, SUMS = true>) do not exist for this "
+                         "camera model yet; refine poses in the eager loop (rasterization(camera_model=..., _camera_grads=True))")
+    if depth is not None:
+        raise ValueError(f"{what} with `depth` -- the fused projection backward + Adam with the depth gradient "
+                         "(gs_project_bwd_adam_depth: project_bwd_depth_kernel) does not exist for this camera model yet")
+    if rounds == "on":
+        raise ValueError(f"{what} with rounds='on' -- the camera models other than pinhole run in one depth round: the fused projection "
+                         "backward over the two row ranges of a two-round step (project_bwd_kernel with ProjBwdArgs.rblk) is not "
+                         "instantiated for this camera model yet")
+
+
 class TrainStepGraph:
     def __init__(self, model, optimizer: FusedAdam, loss_computer, data: Dict[str, Any], gt_img: Tensor,
                  mask: Optional[Tensor] = None, margin: float = 1.3, use_graph: bool = True, check_every: int = 16,
@@ -137,7 +160,7 @@ class TrainStepGraph:
                  pose_lr: float = 1e-3, pose_betas: Tuple[float, float] = (0.9, 0.999), pose_eps: float = 1e-15, exposure=None,
                  exposure_lr: float = 1e-2, exposure_betas: Tuple[float, float] = (0.9, 0.999), exposure_eps: float = 1e-15, bilagrid=None,
                  bilagrid_lr: float = 2e-3, bilagrid_betas: Tuple[float, float] = (0.9, 0.999), bilagrid_eps: float = 1e-15,
-                 bilagrid_tv: float = 10.0, depth=None, gt_depth: Optional[Tensor] = None):
+                 bilagrid_tv: float = 10.0, depth=None, gt_depth: Optional[Tensor] = None, camera_model: str = "pinhole"):
         """`mcmc`: an `mcmc.MCMCStrategy(model, ..., noise="counter")` -- the step then trains under its Gaussian budget: `mcmc_reg` =
         (opacity_reg, scale_reg) of `strategy.regularization()` enters the loss (out["mcmc_reg"]) and the update, and the strategy's
         noise runs behind Adam inside the step, at noise_lr x the means learning rate of that step.  None (default): nothing changes.
@@ -188,7 +211,15 @@ class TrainStepGraph:
         and write the 3-channel image and its gradient as always).  Refused before any device work: a missing `gt_depth` or one of
         another shape (`ValueError`); `rounds="on"` (`ValueError`: the depth lane's gather is one-round only; "auto" resolves to off);
         `poses` (`ValueError`: the camera gradient of the depth term is not formed); `ViewParallelGraphStep` (`ValueError`);
-        `HostFeed` on such a runner (`NotImplementedError`).  None (default): nothing changes, launch for launch."""
+        `HostFeed` on such a runner (`NotImplementedError`).  None (default): nothing changes, launch for launch.
+        `camera_model`: "pinhole" (default: nothing changes, launch for launch), "ortho" or "fisheye" (`rasterization(camera_model=...)`)
+        -- the step then projects with gs_project_fwd_cm and updates with gs_project_bwd_adam_cm / gs_project_bwd_adam_reg_cm.  Works
+        with a mask, the scale regulariser, `exposure`, `bilagrid` and `HostFeed` (none of them touches the projection backward), always
+        in one depth round ("auto" resolves to off).  Refused before any device work (`ValueError`): `mcmc`, `poses`, `depth`,
+        `rounds="on"` and `ViewParallelGraphStep` -- each needs a variant of the fused projection backward that exists for the
+        pinhole model only."""
+        _refuse_camera_model_combinations(camera_model, mcmc, poses, depth, __import__("os").environ.get("GS_TG_ROUNDS", rounds))
+        self.camera_model = rendering.CAMERA_MODELS[camera_model]
         self.depth = depth
         if depth is not None:
             from .depth_loss import MODES, DepthSupervision
@@ -278,6 +309,9 @@ class TrainStepGraph:
                 raise ValueError("TrainStepGraph: the MCMCStrategy works on another model than the one the runner trains")
             self.mcmc_reg = (float(mcmc_reg[0]), float(mcmc_reg[1]))
         _refuse_camera_grads(data)
+        if data.get("camera_model", camera_model) != camera_model:   # (what model(data) would render with in the eager loop)
+            raise ValueError(f"TrainStepGraph: data['camera_model'] is {data['camera_model']!r}, but the runner was asked for "
+                             f"camera_model={camera_model!r}")
         if handback not in ("eager", "lazy"):
             raise ValueError("handback: 'eager' or 'lazy'")
         self.handback = handback
@@ -291,8 +325,8 @@ class TrainStepGraph:
         if rounds not in ("auto", "on", "off"):
             raise ValueError("rounds: 'auto', 'on' or 'off'")
         self.rounds_mode, self.round_fraction = rounds, float(__import__("os").environ.get("GS_TG_ROUND_FRACTION", round_fraction))
-        if depth is not None and rounds == "auto":
-            rounds = self.rounds_mode = "off"   # (one round: see `depth`)
+        if (depth is not None or self.camera_model != nat.GS_CAMERA_PINHOLE) and rounds == "auto":
+            rounds = self.rounds_mode = "off"   # (one round: see `depth`, `camera_model`)
         self.rounds_on = rounds == "on"
         self._live_sum = self._live_n = 0   # tiles the front round left live, summed over the polled steps since the last build
         # "auto" only: the captured step holds the FRONT round alone (gs_rounds_set phase 4), speculating that it finishes every
@@ -793,11 +827,15 @@ class TrainStepGraph:
         if self.poses is not None:   # the corrected view matrix of the record's view, from the deltas as they stand
             self._ck(L.gs_pose_compose(self._st(), int(self.poses.deltas.shape[0]), _p(b["pose_rec"]), _p(self.poses.deltas.data),
                                        _p(b["viewmats"])), "gs_pose_compose")
-        self._ck(L.gs_project_fwd(self._st(), 1, self.N, self.K, int(m.active_sh_degree), _p(m.means), _p(m.quats), _p(m.log_scales),
-                                   _p(m.logit_opacities), _p(m.sh_0), _p(m.sh_rest) if self.K > 1 else None, 0,
-                                   _p(b["viewmats"]), _p(b["Ks"]), self.W, self.H, EPS2D, NEAR_PLANE, FAR_PLANE, RADIUS_CLIP, culling, 0, 1,
-                                   _p(b["radii"]), _p(b["means2d"]), _p(b["depths"]), _p(b["conics"]), _p(b["colors_post"]),
-                                   _p(b["rec"]), _p(b["bbox"]), _p(b["tiles_per_gauss"]), None, _p(b["sh_jac"])), "gs_project_fwd")
+        args = (self._st(), 1, self.N, self.K, int(m.active_sh_degree), _p(m.means), _p(m.quats), _p(m.log_scales),
+                _p(m.logit_opacities), _p(m.sh_0), _p(m.sh_rest) if self.K > 1 else None, 0,
+                _p(b["viewmats"]), _p(b["Ks"]), self.W, self.H, EPS2D, NEAR_PLANE, FAR_PLANE, RADIUS_CLIP, culling, 0, 1,
+                _p(b["radii"]), _p(b["means2d"]), _p(b["depths"]), _p(b["conics"]), _p(b["colors_post"]),
+                _p(b["rec"]), _p(b["bbox"]), _p(b["tiles_per_gauss"]), None, _p(b["sh_jac"]))
+        if self.camera_model == nat.GS_CAMERA_PINHOLE:
+            self._ck(L.gs_project_fwd(*args), "gs_project_fwd")
+        else:
+            self._ck(L.gs_project_fwd_cm(*args, self.camera_model), "gs_project_fwd_cm")
 
     def _count(self, bbox: str = "bbox"):
         b = self.buf
@@ -992,6 +1030,18 @@ class TrainStepGraph:
             elif self.mcmc is not None:
                 self._ck(L.gs_project_bwd_adam_mcmc(*args, int(self.scale_reg), self.max_scale_ratio if self.scale_reg else 0.0,
                                                      self.lambda_scale if self.scale_reg else 0.0, *self.mcmc_reg), "gs_project_bwd_adam_mcmc")
+            elif self.camera_model != nat.GS_CAMERA_PINHOLE:   # (no depth, poses or mcmc here: refused at construction)
+                # (`args`, spelt out: a tuple literal, so that tests/test_native_header.py can count these two calls against the header)
+                cm_args = (st, N, self.K, int(m.active_sh_degree), _p(opt.flat_param), _p(opt.exp_avg), _p(opt.exp_avg_sq), offs,
+                           _p(b["viewmats"]), _p(b["Ks"]), W, H, EPS2D, NEAR_PLANE, FAR_PLANE, _p(b["radii"]), _p(b["colors_post"]),
+                           self._tpg(), _p(b["cum_tiles"]), _p(b["rows"]), _p(b["row_base"]), _p(b["qmask"]), _p(b["v_abs"]), float(b1),
+                           float(b2), float(opt.defaults["eps"]), _p(b["hyper"]), _p(b["applied"]), _p(m.max_radii),
+                           _p(m.grad_norm_accum), _p(m.collecting_counts), _p(b["sh_jac"]))
+                if self.scale_reg:
+                    self._ck(L.gs_project_bwd_adam_reg_cm(*cm_args, self.max_scale_ratio, self.lambda_scale, self.camera_model),
+                             "gs_project_bwd_adam_reg_cm")
+                else:
+                    self._ck(L.gs_project_bwd_adam_cm(*cm_args, self.camera_model), "gs_project_bwd_adam_cm")
             elif self.scale_reg:
                 self._ck(L.gs_project_bwd_adam_reg(*args, self.max_scale_ratio, self.lambda_scale), "gs_project_bwd_adam_reg")
             else:
@@ -1007,6 +1057,9 @@ class TrainStepGraph:
                 self._ck(L.gs_project_bwd_cam(*bwd_args, _p(b["v_means2d"]), _p(b["v_conics"]), _p(b["v_colors_post"]), None,
                                                _p(m.logit_opacities), 1, _p(b["sh_jac"]), None, None, None, _p(b["cam_partials"]),
                                                _p(b["v_viewmats"]), _p(b["v_campos"])), "gs_project_bwd_cam")
+            elif self.camera_model != nat.GS_CAMERA_PINHOLE:
+                self._ck(L.gs_project_bwd_cm(*bwd_args, None, None, None, None, _p(m.logit_opacities), 1, _p(b["sh_jac"]), None, None, None,
+                                              self.camera_model), "gs_project_bwd_cm")
             else:
                 self._ck(L.gs_project_bwd(*bwd_args, None, None, None, None, _p(m.logit_opacities), 1, _p(b["sh_jac"]), None, None, None),
                          "gs_project_bwd")
@@ -1437,6 +1490,10 @@ class ViewParallelGraphStep(TrainStepGraph):
     rasterizer (`fuse_activations`, the default)."""
 
     def __init__(self, model, optimizer, loss_computer, data, gt_img, mask=None, vp=None, **kw):
+        if kw.get("camera_model", "pinhole") != "pinhole":
+            raise ValueError("ViewParallelGraphStep: camera_model='pinhole' only -- the view-parallel step's projection backward takes the "
+                             "row sums (project_bwd_kernel<DEG, ADAM, SUMS = true>), a variant that does not exist for "
+                             f"camera_model={kw['camera_model']!r} yet")
         if kw.get("poses") is not None:
             raise ValueError("ViewParallelGraphStep: no `poses` -- pose refinement inside the captured step is single-GPU "
                              "(TrainStepGraph(poses=...)): the view-parallel step has no camera gradient")

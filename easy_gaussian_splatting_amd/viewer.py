@@ -272,9 +272,14 @@ class FrameRenderer:
     ordered as an evaluation is: the next step waits for the caller's stream on entry; with `handback="lazy"`
     call `runner.fence()` first.  It takes none of the captured step's buffers and leaves the run bit-identical.
 
-    A model in training mode is put into `eval()` for the call and back into `train()` after it."""
+    A model in training mode is put into `eval()` for the call and back into `train()` after it.
 
-    def __init__(self, model, ring: int = 3, device: Optional[Union[str, torch.device]] = None) -> None:
+    `camera_model` ("pinhole" | "ortho" | "fisheye"): what the model's forward receives as `data["camera_model"]` for every frame."""
+
+    def __init__(self, model, ring: int = 3, device: Optional[Union[str, torch.device]] = None, camera_model: str = "pinhole") -> None:
+        if camera_model not in ("pinhole", "ortho", "fisheye"):
+            raise ValueError(f"camera_model: 'pinhole', 'ortho' or 'fisheye' (got {camera_model!r})")
+        self.camera_model = camera_model
         if ring < 2:
             raise ValueError("ring must be at least 2: one buffer with the consumer, one being filled")
         if device is None:
@@ -306,6 +311,8 @@ class FrameRenderer:
         slot.cam_dev.copy_(slot.cam_host, non_blocking=True)
         H, W = int(cs.height), int(cs.width)
         data = {"w2c": slot.cam_dev[:16].view(4, 4), "K": slot.cam_dev[16:25].view(3, 3), "height": H, "width": W}
+        if self.camera_model != "pinhole":
+            data["camera_model"] = self.camera_model
         slot.buffers((out_hw[0], out_hw[1], 3), _FORMATS[fmt], dev)
         if mode == "rgb":
             out = self.model(data, clamp=False)
@@ -410,9 +417,9 @@ class FrameRenderer:
                     s.copied.synchronize()
 
 
-def viewer_render_func(model) -> Callable[[CameraState], np.ndarray]:
+def viewer_render_func(model, camera_model: str = "pinhole") -> Callable[[CameraState], np.ndarray]:
     """`Viewer(viewer_render_func(gaussian_model), camera_states, ...)`: the reference's `gs_render_func`."""
-    return FrameRenderer(model).render
+    return FrameRenderer(model, camera_model=camera_model).render
 
 
 # ---------------------------------------------------------------------------------------------------------------------------

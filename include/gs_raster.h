@@ -1046,6 +1046,64 @@ int gs_project_bwd_adam_depth(void* stream, int64_t N, int K, int sh_degree, flo
                               int64_t* applied_dev, float* max_radii, float* grad_norm_accum, float* counts, const float* sh_jac,
                               int scale_reg, float max_ratio, float lambda, int budget, double a, double b, const float* v_depths);
 
+/* Camera models (rasterization(camera_model=...); DESIGN.md "Camera models").  Only the projection knows the camera model: the mean
+ * goes to camera space (x, y, z) and is culled on z (near / far) as for the pinhole, cov2 = J cov_c J^T + eps2d I with the model's map
+ * and Jacobian, and everything behind cov2 -- determinant cull, radius, conic, screen cull, tile rectangle, tight culling, and every
+ * stage that consumes means2d / conics / depths / radii / the footprint -- is unchanged.  The SH view direction stays mean - camera centre.
+ *   GS_CAMERA_PINHOLE  (fx x / z + cx, fy y / z + cy), J with the FOV clamp: the entry points without `_cm`
+ *   GS_CAMERA_ORTHO    (fx x + cx, fy y + cy), J = [[fx, 0, 0], [0, fy, 0]], no clamp
+ *   GS_CAMERA_FISHEYE  ideal equidistant, no distortion terms: (fx x k + cx, fy y k + cy), k = theta / r, theta = atan2(r, z),
+ *                      r^2 = x^2 + y^2; J = [[fx (k + x^2 g), fx x y g, -fx x / d^2], [fy x y g, fy (k + y^2 g), -fy y / d^2]] with
+ *                      d^2 = r^2 + z^2, g = (z / d^2 - k) / r^2; no clamp; k, g and (in the VJP) dg/dr come from a series in
+ *                      (r / z)^2 below (r / z)^2 < 1/256, so a Gaussian on the optical axis is an ordinary visible one
+ * The `_cm` entry points take the arguments of the entry point they are named after plus `camera_model` last; with GS_CAMERA_PINHOLE
+ * they are that entry point (same kernels).  The other models: gs_project_fwd_cm stage 2 (colour only) launches the pinhole path's
+ * kernel (the stage has no camera model in it); gs_project_bwd_cm / gs_project_bwd_cam_cm walk the gradient rows (row_sums, stat_grad_norm
+ * and stat_count NULL); the fused backward + Adam exists plain and with the scale-ratio regulariser -- there is no budget, row-sums
+ * or depth variant of it. */
+#define GS_CAMERA_PINHOLE 0
+#define GS_CAMERA_ORTHO 1
+#define GS_CAMERA_FISHEYE 2
+int gs_project_fwd_cm(void* stream, int C, int64_t N, int K, int sh_degree, const float* means, const float* quats,
+                      const float* scales, const float* opacities, const float* colors_in, const float* sh_rest,
+                      int colors_per_camera, const float* viewmats, const float* Ks, int width, int height, float eps2d,
+                      float near_plane, float far_plane, float radius_clip, int tile_culling, int stage, int activations,
+                      int32_t* radii, float* means2d, float* depths, float* conics, float* colors_out, float* rec, uint32_t* bbox,
+                      int32_t* tiles_per_gauss, uint32_t* rect_ref, float* sh_jac, int camera_model);
+int gs_project_bwd_cm(void* stream, int C, int64_t N, int K, int sh_degree, const float* means, const float* quats,
+                      const float* scales, const float* colors_in, const float* sh_rest, int colors_per_camera,
+                      const float* viewmats, const float* Ks, int width, int height, float eps2d, float near_plane, float far_plane,
+                      const int32_t* radii, const float* colors_post, const int32_t* tiles_per_gauss, const int32_t* cum_tiles,
+                      const float* rows, const int32_t* row_base, const uint8_t* qmask, float* v_means, float* v_quats,
+                      float* v_scales, float* v_opacities, float* v_colors, float* v_sh_rest, float* v_means2d_abs,
+                      float* v_means2d, float* v_conics, float* v_colors_post, float* v_colors_pre, const float* opacities,
+                      int activations, const float* sh_jac, const float* row_sums, float* stat_grad_norm, float* stat_count,
+                      int camera_model);
+int gs_project_bwd_cam_cm(void* stream, int C, int64_t N, int K, int sh_degree, const float* means, const float* quats,
+                          const float* scales, const float* colors_in, const float* sh_rest, int colors_per_camera,
+                          const float* viewmats, const float* Ks, int width, int height, float eps2d, float near_plane,
+                          float far_plane, const int32_t* radii, const float* colors_post, const int32_t* tiles_per_gauss,
+                          const int32_t* cum_tiles, const float* rows, const int32_t* row_base, const uint8_t* qmask, float* v_means,
+                          float* v_quats, float* v_scales, float* v_opacities, float* v_colors, float* v_sh_rest,
+                          float* v_means2d_abs, float* v_means2d, float* v_conics, float* v_colors_post, float* v_colors_pre,
+                          const float* opacities, int activations, const float* sh_jac, const float* row_sums,
+                          float* stat_grad_norm, float* stat_count, double* cam_partials, float* v_viewmats, float* v_campos,
+                          int camera_model);
+int gs_project_bwd_adam_cm(void* stream, int64_t N, int K, int sh_degree, float* params, float* exp_avg, float* exp_avg_sq,
+                           const int64_t* offsets_host, const float* viewmats, const float* Ks, int width, int height, float eps2d,
+                           float near_plane, float far_plane, const int32_t* radii, const float* colors_post,
+                           const int32_t* tiles_per_gauss, const int32_t* cum_tiles, const float* rows, const int32_t* row_base,
+                           const uint8_t* qmask, float* v_means2d_abs, float beta1, float beta2, float eps, const float* hyper_dev,
+                           int64_t* applied_dev, float* max_radii, float* grad_norm_accum, float* counts, const float* sh_jac,
+                           int camera_model);
+int gs_project_bwd_adam_reg_cm(void* stream, int64_t N, int K, int sh_degree, float* params, float* exp_avg, float* exp_avg_sq,
+                               const int64_t* offsets_host, const float* viewmats, const float* Ks, int width, int height,
+                               float eps2d, float near_plane, float far_plane, const int32_t* radii, const float* colors_post,
+                               const int32_t* tiles_per_gauss, const int32_t* cum_tiles, const float* rows, const int32_t* row_base,
+                               const uint8_t* qmask, float* v_means2d_abs, float beta1, float beta2, float eps,
+                               const float* hyper_dev, int64_t* applied_dev, float* max_radii, float* grad_norm_accum, float* counts,
+                               const float* sh_jac, float max_ratio, float lambda, int camera_model);
+
 #ifdef __cplusplus
 }
 #endif
