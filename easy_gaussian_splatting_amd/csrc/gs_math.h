@@ -46,6 +46,7 @@ struct Splat2D {
     float A, B, C;   // conic
     float cxx, cyy;  // diagonal of the blurred 2-D covariance (for opacity-aware extents)
     int radius;      // 0 => culled
+    float rho;       // antialiased mode only (project_gaussian_t<.., AA = true>): the opacity compensation, 0 where culled
     int x0, x1, y0, y1;  // tile rectangle of the 3-sigma square (project_gaussian with tile > 0)
 };
 
@@ -148,10 +149,15 @@ struct ProjChainT {
     T j01, j10;                       // the rest of the 2x3 Jacobian (fisheye; pinhole and ortho: zero, and not touched)
     T fk;                             // fisheye: k = theta / r of the mean map
     T a, b, c, det;                   // blurred 2-D covariance and determinant
+    T rho;                            // antialiased mode only (AA): sqrt(det(cov2 before the blur) / det), the opacity's factor
 };
 typedef ProjChainT<preal> ProjChain;
 
-template <typename T, int CAM = kCamPinhole>
+// AA (gsplat's rasterize_mode="antialiased", DESIGN.md "Antialiased mode"; pinhole only): also yields det0 = a0 c0 - b^2 of
+// cov2_0 = J cov_c J^T, formed BEFORE eps2d joins the diagonal (a - eps2d would lose the digits a sub-pixel Gaussian lives on), and
+// rho = sqrt(max(0, det0 / det)), the factor the opacity is multiplied with.  a, b, c and det are formed by the same operations in
+// the same order as without AA.
+template <typename T, int CAM = kCamPinhole, bool AA = false>
 GS_HD bool project_chain(const float* mean, const float* quat, const float* scale,
                          const Camera& cam, float eps2d, float near_p, float far_p,
                          ProjChainT<T>& o) {
@@ -195,6 +201,7 @@ GS_HD bool project_chain(const float* mean, const float* quat, const float* scal
     o.cc12 = t10 * V[6] + t11 * V[7] + t12 * V[8];
     o.cc22 = t20 * V[6] + t21 * V[7] + t22 * V[8];
 
+    static_assert(!AA || CAM == kCamPinhole, "the antialiased mode exists for the pinhole model only");
     const T fx = cam.fx, fy = cam.fy;
     if (CAM != kCamPinhole) {
         // cov2 = J cov_c J^T + eps2d I with the model's J: constant (ortho), or the full 2x3 one (fisheye)
@@ -232,6 +239,19 @@ GS_HD bool project_chain(const float* mean, const float* quat, const float* scal
     o.ty = o.z * (o.clampy > 0 ? limy : (o.clampy < 0 ? -limy : ry));
     o.j00 = fx * rz; o.j11 = fy * rz;
     o.j02 = -fx * o.tx * rz * rz; o.j12 = -fy * o.ty * rz * rz;
+    if (AA) {
+        const T a0 = o.j00 * o.j00 * o.cc00 + T(2) * o.j00 * o.j02 * o.cc02 + o.j02 * o.j02 * o.cc22;
+        o.b = o.j00 * o.j11 * o.cc01 + o.j00 * o.j12 * o.cc02 + o.j02 * o.j11 * o.cc12 + o.j02 * o.j12 * o.cc22;
+        const T c0 = o.j11 * o.j11 * o.cc11 + T(2) * o.j11 * o.j12 * o.cc12 + o.j12 * o.j12 * o.cc22;
+        o.a = a0 + (T)eps2d;
+        o.c = c0 + (T)eps2d;
+        o.det = o.a * o.c - o.b * o.b;
+        const T det0 = a0 * c0 - o.b * o.b;
+        // (det0 <= 0: a rank-deficient covariance, rho = 0 and with it the effective opacity; det <= 0: culled by the caller, which does
+        //  not look at rho then)
+        o.rho = r_sqrt(r_max(T(0), det0 / o.det));
+        return true;
+    }
     o.a = o.j00 * o.j00 * o.cc00 + T(2) * o.j00 * o.j02 * o.cc02 + o.j02 * o.j02 * o.cc22 + (T)eps2d;
     o.b = o.j00 * o.j11 * o.cc01 + o.j00 * o.j12 * o.cc02 + o.j02 * o.j11 * o.cc12 + o.j02 * o.j12 * o.cc22;
     o.c = o.j11 * o.j11 * o.cc11 + T(2) * o.j11 * o.j12 * o.cc12 + o.j12 * o.j12 * o.cc22 + (T)eps2d;
@@ -253,15 +273,16 @@ GS_HD void tile_rect(T mx, T my, int radius, int tile, int tw, int th, int& x0, 
 
 // Appendix A.1: full forward projection of one Gaussian for one camera.  With tile > 0 the tile rectangle of the
 // 3-sigma square is taken from the unrounded centre as well (s.x0..s.y1).
-template <typename T, int CAM = kCamPinhole>
+template <typename T, int CAM = kCamPinhole, bool AA = false>
 GS_HD Splat2D project_gaussian_t(const float* mean, const float* quat, const float* scale,
                                  const Camera& cam, int W, int H, float eps2d, float near_p,
                                  float far_p, float radius_clip, int tile, int tw, int th) {
     Splat2D s;
     s.mx = s.my = s.depth = s.A = s.B = s.C = s.cxx = s.cyy = 0.f;
     s.radius = 0; s.x0 = s.x1 = s.y0 = s.y1 = 0;
+    s.rho = 0.f;
     ProjChainT<T> p;
-    if (!project_chain<T, CAM>(mean, quat, scale, cam, eps2d, near_p, far_p, p)) return s;
+    if (!project_chain<T, CAM, AA>(mean, quat, scale, cam, eps2d, near_p, far_p, p)) return s;
     if (!(p.det > T(0))) return s;
     const T mid = T(0.5) * (p.a + p.c);
     const T lam = mid + r_sqrt(r_max((T)kRadiusDiscFloor, mid * mid - p.det));
@@ -277,6 +298,7 @@ GS_HD Splat2D project_gaussian_t(const float* mean, const float* quat, const flo
     s.A = (float)(p.c * rdet); s.B = (float)(-p.b * rdet); s.C = (float)(p.a * rdet);
     s.cxx = (float)p.a; s.cyy = (float)p.c;
     s.radius = (int)radius;
+    if (AA) s.rho = (float)p.rho;
     if (tile > 0) tile_rect<T>(mx, my, s.radius, tile, tw, th, s.x0, s.x1, s.y0, s.y1);
     return s;
 }
@@ -287,11 +309,11 @@ GS_HD Splat2D project_gaussian(const float* mean, const float* quat, const float
     return project_gaussian_t<preal>(mean, quat, scale, cam, W, H, eps2d, near_p, far_p, radius_clip, tile, tw, th);
 }
 // ... under the camera model CAM (CAM = kCamPinhole is project_gaussian itself)
-template <int CAM>
+template <int CAM, bool AA = false>
 GS_HD Splat2D project_gaussian_cm(const float* mean, const float* quat, const float* scale,
                                   const Camera& cam, int W, int H, float eps2d, float near_p,
                                   float far_p, float radius_clip, int tile = 0, int tw = 0, int th = 0) {
-    return project_gaussian_t<preal, CAM>(mean, quat, scale, cam, W, H, eps2d, near_p, far_p, radius_clip, tile, tw, th);
+    return project_gaussian_t<preal, CAM, AA>(mean, quat, scale, cam, W, H, eps2d, near_p, far_p, radius_clip, tile, tw, th);
 }
 
 // Minimum of the positive-definite form a dx^2 + b dx dy + c dy^2 over the axis-aligned
@@ -532,10 +554,16 @@ GS_HD void sh_dir_term_jac(int degree, const float* G, const float* rgb, const f
 // sums them over the Gaussians of a camera.
 // CAM: the camera model.  Everything but the step from (v_means2d, G = v_cov2) to the camera-space gradient of the mean v_pc = (vx, vy, vz)
 // and to v_covc = J^T G J is the same for all models -- in particular v_t = v_pc and v_A = v_pc mean^T + 2 v_covc A Sigma.
-template <typename T, bool CAMG, int CAM = kCamPinhole>
+// AA: v_rho, the gradient of the chain's rho (the blend's gradient of the record's opacity times the opacity), joins G = v_cov2 in
+// front of everything formed from G:  d rho / d cov2_0 = (adj(cov2_0) - rho^2 adj(cov2)) / (2 rho det), the 2 rho guarded as gsplat
+// guards it (rho + 1e-6: bounded where rho -> 0).  The adjugate of cov2_0 is taken from cov2's entries less aa_eps2d (= eps2d): it
+// is the one place behind rho where a rounding of a - eps2d costs nothing (an ulp of a against a term of the size of eps2d), and the
+// VJP keeps two values fewer alive than with the unblurred diagonal carried over from the chain.
+constexpr double kAaRhoGuard = 1e-6;
+template <typename T, bool CAMG, int CAM = kCamPinhole, bool AA = false>
 GS_HD void project_vjp_impl(const float* mean, const float* scale, const Camera& cam, const ProjChainT<T>& p, float v_mx_f,
                             float v_my_f, float vA_f, float vB_f, float vC_f, float v_depth_f, float* v_mean,
-                            float* v_quat, float* v_scale, T* v_A, T* v_t) {
+                            float* v_quat, float* v_scale, T* v_A, T* v_t, T v_rho = T(0), T aa_eps2d = T(0)) {
     const T v_mx = v_mx_f, v_my = v_my_f, vA = vA_f, vB = vB_f, vC = vC_f, v_depth = v_depth_f;
     const T fx = cam.fx, fy = cam.fy;
     T limx, limy;
@@ -548,9 +576,15 @@ GS_HD void project_vjp_impl(const float* mean, const float* scale, const Camera&
     const T h = T(0.5) * vB;
     const T xv00 = X00 * vA + X01 * h, xv01 = X00 * h + X01 * vC;
     const T xv10 = X01 * vA + X11 * h, xv11 = X01 * h + X11 * vC;
-    const T g00 = -(xv00 * X00 + xv01 * X01);
-    const T g01 = -(xv00 * X01 + xv01 * X11);
-    const T g11 = -(xv10 * X01 + xv11 * X11);
+    T g00 = -(xv00 * X00 + xv01 * X01);
+    T g01 = -(xv00 * X01 + xv01 * X11);
+    T g11 = -(xv10 * X01 + xv11 * X11);
+    if (AA) {
+        const T rho2 = p.rho * p.rho, w = v_rho * T(0.5) / (p.rho + (T)kAaRhoGuard) * rdet;
+        g00 += w * ((p.c - aa_eps2d) - rho2 * p.c);
+        g11 += w * ((p.a - aa_eps2d) - rho2 * p.a);
+        g01 += w * (-p.b * (T(1) - rho2));
+    }
     T vc00, vc01, vc02, vc11, vc12, vc22, vx, vy, vz;
     if (CAM == kCamPinhole) {
         const T j00 = p.j00, j02 = p.j02, j11 = p.j11, j12 = p.j12;
@@ -654,22 +688,22 @@ GS_HD void project_vjp_impl(const float* mean, const float* scale, const Camera&
     v_quat[2] += (float)((vq2 - y * dot) * p.qinv); v_quat[3] += (float)((vq3 - z * dot) * p.qinv);
 }
 
-template <typename T, int CAM = kCamPinhole>
+template <typename T, int CAM = kCamPinhole, bool AA = false>
 GS_HD void project_vjp(const float* scale, const Camera& cam, const ProjChainT<T>& p, float v_mx_f,
                        float v_my_f, float vA_f, float vB_f, float vC_f, float v_depth_f, float* v_mean,
-                       float* v_quat, float* v_scale) {
-    project_vjp_impl<T, false, CAM>(nullptr, scale, cam, p, v_mx_f, v_my_f, vA_f, vB_f, vC_f, v_depth_f, v_mean, v_quat, v_scale,
-                               (T*)nullptr, (T*)nullptr);
+                       float* v_quat, float* v_scale, T v_rho = T(0), T aa_eps2d = T(0)) {
+    project_vjp_impl<T, false, CAM, AA>(nullptr, scale, cam, p, v_mx_f, v_my_f, vA_f, vB_f, vC_f, v_depth_f, v_mean, v_quat, v_scale,
+                               (T*)nullptr, (T*)nullptr, v_rho, aa_eps2d);
 }
 
 // The camera-gradient form: project_vjp (same v_mean / v_quat / v_scale, bit for bit) plus v_A[9] (row-major) and v_t[3] of
 // this (camera, Gaussian) in T -- fp64 in the product, not rounded to fp32 per Gaussian: the sum over a camera's Gaussians
 // cancels heavily (DESIGN.md "Camera gradients").  `mean`: the Gaussian's world-space mean.
-template <typename T, int CAM = kCamPinhole>
+template <typename T, int CAM = kCamPinhole, bool AA = false>
 GS_HD void project_vjp_cam(const float* mean, const float* scale, const Camera& cam, const ProjChainT<T>& p, float v_mx_f,
                            float v_my_f, float vA_f, float vB_f, float vC_f, float v_depth_f, float* v_mean,
-                           float* v_quat, float* v_scale, T* v_A, T* v_t) {
-    project_vjp_impl<T, true, CAM>(mean, scale, cam, p, v_mx_f, v_my_f, vA_f, vB_f, vC_f, v_depth_f, v_mean, v_quat, v_scale, v_A, v_t);
+                           float* v_quat, float* v_scale, T* v_A, T* v_t, T v_rho = T(0), T aa_eps2d = T(0)) {
+    project_vjp_impl<T, true, CAM, AA>(mean, scale, cam, p, v_mx_f, v_my_f, vA_f, vB_f, vC_f, v_depth_f, v_mean, v_quat, v_scale, v_A, v_t, v_rho, aa_eps2d);
 }
 
 // Camera constants from raw viewmat[16] / K[9] (row-major), incl. the general 3x3 inverse for the

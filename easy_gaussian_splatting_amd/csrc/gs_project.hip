@@ -28,6 +28,7 @@ struct ProjFwdArgs {
     int32_t* tiles_per_gauss;
     uint2* rect_ref;   // optional [C*N]: the 3-sigma tile rectangle itself (x0 | x1 << 16, y0 | y1 << 16), whatever `tight` does to bbox
     float4* sh_jac;    // optional, 9 floats per (camera, Gaussian): d(pre-clamp colour)/d(view direction) of the visible Gaussians, for a backward without the coefficients
+    float* compensations;   // antialiased mode (project_fwd_aa_kernel only) [C*N]: rho = sqrt(det(cov2_0) / det(cov2)), 0 where culled
 };
 
 // activations != 0: `scales` / `opacities` hold the reference model's parameters (log-scales, logit
@@ -234,6 +235,7 @@ __device__ __forceinline__ void sh_rows_commit(const ShPrefetch& pf, const float
 template <int DEG, int STAGE>
 __global__ __launch_bounds__(kProjThreads) void project_fwd_kernel(const ProjFwdArgs a) {
     constexpr int CAM = kCamPinhole;
+    constexpr bool AA = false;
 #include "gs_project_fwd_body.h"
 }
 // ... under another camera model (gs_project_fwd_cm: CAM = kCamOrtho, kCamFisheye): the same text around project_gaussian_cm<CAM>.  A kernel
@@ -241,6 +243,16 @@ __global__ __launch_bounds__(kProjThreads) void project_fwd_kernel(const ProjFwd
 template <int DEG, int STAGE, int CAM>
 __global__ __launch_bounds__(kProjThreads) void project_fwd_cm_kernel(const ProjFwdArgs a) {
     static_assert(CAM != kCamPinhole && STAGE != 2, "the pinhole model and the colour stage are project_fwd_kernel's");
+    constexpr bool AA = false;
+#include "gs_project_fwd_body.h"
+}
+// ... in the antialiased mode (gs_project_fwd_aa; pinhole): the record's opacity, the extents and the tile mask take opacity * rho, and rho
+// is left in a.compensations.  Again a template of its own; the colour stage has no opacity in it and stays project_fwd_kernel's.
+template <int DEG, int STAGE>
+__global__ __launch_bounds__(kProjThreads) void project_fwd_aa_kernel(const ProjFwdArgs a) {
+    static_assert(STAGE != 2, "the colour stage is project_fwd_kernel's");
+    constexpr int CAM = kCamPinhole;
+    constexpr bool AA = true;
 #include "gs_project_fwd_body.h"
 }
 
@@ -290,6 +302,9 @@ struct ProjBwdArgs {
     // Depth supervision (gs_project_bwd_adam_depth; REG & 4 only): v_z per Gaussian from gs_depth_grads_z -- v_z times row 2 of the view
     // matrix joins v_mean behind the projection's VJP, as gs_depth_grads adds it to the gradient gs_project_bwd wrote
     const float* v_depths;
+    // Antialiased mode (project_bwd_aa_kernel only): optional [C*N], the row sum's gradient of the record's opacity as it is -- what
+    // the camera-gradient kernel needs per (camera, Gaussian) to form v_rho (gs_project_bwd_cam_aa)
+    float* v_op_rec;
 };
 
 __device__ __forceinline__ float* adam_p(const ProjBwdArgs& a, int t) { return a.ad_pbase + a.ad_off[t]; }
@@ -629,12 +644,13 @@ __device__ __forceinline__ void row_sum_wave(const A& a, int nr, int r0, int bas
 template <int DEG, bool ADAM, bool SUMS = false, bool SCALE_REG = false>
 __global__ __launch_bounds__(kProjThreads) void project_bwd_kernel(const ProjBwdArgs a) {
     constexpr int REG = SCALE_REG ? 1 : 0, CAM = kCamPinhole;
+    constexpr bool AA = false;
 #include "gs_project_bwd_body.h"
 }
 // the fused form under a Gaussian budget (gs_project_bwd_adam_mcmc): REG = 2 the budget term alone, 3 behind the scale-ratio term
 template <int DEG, int REG, bool SUMS = false>
 __global__ __launch_bounds__(kProjThreads) void project_bwd_budget_kernel(const ProjBwdArgs a) {
-    constexpr bool ADAM = true;
+    constexpr bool ADAM = true, AA = false;
     constexpr int CAM = kCamPinhole;
 #include "gs_project_bwd_body.h"
 }
@@ -642,7 +658,7 @@ __global__ __launch_bounds__(kProjThreads) void project_bwd_budget_kernel(const 
 // the fused form with a depth gradient (gs_project_bwd_adam_depth): REG = 4 | the two regularisers' bits
 template <int DEG, int REG>
 __global__ __launch_bounds__(kProjThreads) void project_bwd_depth_kernel(const ProjBwdArgs a) {
-    constexpr bool ADAM = true, SUMS = false;
+    constexpr bool ADAM = true, SUMS = false, AA = false;
     constexpr int CAM = kCamPinhole;
 #include "gs_project_bwd_body.h"
 }
@@ -653,7 +669,18 @@ __global__ __launch_bounds__(kProjThreads) void project_bwd_depth_kernel(const P
 template <int DEG, bool ADAM, int REG, int CAM>
 __global__ __launch_bounds__(kProjThreads) void project_bwd_cm_kernel(const ProjBwdArgs a) {
     static_assert(CAM != kCamPinhole && (REG == 0 || (ADAM && REG == 1)), "pinhole: project_bwd_kernel; REG: the scale-ratio term, fused form only");
-    constexpr bool SUMS = false;
+    constexpr bool SUMS = false, AA = false;
+#include "gs_project_bwd_body.h"
+}
+
+// the eager and the fused form (REG = 0, or 1: the scale-ratio regulariser) in the antialiased mode (gs_project_bwd_aa, gs_project_bwd_adam_aa,
+// gs_project_bwd_adam_reg_aa; pinhole): the opacity's gradient is the record's times rho, and v_rho joins v_cov2 inside the chain's VJP.
+// The gradient rows are walked (no SUMS form); the budget and depth variants of the fused form do not exist in this mode.
+template <int DEG, bool ADAM, int REG>
+__global__ __launch_bounds__(kProjThreads) void project_bwd_aa_kernel(const ProjBwdArgs a) {
+    static_assert(REG == 0 || (ADAM && REG == 1), "REG: the scale-ratio term, fused form only");
+    constexpr bool SUMS = false, AA = true;
+    constexpr int CAM = kCamPinhole;
 #include "gs_project_bwd_body.h"
 }
 
@@ -828,6 +855,8 @@ struct ProjCamArgs {
     const float4* row_sums;   // SUMS: gs_row_sums' [N][12] in their place (C = 1)
     double* cam_partials;     // [C][gridDim.x][16]
     const int64_t* guard;
+    // antialiased mode (project_cam_aa_kernel only): the opacities (raw with activations) and project_bwd_aa_kernel's v_op_rec [C*N]
+    const float *opacities, *v_op_rec;
 };
 
 constexpr int kCamTerms = 15;
@@ -837,6 +866,7 @@ constexpr int kCamTerms = 15;
 template <int DEG, bool SUMS = false>
 __global__ __launch_bounds__(kProjThreads) void project_cam_kernel(const ProjCamArgs a) {
     constexpr int CAM = kCamPinhole;
+    constexpr bool AA = false;
 #include "gs_project_cam_body.h"
 }
 // ... under another camera model (gs_project_bwd_cam_cm): v_t = v_pc and v_A = v_pc mean^T + 2 v_covc A Sigma hold for any model once the
@@ -844,7 +874,14 @@ __global__ __launch_bounds__(kProjThreads) void project_cam_kernel(const ProjCam
 template <int DEG, int CAM>
 __global__ __launch_bounds__(kProjThreads) void project_cam_cm_kernel(const ProjCamArgs a) {
     static_assert(CAM != kCamPinhole, "the pinhole model is project_cam_kernel's");
-    constexpr bool SUMS = false;
+    constexpr bool SUMS = false, AA = false;
+#include "gs_project_cam_body.h"
+}
+// ... in the antialiased mode (gs_project_bwd_cam_aa; pinhole): the VJP with v_rho in it
+template <int DEG>
+__global__ __launch_bounds__(kProjThreads) void project_cam_aa_kernel(const ProjCamArgs a) {
+    constexpr bool SUMS = false, AA = true;
+    constexpr int CAM = kCamPinhole;
 #include "gs_project_cam_body.h"
 }
 
@@ -978,8 +1015,11 @@ static int project_fwd(void* stream, int C, int64_t N, int K, int sh_degree, con
                        float eps2d, float near_plane, float far_plane, float radius_clip,
                        int tile_culling, int stage, int activations, int32_t* radii,
                        float* means2d, float* depths, float* conics, float* colors_out, float* rec,
-                       uint32_t* bbox, int32_t* tiles_per_gauss, uint32_t* rect_ref, float* sh_jac, int camera_model) {
+                       uint32_t* bbox, int32_t* tiles_per_gauss, uint32_t* rect_ref, float* sh_jac, int camera_model,
+                       bool aa = false, float* compensations = nullptr) {
     GS_REQUIRE_CAMERA(camera_model);
+    GS_REQUIRE(!aa || camera_model == GS_CAMERA_PINHOLE, "the antialiased mode exists for the pinhole model only");
+    GS_REQUIRE(!aa || N == 0 || compensations, "compensations must not be NULL");
     GS_REQUIRE(C >= 1 && N >= 0 && width > 0 && height > 0, "C>=1, N>=0, positive image size");
     GS_REQUIRE(sh_degree <= 4, "sh_degree must be <= 4");
     GS_REQUIRE(sh_degree < 0 || (K >= (sh_degree + 1) * (sh_degree + 1) && K <= 25), "K must hold (sh_degree+1)^2 coefficients and be <= 25");
@@ -999,6 +1039,7 @@ static int project_fwd(void* stream, int C, int64_t N, int K, int sh_degree, con
     a.bbox = reinterpret_cast<uint4*>(bbox); a.tiles_per_gauss = tiles_per_gauss;
     a.rect_ref = reinterpret_cast<uint2*>(rect_ref);
     a.sh_jac = sh_degree >= 1 ? reinterpret_cast<float4*>(sh_jac) : nullptr;
+    a.compensations = compensations;
     dim3 grid((unsigned)((N + kProjThreads - 1) / kProjThreads), (unsigned)C);
     const size_t lds = proj_lds_bytes(K, sh_degree);
     hipStream_t st = (hipStream_t)stream;
@@ -1029,6 +1070,22 @@ static int project_fwd(void* stream, int C, int64_t N, int K, int sh_degree, con
         case 4: GS_PFC(4, 0, M); break;                                   \
         default: GS_PFC(-1, 0, M); break;                                 \
     }
+    // the antialiased mode: as for the camera models -- a kernel per degree for the one-launch form, one for the geometry stage, and the
+    // colour stage (no opacity in it) the classic kernel
+#define GS_PFA(D, S)                                                                                             \
+    { if ((S) != 1) GS_LDS((project_fwd_aa_kernel<D, S>));                                                       \
+      hipLaunchKernelGGL((project_fwd_aa_kernel<D, S>), grid, dim3(kProjThreads), (S) == 1 ? proj_lds_bytes(K, -1) : lds, st, a); }
+    if (aa && stage != 2) {
+        if (stage == 1) GS_PFA(-1, 1) else switch (sh_degree) {
+            case 0: GS_PFA(0, 0); break;
+            case 1: GS_PFA(1, 0); break;
+            case 2: GS_PFA(2, 0); break;
+            case 3: GS_PFA(3, 0); break;
+            case 4: GS_PFA(4, 0); break;
+            default: GS_PFA(-1, 0); break;
+        }
+    } else
+#undef GS_PFA
     if (camera_model == GS_CAMERA_ORTHO && stage != 2) { GS_PFC_DEG(kCamOrtho) }
     else if (camera_model == GS_CAMERA_FISHEYE && stage != 2) { GS_PFC_DEG(kCamFisheye) }
     else if (stage == 0) { GS_PF_DEG(0) } else if (stage == 1) { GS_PF_DEG(1) } else { GS_PF_DEG(2) }
@@ -1067,6 +1124,20 @@ extern "C" int gs_project_fwd_cm(void* stream, int C, int64_t N, int K, int sh_d
                        conics, colors_out, rec, bbox, tiles_per_gauss, rect_ref, sh_jac, camera_model);
 }
 
+// gs_project_fwd in the antialiased mode (pinhole): + compensations [C*N], never NULL
+extern "C" int gs_project_fwd_aa(void* stream, int C, int64_t N, int K, int sh_degree, const float* means,
+                                 const float* quats, const float* scales, const float* opacities,
+                                 const float* colors_in, const float* sh_rest, int colors_per_camera,
+                                 const float* viewmats, const float* Ks, int width, int height,
+                                 float eps2d, float near_plane, float far_plane, float radius_clip,
+                                 int tile_culling, int stage, int activations, int32_t* radii,
+                                 float* means2d, float* depths, float* conics, float* colors_out, float* rec,
+                                 uint32_t* bbox, int32_t* tiles_per_gauss, uint32_t* rect_ref, float* sh_jac, float* compensations) {
+    return project_fwd(stream, C, N, K, sh_degree, means, quats, scales, opacities, colors_in, sh_rest, colors_per_camera, viewmats, Ks,
+                       width, height, eps2d, near_plane, far_plane, radius_clip, tile_culling, stage, activations, radii, means2d, depths,
+                       conics, colors_out, rec, bbox, tiles_per_gauss, rect_ref, sh_jac, GS_CAMERA_PINHOLE, true, compensations);
+}
+
 static int project_bwd(void* stream, int C, int64_t N, int K, int sh_degree, const float* means,
                               const float* quats, const float* scales, const float* colors_in,
                               const float* sh_rest, int colors_per_camera, const float* viewmats,
@@ -1078,9 +1149,12 @@ static int project_bwd(void* stream, int C, int64_t N, int K, int sh_degree, con
                               float* v_opacities, float* v_colors, float* v_sh_rest, float* v_means2d_abs,
                               float* v_means2d, float* v_conics, float* v_colors_post, float* v_colors_pre,
                               const float* opacities, int activations, const float* sh_jac, const float* row_sums,
-                              float* stat_grad_norm, float* stat_count, int camera_model) {
+                              float* stat_grad_norm, float* stat_count, int camera_model, bool aa = false, float* v_op_rec = nullptr) {
     GS_REQUIRE_CAMERA(camera_model);
     GS_REQUIRE(camera_model == GS_CAMERA_PINHOLE || !row_sums, "row_sums (the view-parallel step's form) exist for the pinhole model only");
+    GS_REQUIRE(!aa || (camera_model == GS_CAMERA_PINHOLE && !row_sums), "the antialiased mode: the pinhole model, the gradient rows walked (no row_sums)");
+    GS_REQUIRE(!aa || N == 0 || opacities, "the antialiased mode needs the opacities");
+    GS_REQUIRE(!aa || current_rounds().phase == 0, "the antialiased mode is one-round only");
     GS_REQUIRE(C >= 1 && N >= 0 && width > 0 && height > 0, "C>=1, N>=0, positive image size");
     GS_REQUIRE((stat_grad_norm == nullptr) == (stat_count == nullptr) && (!stat_count || (C == 1 && row_sums)),
                "stat_grad_norm / stat_count: both or neither, single camera, together with row_sums");
@@ -1112,6 +1186,7 @@ static int project_bwd(void* stream, int C, int64_t N, int K, int sh_degree, con
     a.ad_pbase = a.ad_mbase = a.ad_vbase = nullptr;
     for (int t = 0; t < 6; ++t) a.ad_off[t] = 0;
     a.reg_ratio = a.reg_grad = 0.f;
+    a.v_op_rec = v_op_rec;
     dim3 grid((unsigned)((N + kProjThreads - 1) / kProjThreads));
     const size_t lds = proj_bwd_lds_bytes(K, sh_degree);
     hipStream_t st = (hipStream_t)stream;
@@ -1121,6 +1196,7 @@ static int project_bwd(void* stream, int C, int64_t N, int K, int sh_degree, con
         a.cam = c; a.accumulate = c > 0;
 #define GS_PBC(D, M) { GS_LDS((project_bwd_cm_kernel<D, false, 0, M>)); hipLaunchKernelGGL((project_bwd_cm_kernel<D, false, 0, M>), grid, dim3(kProjThreads), lds, st, a); }
 #define GS_PB(D)                                                                                                        \
+        if (aa) { GS_LDS((project_bwd_aa_kernel<D, false, 0>)); hipLaunchKernelGGL((project_bwd_aa_kernel<D, false, 0>), grid, dim3(kProjThreads), lds, st, a); } else \
         if (camera_model == GS_CAMERA_ORTHO) GS_PBC(D, kCamOrtho) else if (camera_model == GS_CAMERA_FISHEYE) GS_PBC(D, kCamFisheye) else \
         if (row_sums) { GS_LDS((project_bwd_kernel<D, false, true>)); hipLaunchKernelGGL((project_bwd_kernel<D, false, true>), grid, dim3(kProjThreads), lds, st, a); } \
         else { GS_LDS((project_bwd_kernel<D, false, false>)); hipLaunchKernelGGL((project_bwd_kernel<D, false, false>), grid, dim3(kProjThreads), lds, st, a); }
@@ -1178,10 +1254,37 @@ extern "C" int gs_project_bwd_cm(void* stream, int C, int64_t N, int K, int sh_d
                        stat_grad_norm, stat_count, camera_model);
 }
 
+// gs_project_bwd in the antialiased mode (pinhole; opacities never NULL; the gradient rows are walked: row_sums NULL)
+extern "C" int gs_project_bwd_aa(void* stream, int C, int64_t N, int K, int sh_degree, const float* means,
+                              const float* quats, const float* scales, const float* colors_in,
+                              const float* sh_rest, int colors_per_camera, const float* viewmats,
+                              const float* Ks, int width,
+                              int height, float eps2d, float near_plane, float far_plane,
+                              const int32_t* radii, const float* colors_post,
+                              const int32_t* tiles_per_gauss, const int32_t* cum_tiles,
+                              const float* rows, const int32_t* row_base, const uint8_t* qmask, float* v_means, float* v_quats, float* v_scales,
+                              float* v_opacities, float* v_colors, float* v_sh_rest, float* v_means2d_abs,
+                              float* v_means2d, float* v_conics, float* v_colors_post, float* v_colors_pre,
+                              const float* opacities, int activations, const float* sh_jac, const float* row_sums,
+                              float* stat_grad_norm, float* stat_count) {
+    return project_bwd(stream, C, N, K, sh_degree, means, quats, scales, colors_in, sh_rest, colors_per_camera, viewmats, Ks,
+                       width, height, eps2d, near_plane, far_plane, radii, colors_post, tiles_per_gauss, cum_tiles, rows,
+                       row_base, qmask, v_means, v_quats, v_scales, v_opacities, v_colors, v_sh_rest, v_means2d_abs,
+                       v_means2d, v_conics, v_colors_post, v_colors_pre, opacities, activations, sh_jac, row_sums,
+                       stat_grad_norm, stat_count, GS_CAMERA_PINHOLE, true);
+}
+
 
 extern "C" size_t gs_cam_partials_doubles(int C, int64_t N) {
     if (C < 1 || N < 0) return 0;
     return (size_t)C * (size_t)((N + kProjThreads - 1) / kProjThreads) * 16;
+}
+
+// The antialiased mode's partials: gs_cam_partials_doubles' blocks, and behind them C*N floats -- the record-opacity gradient the projection
+// backward leaves per (camera, Gaussian) for the camera kernel (ProjBwdArgs::v_op_rec)
+extern "C" size_t gs_cam_partials_doubles_aa(int C, int64_t N) {
+    if (C < 1 || N < 0) return 0;
+    return gs_cam_partials_doubles(C, N) + ((size_t)C * (size_t)N + 1) / 2;
 }
 
 static int project_bwd_cam(int camera_model, void* stream, int C, int64_t N, int K, int sh_degree, const float* means,
@@ -1196,7 +1299,7 @@ static int project_bwd_cam(int camera_model, void* stream, int C, int64_t N, int
                                   float* v_means2d, float* v_conics, float* v_colors_post, float* v_colors_pre,
                                   const float* opacities, int activations, const float* sh_jac, const float* row_sums,
                                   float* stat_grad_norm, float* stat_count, double* cam_partials, float* v_viewmats,
-                                  float* v_campos) {
+                                  float* v_campos, bool aa = false) {
     GS_REQUIRE_CAMERA(camera_model);
     GS_REQUIRE(C >= 1 && N >= 0, "C>=1, N>=0");
     GS_REQUIRE(v_viewmats && v_campos && (N == 0 || cam_partials), "null camera-gradient pointer");
@@ -1214,7 +1317,8 @@ static int project_bwd_cam(int camera_model, void* stream, int C, int64_t N, int
                              width, height, eps2d, near_plane, far_plane, radii, colors_post, tiles_per_gauss, cum_tiles, rows,
                              row_base, qmask, v_means, v_quats, v_scales, v_opacities, v_colors, v_sh_rest, v_means2d_abs,
                              v_means2d, v_conics, v_colors_post, v_colors_pre, opacities, activations, sh_jac, row_sums,
-                             stat_grad_norm, stat_count, camera_model))
+                             stat_grad_norm, stat_count, camera_model, aa,
+                             aa ? reinterpret_cast<float*>(cam_partials + gs_cam_partials_doubles(C, N)) : nullptr))
         return rc;
     ProjCamArgs a;
     a.K = K; a.W = width; a.H = height; a.activations = activations != 0; a.N = N;
@@ -1226,9 +1330,11 @@ static int project_bwd_cam(int camera_model, void* stream, int C, int64_t N, int
     a.radii = radii; a.sh_jac = sh_degree >= 1 ? reinterpret_cast<const float4*>(sh_jac) : nullptr;
     a.v_means2d = v_means2d; a.v_conics = v_conics; a.v_colors_post = v_colors_post; a.row_sums = nullptr;
     a.cam_partials = cam_partials; a.guard = current_guard().info;
+    a.opacities = opacities; a.v_op_rec = aa ? reinterpret_cast<const float*>(cam_partials + gs_cam_partials_doubles(C, N)) : nullptr;
     const int n_blocks = (int)((N + kProjThreads - 1) / kProjThreads);
     dim3 grid((unsigned)n_blocks, (unsigned)C);
 #define GS_PC(D)                                                                                                                         \
+    if (aa) hipLaunchKernelGGL((project_cam_aa_kernel<D>), grid, dim3(kProjThreads), 0, st, a); else                                     \
     if (camera_model == GS_CAMERA_ORTHO) hipLaunchKernelGGL((project_cam_cm_kernel<D, kCamOrtho>), grid, dim3(kProjThreads), 0, st, a);          \
     else if (camera_model == GS_CAMERA_FISHEYE) hipLaunchKernelGGL((project_cam_cm_kernel<D, kCamFisheye>), grid, dim3(kProjThreads), 0, st, a); \
     else hipLaunchKernelGGL((project_cam_kernel<D>), grid, dim3(kProjThreads), 0, st, a)
@@ -1263,6 +1369,26 @@ extern "C" int gs_project_bwd_cam(void* stream, int C, int64_t N, int K, int sh_
                        row_base, qmask, v_means, v_quats, v_scales, v_opacities, v_colors, v_sh_rest, v_means2d_abs,
                        v_means2d, v_conics, v_colors_post, v_colors_pre, opacities, activations, sh_jac, row_sums,
                        stat_grad_norm, stat_count, cam_partials, v_viewmats, v_campos);
+}
+
+// gs_project_bwd_cam in the antialiased mode (pinhole): cam_partials holds gs_cam_partials_doubles_aa(C, N) doubles
+extern "C" int gs_project_bwd_cam_aa(void* stream, int C, int64_t N, int K, int sh_degree, const float* means,
+                              const float* quats, const float* scales, const float* colors_in,
+                              const float* sh_rest, int colors_per_camera, const float* viewmats,
+                              const float* Ks, int width,
+                              int height, float eps2d, float near_plane, float far_plane,
+                              const int32_t* radii, const float* colors_post,
+                              const int32_t* tiles_per_gauss, const int32_t* cum_tiles,
+                              const float* rows, const int32_t* row_base, const uint8_t* qmask, float* v_means, float* v_quats, float* v_scales,
+                              float* v_opacities, float* v_colors, float* v_sh_rest, float* v_means2d_abs,
+                              float* v_means2d, float* v_conics, float* v_colors_post, float* v_colors_pre,
+                              const float* opacities, int activations, const float* sh_jac, const float* row_sums,
+                              float* stat_grad_norm, float* stat_count, double* cam_partials, float* v_viewmats, float* v_campos) {
+    return project_bwd_cam(GS_CAMERA_PINHOLE, stream, C, N, K, sh_degree, means, quats, scales, colors_in, sh_rest, colors_per_camera, viewmats, Ks,
+                       width, height, eps2d, near_plane, far_plane, radii, colors_post, tiles_per_gauss, cum_tiles, rows,
+                       row_base, qmask, v_means, v_quats, v_scales, v_opacities, v_colors, v_sh_rest, v_means2d_abs,
+                       v_means2d, v_conics, v_colors_post, v_colors_pre, opacities, activations, sh_jac, row_sums,
+                       stat_grad_norm, stat_count, cam_partials, v_viewmats, v_campos, true);
 }
 
 // gs_project_bwd_cam under the camera model `camera_model` (GS_CAMERA_PINHOLE: that very call)
@@ -1312,6 +1438,7 @@ extern "C" int gs_cam_grad_sums(void* stream, int64_t N, int K, int sh_degree, c
     a.radii = radii; a.sh_jac = sh_degree >= 1 ? reinterpret_cast<const float4*>(sh_jac) : nullptr;
     a.v_means2d = a.v_conics = a.v_colors_post = nullptr; a.row_sums = reinterpret_cast<const float4*>(row_sums);
     a.cam_partials = cam_partials; a.guard = current_guard().info;
+    a.opacities = a.v_op_rec = nullptr;
     const int n_blocks = (int)((N + kProjThreads - 1) / kProjThreads);
     dim3 grid((unsigned)n_blocks, 1u);
 #define GS_PC(D) hipLaunchKernelGGL((project_cam_kernel<D, true>), grid, dim3(kProjThreads), 0, st, a)
@@ -1342,8 +1469,12 @@ static int project_bwd_adam(void* stream, int64_t N, int K, int sh_degree, float
                             float* v_means2d_abs, float beta1, float beta2, float eps, const float* hyper_dev,
                             int64_t* applied_dev, float* max_radii, float* grad_norm_accum, float* counts,
                             const float* sh_jac, int reg, float max_ratio, float lambda, double bud_a, double bud_b,
-                            const float* row_sums = nullptr, const float* v_depths = nullptr, int camera_model = GS_CAMERA_PINHOLE) {
+                            const float* row_sums = nullptr, const float* v_depths = nullptr, int camera_model = GS_CAMERA_PINHOLE,
+                            bool aa = false) {
     GS_REQUIRE_CAMERA(camera_model);
+    GS_REQUIRE(!aa || (camera_model == GS_CAMERA_PINHOLE && !(reg & 2) && !row_sums && !v_depths),
+               "the antialiased mode: the pinhole model; no budget, row-sums or depth variant of the fused backward exists for it");
+    GS_REQUIRE(!aa || current_rounds().phase == 0, "the antialiased mode is one-round only");
     GS_REQUIRE(camera_model == GS_CAMERA_PINHOLE || (!(reg & 2) && !row_sums && !v_depths),
                "the budget, row-sums and depth variants of the fused backward exist for the pinhole model only");
     GS_REQUIRE(N >= 0 && width > 0 && height > 0, "N>=0, positive image size");
@@ -1379,6 +1510,7 @@ static int project_bwd_adam(void* stream, int64_t N, int K, int sh_degree, float
     a.reg_ratio = max_ratio; a.reg_grad = (reg & 1) ? scale_reg_upstream(lambda, N) : 0.f;
     a.bud_ga = (reg & 2) ? budget_reg_upstream(bud_a, N) : 0.f; a.bud_gb = (reg & 2) ? budget_reg_upstream(bud_b, 3 * N) : 0.f;
     a.v_depths = v_depths;
+    a.v_op_rec = nullptr;
     dim3 grid((unsigned)((N + kProjThreads - 1) / kProjThreads));
     const size_t lds = proj_bwd_lds_bytes(K, sh_degree);
     hipStream_t st = (hipStream_t)stream;
@@ -1391,6 +1523,7 @@ static int project_bwd_adam(void* stream, int64_t N, int K, int sh_degree, float
     if (reg == 1) GS_PBK(project_bwd_cm_kernel<D, true, 1, ((D) == 4 && (M) == kCamFisheye) ? kCamFisheyeSelect : (M)>)                   \
     else GS_PBK(project_bwd_cm_kernel<D, true, 0, M>)
 #define GS_PB(D)                                                                                                        \
+    if (aa) { if (reg == 1) GS_PBK(project_bwd_aa_kernel<D, true, 1>) else GS_PBK(project_bwd_aa_kernel<D, true, 0>) } else \
     if (camera_model == GS_CAMERA_ORTHO) { GS_PBC(D, kCamOrtho) } else if (camera_model == GS_CAMERA_FISHEYE) { GS_PBC(D, kCamFisheye) } else \
     if (v_depths) {                                                                                                     \
         if (reg == 3) GS_PBK(project_bwd_depth_kernel<D, 7>) else if (reg == 2) GS_PBK(project_bwd_depth_kernel<D, 6>)                  \
@@ -1465,6 +1598,33 @@ extern "C" int gs_project_bwd_adam_reg_cm(void* stream, int64_t N, int K, int sh
                             near_plane, far_plane, radii, colors_post, tiles_per_gauss, cum_tiles, rows, row_base, qmask, v_means2d_abs,
                             beta1, beta2, eps, hyper_dev, applied_dev, max_radii, grad_norm_accum, counts, sh_jac, 1, max_ratio, lambda, 0.0, 0.0,
                             nullptr, nullptr, camera_model);
+}
+
+// gs_project_bwd_adam / gs_project_bwd_adam_reg in the antialiased mode (pinhole)
+extern "C" int gs_project_bwd_adam_aa(void* stream, int64_t N, int K, int sh_degree, float* params, float* exp_avg, float* exp_avg_sq,
+                                   const int64_t* offsets_host, const float* viewmats, const float* Ks, int width, int height,
+                                   float eps2d, float near_plane, float far_plane, const int32_t* radii, const float* colors_post,
+                                   const int32_t* tiles_per_gauss, const int32_t* cum_tiles, const float* rows, const int32_t* row_base, const uint8_t* qmask,
+                                   float* v_means2d_abs, float beta1, float beta2, float eps, const float* hyper_dev,
+                                   int64_t* applied_dev, float* max_radii, float* grad_norm_accum, float* counts,
+                                   const float* sh_jac) {
+    return project_bwd_adam(stream, N, K, sh_degree, params, exp_avg, exp_avg_sq, offsets_host, viewmats, Ks, width, height, eps2d,
+                            near_plane, far_plane, radii, colors_post, tiles_per_gauss, cum_tiles, rows, row_base, qmask, v_means2d_abs,
+                            beta1, beta2, eps, hyper_dev, applied_dev, max_radii, grad_norm_accum, counts, sh_jac, 0, 0.f, 0.f, 0.0, 0.0,
+                            nullptr, nullptr, GS_CAMERA_PINHOLE, true);
+}
+extern "C" int gs_project_bwd_adam_reg_aa(void* stream, int64_t N, int K, int sh_degree, float* params, float* exp_avg, float* exp_avg_sq,
+                                   const int64_t* offsets_host, const float* viewmats, const float* Ks, int width, int height,
+                                   float eps2d, float near_plane, float far_plane, const int32_t* radii, const float* colors_post,
+                                   const int32_t* tiles_per_gauss, const int32_t* cum_tiles, const float* rows, const int32_t* row_base, const uint8_t* qmask,
+                                   float* v_means2d_abs, float beta1, float beta2, float eps, const float* hyper_dev,
+                                   int64_t* applied_dev, float* max_radii, float* grad_norm_accum, float* counts,
+                                   const float* sh_jac, float max_ratio, float lambda) {
+    GS_REQUIRE(((uintptr_t)params & 3) == 0, "params must be 4-byte aligned");
+    return project_bwd_adam(stream, N, K, sh_degree, params, exp_avg, exp_avg_sq, offsets_host, viewmats, Ks, width, height, eps2d,
+                            near_plane, far_plane, radii, colors_post, tiles_per_gauss, cum_tiles, rows, row_base, qmask, v_means2d_abs,
+                            beta1, beta2, eps, hyper_dev, applied_dev, max_radii, grad_norm_accum, counts, sh_jac, 1, max_ratio, lambda, 0.0, 0.0,
+                            nullptr, nullptr, GS_CAMERA_PINHOLE, true);
 }
 
 // ... with the budget regulariser's gradients in v_opacity and v_scale (its value: gs_mcmc_reg in front of this call), behind the

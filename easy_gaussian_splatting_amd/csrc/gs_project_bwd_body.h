@@ -1,5 +1,5 @@
 // The body of project_bwd_kernel / project_bwd_budget_kernel / project_bwd_depth_kernel / project_bwd_cm_kernel (gs_project.hip), which define DEG, ADAM,
-// SUMS, the mask REG and the camera model CAM around it.
+// SUMS, the mask REG, the camera model CAM and the antialiased mode AA around it.
 // Included once per kernel template, inside its braces: no include guard, nothing but the body.
     extern __shared__ __attribute__((aligned(16))) float smem[];
     if (guard_tripped(a.guard)) return;
@@ -116,6 +116,7 @@
 
     // ---- 3. projection VJP
     float sc_fac[3] = {1.f, 1.f, 1.f}, op_fac = 1.f;   // d activated / d raw (identity without activations)
+    float aa_vop = 0.f;   // (AA) the activated opacity's gradient: the record opacity's (s.v[7]) times d record / d activated = the chain's rho
     if (vis) {
         const float4 q4 = reinterpret_cast<const float4*>(p_quats)[n];
         const float quat[4] = {q4.x, q4.y, q4.z, q4.w};
@@ -123,8 +124,16 @@
                                 act_scale(p_scales[3 * n + 2], a.activations)};
         if (a.activations) { sc_fac[0] = scale[0]; sc_fac[1] = scale[1]; sc_fac[2] = scale[2]; }
         ProjChainT<preal> p;
-        if (project_chain<preal, CAM>(mean, quat, scale, cam, a.eps2d, a.near_p, a.far_p, p))
-            project_vjp<preal, CAM>(scale, cam, p, s.v[0], s.v[1], s.v[4], s.v[5], s.v[6], 0.f, v_mean, v_quat, v_scale);
+        // (AA) s.v[7] is the gradient of the record's opacity, opacity * rho: times the opacity it reaches rho and through it cov2_0
+        if (project_chain<preal, CAM, AA>(mean, quat, scale, cam, a.eps2d, a.near_p, a.far_p, p)) {
+            preal v_rho = 0;
+            if (AA) v_rho = (preal)s.v[7] * (preal)act_opacity(p_opac[n], a.activations);
+            project_vjp<preal, CAM, AA>(scale, cam, p, s.v[0], s.v[1], s.v[4], s.v[5], s.v[6], 0.f, v_mean, v_quat, v_scale, v_rho, (preal)a.eps2d);
+            if (AA) {
+                if (!ADAM && a.v_op_rec) a.v_op_rec[f] = s.v[7];   // (gs_project_bwd_cam_aa: the camera kernel forms v_rho from it)
+                aa_vop = s.v[7] * (float)p.rho;
+            }
+        }
     }
     if ((REG & 4) && in_range) {   // + the depth channel's gradient (culled Gaussians: v_z = 0), onto the rounded v_mean as gs_depth_grads adds it
         const float row2[3] = {lds_cam[6], lds_cam[7], lds_cam[8]};   // (make_camera: R[6..8] = row 2 of the view matrix, as it lies there)
@@ -141,6 +150,7 @@
             v_scale[0] = fp_opaque(v_scale[0]) + gl[0]; v_scale[1] = fp_opaque(v_scale[1]) + gl[1]; v_scale[2] = fp_opaque(v_scale[2]) + gl[2];
         }
         float v_op = s.v[7] * op_fac;
+        if (AA) v_op = aa_vop * op_fac;
         if (REG & 2) {   // + the budget regulariser's gradients, as gs_mcmc_reg adds them to the gradients gs_project_bwd wrote
             double o, sk[3];
             float go, gl[3];

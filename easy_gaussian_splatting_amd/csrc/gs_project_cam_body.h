@@ -1,4 +1,5 @@
-// The body of project_cam_kernel / project_cam_cm_kernel (gs_project.hip), which define DEG, SUMS and the camera model CAM around it.
+// The body of project_cam_kernel / project_cam_cm_kernel (gs_project.hip), which define DEG, SUMS, the camera model CAM and the
+// antialiased mode AA around it.
 // Included once per kernel template, inside its braces: no include guard, nothing but the body.
     __shared__ float lds_cam[32];
     __shared__ double wave_sums[kProjThreads / 64][16];
@@ -36,7 +37,7 @@
             acc[12] = -(double)term[0]; acc[13] = -(double)term[1]; acc[14] = -(double)term[2];
         }
         ProjChainT<preal> p;
-        if (project_chain<preal, CAM>(mean, quat, scale, cam, a.eps2d, a.near_p, a.far_p, p)) {
+        if (project_chain<preal, CAM, AA>(mean, quat, scale, cam, a.eps2d, a.near_p, a.far_p, p)) {
             float v_mean[3] = {0.f, 0.f, 0.f}, v_quat[4] = {0.f, 0.f, 0.f, 0.f}, v_scale[3] = {0.f, 0.f, 0.f};   // (not used here)
             float2 vm;
             float vc[3];
@@ -47,6 +48,10 @@
                 vm = reinterpret_cast<const float2*>(a.v_means2d)[f];
                 vc[0] = a.v_conics[3 * f]; vc[1] = a.v_conics[3 * f + 1]; vc[2] = a.v_conics[3 * f + 2];
             }
+            if (AA) {   // (project_bwd_kernel's v_rho, from the record-opacity gradient it left per (camera, Gaussian))
+                const preal v_rho = (preal)a.v_op_rec[f] * (preal)act_opacity(a.opacities[n], a.activations);
+                project_vjp_cam<preal, CAM, AA>(mean, scale, cam, p, vm.x, vm.y, vc[0], vc[1], vc[2], 0.f, v_mean, v_quat, v_scale, acc, acc + 9, v_rho, (preal)a.eps2d);
+            } else
             project_vjp_cam<preal, CAM>(mean, scale, cam, p, vm.x, vm.y, vc[0], vc[1], vc[2], 0.f, v_mean, v_quat, v_scale, acc, acc + 9);
         }
     }

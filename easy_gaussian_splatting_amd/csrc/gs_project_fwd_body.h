@@ -1,4 +1,5 @@
-// The body of project_fwd_kernel / project_fwd_cm_kernel (gs_project.hip), which define DEG, STAGE and the camera model CAM around it.
+// The body of project_fwd_kernel / project_fwd_cm_kernel (gs_project.hip), which define DEG, STAGE, the camera model CAM and
+// the antialiased mode AA around it.
 // Included once per kernel template, inside its braces: no include guard, nothing but the body.
     extern __shared__ __attribute__((aligned(16))) float smem[];
     float* lds_cam = smem;
@@ -39,7 +40,7 @@
             const float quat[4] = {q4.x, q4.y, q4.z, q4.w};
             const float scale[3] = {act_scale(sc_raw[0], a.activations), act_scale(sc_raw[1], a.activations),
                                     act_scale(sc_raw[2], a.activations)};
-            s = project_gaussian_cm<CAM>(mean, quat, scale, cam, a.W, a.H, a.eps2d, a.near_p, a.far_p, a.radius_clip, GS_TILE, a.tw, a.th);
+            s = project_gaussian_cm<CAM, AA>(mean, quat, scale, cam, a.W, a.H, a.eps2d, a.near_p, a.far_p, a.radius_clip, GS_TILE, a.tw, a.th);
         }
         vis = s.radius > 0;
         if (!vis && in_range && a.rect_ref) a.rect_ref[f] = make_uint2(0u, 0u);
@@ -49,6 +50,10 @@
             x0 = s.x0; x1 = s.x1; y0 = s.y0; y1 = s.y1;   // from the unrounded centre (gs_math.h: preal)
             if (a.rect_ref) a.rect_ref[f] = make_uint2(fp_span(x0, x1), fp_span(y0, y1));
             op = act_opacity(op_raw, a.activations);
+            // antialiased mode: everything behind the projection sees op_eff = opacity * rho -- the record, the extents and the tile mask
+            // below.  rho = 0 (a rank-deficient covariance) is an opacity of 0: no extent (alpha_extent's v > 1 test), an empty tight
+            // rectangle, and in the full rectangle a record no pixel takes.
+            if (AA) op *= s.rho;
             alpha_extent(op, s.cxx, s.cyy, ex, ey);
             // tight mode: keep only the tiles of the 3-sigma rectangle that hold a pixel centre where
             // alpha can reach 1/255 (the blend skips every other pixel anyway: identical image)
@@ -77,6 +82,7 @@
             a.conics[3 * f] = s.A; a.conics[3 * f + 1] = s.B; a.conics[3 * f + 2] = s.C;
             a.bbox[f] = fp_pack(x0, x1, y0, y1, tmask, (uint32_t)cnt);
             a.tiles_per_gauss[f] = cnt;
+            if (AA) a.compensations[f] = vis ? s.rho : 0.f;
             if (vis) {
                 // blend record: conic pre-scaled so the kernels evaluate exp2(-(hA dx^2 + B dx dy + hC dy^2))
                 float4* r = a.rec + 3 * f;

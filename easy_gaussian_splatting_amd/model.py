@@ -87,6 +87,7 @@ class GaussianModel(nn.Module):
     grad_out = None             # callable -> {name: tensor}: caller-owned geometry-gradient tensors (distributed.ViewParallelStep)
     view_payload = None         # callable -> tensor: this rank's all-gather record, filled by the rasterizer's backward (same)
     device_refine = True
+    rasterize_mode = "classic"  # or "antialiased" (rasterization(rasterize_mode=...)); set it on the instance
     # hooks a training driver installs on a live model (bound methods of distributed.ViewParallelStep): never pickled -- a
     # checkpoint must not drag the step object, its optimizer and its exchange buffers along, nor name classes the reference
     # cannot import; an unpickled model falls back to the class defaults above
@@ -427,7 +428,7 @@ class GaussianModel(nn.Module):
         camera gradients (`rasterization(_camera_grads=True)`).  Eager loop only: `TrainStepGraph` refuses such a `w2c`, and a
         model with `sh_grads = "colors_pre"` (`ViewParallelStep` with its exchange on) is refused by `rasterization()`.
         `data.get("camera_model", "pinhole")` ("pinhole" | "ortho" | "fisheye", what `scene.Frame` carries) goes to
-        `rasterization(camera_model=...)`."""
+        `rasterization(camera_model=...)`, and the model's `rasterize_mode` ("classic" | "antialiased") to `rasterization(rasterize_mode=...)`."""
         w2c = data["w2c"]
         camera_model = data.get("camera_model", "pinhole")
         if depth not in (None, "D", "ED"):
@@ -460,6 +461,7 @@ class GaussianModel(nn.Module):
             _camera_grads=bool(w2c.requires_grad),
             **({} if depth is None else {"render_mode": "RGB+" + depth}),
             **({} if camera_model == "pinhole" else {"camera_model": camera_model}),   # (pinhole: the call as it was)
+            **({} if self.rasterize_mode == "classic" else {"rasterize_mode": self.rasterize_mode}),   # (classic: likewise)
         )
         render_img = batch_render_imgs.squeeze(0)   # (a view both ways: `[0]` would cost a zero-fill + copy in backward)
         render_depth = None

@@ -573,6 +573,9 @@ def _forward_stages(means, quats, scales, opacities, colors, colors_rest, viewma
     if dmode:
         ch = dc + 1
     cam_model = int(cfg.get("camera_model", nat.GS_CAMERA_PINHOLE))   # (another model: the `_cm` entry points, one depth round)
+    # antialiased mode (gs_raster.h "Antialiased mode"): the `_aa` entry points, which also leave rho per (camera, Gaussian); one depth round
+    aa = bool(cfg.get("antialiased"))
+    compensations = torch.empty((C, N), **f32) if aa else None
     split_project = _SPLIT_PROJECT and not dmode
 
     # what escapes to the caller through `meta` is allocated per call; everything else is workspace
@@ -596,7 +599,7 @@ def _forward_stages(means, quats, scales, opacities, colors, colors_rest, viewma
     # depth rounds: inference, one camera, long lists (see ROUNDS_MIN_LISTED above); the decision of a call shape is taken from
     # what its one-round calls listed and kept (a two-round call reports the short total of its two rounds)
     rmode = cfg.get("rounds") or rounds_mode()
-    rounds = (not need_grad) and C == 1 and N > 0 and ch == 3 and not dmode and cam_model == nat.GS_CAMERA_PINHOLE and rmode != "off" and (rmode == "on" or (
+    rounds = (not need_grad) and C == 1 and N > 0 and ch == 3 and not dmode and cam_model == nat.GS_CAMERA_PINHOLE and not aa and rmode != "off" and (rmode == "on" or (
         two_level and int(hint.get("n", -1)) == N and int(hint.get("listed_one_round", 0)) >= ROUNDS_MIN_LISTED and not hint.get("rounds_off")))
     rb = _round_buffers(dev, st, N, tiles) if rounds else None
     eager_ids = os.environ.get("GS_EAGER_ISECT_IDS") == "1"   # (default: meta builds isect_ids on first access, _LazyMeta)
@@ -635,7 +638,9 @@ def _forward_stages(means, quats, scales, opacities, colors, colors_rest, viewma
                 cfg["radius_clip"], cfg["tile_culling"], stage, cfg.get("activations", 0), _ptr(radii), _ptr(means2d), _ptr(depths), _ptr(conics),
                 P(WS.COLORS_POST), P(WS.REC), P(WS.BBOX), P(WS.TILES_PER_GAUSS), _ptr(rect_ref),
                 P(WS.SH_JAC) if use_jac else None)
-        if cam_model == nat.GS_CAMERA_PINHOLE:   # (today's call, untouched)
+        if aa:
+            _stage(tag, dev, lambda: nat.check(L.gs_project_fwd_aa(*args, _ptr(compensations)), "gs_project_fwd_aa"))
+        elif cam_model == nat.GS_CAMERA_PINHOLE:   # (today's call, untouched)
             _stage(tag, dev, lambda: nat.check(L.gs_project_fwd(*args), "gs_project_fwd"))
         else:
             _stage(tag, dev, lambda: nat.check(L.gs_project_fwd_cm(*args, cam_model), "gs_project_fwd_cm"))
@@ -866,7 +871,9 @@ def _forward_stages(means, quats, scales, opacities, colors, colors_rest, viewma
     meta = _LazyMeta({
         "camera_ids": None, "gaussian_ids": None,
         "radii": radii, "means2d": means2d, "depths": depths, "conics": conics,
-        "opacities": opacities[None, :].expand(C, N),
+        # antialiased: gsplat's op_eff = opacity * rho per camera, 0 where culled (the product the kernel formed; built on first read)
+        "opacities": lazy(lambda: (torch.sigmoid(opacities) if cfg.get("activations") else opacities)[None, :] * compensations) if aa
+                     else opacities[None, :].expand(C, N),
         "tile_width": tw, "tile_height": th, **list_entries,
         "width": W, "height": H, "tile_size": _TILE, "n_cameras": C,
     })
@@ -1063,6 +1070,7 @@ class _Rasterize(torch.autograd.Function):
                             _ptr(opacities), cfg.get("activations", 0), P(WS.SH_JAC) if s.get("sh_jac") else None,
                             _ptr(row_sums), _ptr(go.get("grad_norm")), _ptr(go.get("count")))
         cam_model = int(cfg.get("camera_model", nat.GS_CAMERA_PINHOLE))
+        aa = bool(cfg.get("antialiased"))
         if ctx.camera_grads:
             # gs_project_bwd_cam: the same projection backward (same bits), then the camera terms from the per-(camera, Gaussian)
             # sums it hands out -- which are therefore written -- reduced per camera in fp64 without atomics.  The partials are
@@ -1070,14 +1078,19 @@ class _Rasterize(torch.autograd.Function):
             v_m2 = torch.empty((C, N, 2), **f32) if v_m2 is None else v_m2
             v_cn = torch.empty((C, N, 3), **f32) if v_cn is None else v_cn
             v_cp = torch.empty((C, N, 3), **f32) if v_cp is None else v_cp
-            partials = torch.empty((int(L.gs_cam_partials_doubles(C, N)),), dtype=torch.float64, device=dev)
+            partials = torch.empty((int((L.gs_cam_partials_doubles_aa if aa else L.gs_cam_partials_doubles)(C, N)),), dtype=torch.float64, device=dev)
             v_viewmats, v_campos = torch.empty((C, 4, 4), **f32), torch.empty((C, 3), **f32)
-            if cam_model == nat.GS_CAMERA_PINHOLE:
+            if aa:
+                _stage("gs_project_bwd", dev, lambda: nat.check(L.gs_project_bwd_cam_aa(*bwd_args(), _ptr(partials), _ptr(v_viewmats), _ptr(v_campos)),
+                                                                "gs_project_bwd_cam_aa"))
+            elif cam_model == nat.GS_CAMERA_PINHOLE:
                 _stage("gs_project_bwd", dev, lambda: nat.check(L.gs_project_bwd_cam(*bwd_args(), _ptr(partials), _ptr(v_viewmats), _ptr(v_campos)),
                                                                 "gs_project_bwd_cam"))
             else:
                 _stage("gs_project_bwd", dev, lambda: nat.check(L.gs_project_bwd_cam_cm(*bwd_args(), _ptr(partials), _ptr(v_viewmats), _ptr(v_campos),
                                                                                         cam_model), "gs_project_bwd_cam_cm"))
+        elif aa:
+            _stage("gs_project_bwd", dev, lambda: nat.check(L.gs_project_bwd_aa(*bwd_args()), "gs_project_bwd_aa"))
         elif cam_model == nat.GS_CAMERA_PINHOLE:
             _stage("gs_project_bwd", dev, lambda: nat.check(L.gs_project_bwd(*bwd_args()), "gs_project_bwd"))
         else:
@@ -1169,6 +1182,10 @@ def quat_to_rotmat_torch(quats: Tensor) -> Tensor:
 
 # rasterization(camera_model=...): gsplat's names -> the C ABI's GS_CAMERA_* (include/gs_raster.h "Camera models")
 CAMERA_MODELS = {"pinhole": nat.GS_CAMERA_PINHOLE, "ortho": nat.GS_CAMERA_ORTHO, "fisheye": nat.GS_CAMERA_FISHEYE}
+
+
+# rasterization(rasterize_mode=...): gsplat's two names
+RASTERIZE_MODES = ("classic", "antialiased")
 
 
 def rasterization(
@@ -1281,6 +1298,17 @@ def rasterization(
     round; not together with `_sh_grads="colors_pre"`, `_grad_out` or `_view_payload` (`ValueError`), an unknown name raises
     `ValueError`.  INTEGRATION.md "Cameras other than pinhole".
 
+    `rasterize_mode` (gsplat's): "classic" (default: the call without the keyword, bit for bit) or "antialiased" -- Mip-Splatting's
+    screen-space filter as gsplat applies it: with cov2_0 = J cov_c J^T before `eps2d` joins its diagonal, every Gaussian's opacity is
+    multiplied by rho = sqrt(max(0, det(cov2_0) / det(cov2_0 + eps2d I))) per camera, so that the blur `eps2d` adds spreads a sub-pixel
+    Gaussian's energy instead of adding to it.  `radii`, `means2d`, `conics` and `depths` are the classic call's; `meta["opacities"]` is
+    [C,N] opacity * rho (0 where culled; with `_activations` the activated opacity), as in gsplat.  The definition is written down in
+    DESIGN.md "Antialiased mode" (from gsplat's public source as remembered; not checked against a run of it).  Pinhole only
+    (`NotImplementedError` otherwise); SH degrees 0-4, 1-4 feature channels, C >= 1, `backgrounds`, `absgrad`, every `_tile_culling`,
+    the depth render modes, `_camera_grads` and `_activations` work; always one depth round; not together with
+    `_sh_grads="colors_pre"`, `_grad_out` or `_view_payload` (`ValueError`); HIP tensors only (`NotImplementedError` on CPU tensors).
+    INTEGRATION.md "Antialiased mode".
+
     `_rounds` ("auto" | "on" | "off"; default: env GS_ROUNDS or "auto"): depth rounds of the list stages for INFERENCE calls with
     one camera -- the front slab by depth is listed, sorted and blended first, the rest only into tiles it has not finished
     (include/gs_raster.h "Depth rounds"; same image bit for bit).  "auto": on for a call shape whose one-round call listed
@@ -1340,8 +1368,18 @@ def rasterization(
     if camera_model != "pinhole" and (_sh_grads == "colors_pre" or _grad_out is not None or _view_payload is not None):
         raise ValueError(f"camera_model={camera_model!r} cannot be combined with _sh_grads='colors_pre', _grad_out or _view_payload "
                          "(the view-parallel step's projection backward exists for the pinhole model only)")
-    if rasterize_mode != "classic":
-        raise NotImplementedError("only rasterize_mode='classic' is implemented")
+    if rasterize_mode not in RASTERIZE_MODES:
+        raise ValueError(f"rasterize_mode: one of {sorted(RASTERIZE_MODES)} (got {rasterize_mode!r})")
+    if rasterize_mode == "antialiased":
+        if _sh_grads == "colors_pre" or _grad_out is not None or _view_payload is not None:
+            raise ValueError("rasterize_mode='antialiased' cannot be combined with _sh_grads='colors_pre', _grad_out or _view_payload "
+                             "(the view-parallel step's projection backward exists for the classic mode only)")
+        if camera_model != "pinhole":
+            raise NotImplementedError(f"rasterize_mode='antialiased' with camera_model={camera_model!r}: the antialiased projection kernels "
+                                      "(gs_project_fwd_aa / gs_project_bwd_aa) exist for the pinhole model only")
+        if not means.is_cuda:   # (a NotImplementedError, as for the depth modes: callers that probed for the mode keep their handler)
+            raise NotImplementedError("rasterize_mode='antialiased' runs on the GPU only: tensors must live on a HIP device "
+                                      "(there is no CPU fallback in this package)")
     if tile_size != _TILE:
         raise NotImplementedError(f"only tile_size={_TILE} is implemented")
     if sparse_grad:
@@ -1395,6 +1433,8 @@ def rasterization(
                camera_grads=bool(_camera_grads and viewmats.requires_grad and torch.is_grad_enabled()))
     if camera_model != "pinhole":   # (the pinhole call's cfg is today's, key for key)
         cfg["camera_model"] = CAMERA_MODELS[camera_model]
+    if rasterize_mode == "antialiased":   # (likewise: the classic call's cfg carries no key for the mode)
+        cfg["antialiased"] = True
     if _sh_grads not in ("dense", "colors_pre") or (_sh_grads == "colors_pre" and sh_degree is None):
         raise ValueError("_sh_grads: 'dense', or 'colors_pre' together with sh_degree")
     holder = _Holder(absgrad)

@@ -152,6 +152,39 @@ def _refuse_camera_model_combinations(camera_model, mcmc, poses, depth, rounds) 
                          "instantiated for this camera model yet")
 
 
+def _refuse_rasterize_mode_combinations(rasterize_mode, model, camera_model, mcmc, poses, depth, rounds) -> str:
+    """TrainStepGraph(rasterize_mode=...): resolves the mode against the model's attribute and refuses, before any device work, what the
+    antialiased mode cannot be combined with.  Returns the mode."""
+    model_mode = getattr(model, "rasterize_mode", "classic")
+    if rasterize_mode is None:
+        rasterize_mode = model_mode
+    if rasterize_mode not in rendering.RASTERIZE_MODES:
+        raise ValueError(f"TrainStepGraph: rasterize_mode: one of {sorted(rendering.RASTERIZE_MODES)} (got {rasterize_mode!r})")
+    if rasterize_mode != model_mode:   # (what model(data) would render with in the eager loop, and every evaluation of the model)
+        raise ValueError(f"TrainStepGraph: the model's rasterize_mode is {model_mode!r}, but the runner was asked for "
+                         f"rasterize_mode={rasterize_mode!r}; set model.rasterize_mode first")
+    if rasterize_mode == "classic":
+        return rasterize_mode
+    what = "TrainStepGraph(rasterize_mode='antialiased')"
+    if camera_model != "pinhole":
+        raise ValueError(f"{what} with camera_model={camera_model!r} -- the antialiased projection and its fused backward + Adam "
+                         "(gs_project_fwd_aa, gs_project_bwd_adam_aa: project_bwd_aa_kernel) exist for the pinhole model only")
+    if mcmc is not None:
+        raise ValueError(f"{what} with `mcmc` -- the fused projection backward + Adam with the budget regulariser "
+                         "(gs_project_bwd_adam_mcmc: project_bwd_budget_kernel) does not exist in the antialiased mode yet")
+    if poses is not None:
+        raise ValueError(f"{what} with `poses` -- the fused projection backward + Adam from the row sums and the camera gradient from "
+                         "them (gs_project_bwd_adam_sums, gs_cam_grad_sums: project_cam_kernel<DEG, SUMS = true>) do not exist in the "
+                         "antialiased mode yet; refine poses in the eager loop (rasterization(rasterize_mode='antialiased', _camera_grads=True))")
+    if depth is not None:
+        raise ValueError(f"{what} with `depth` -- the fused projection backward + Adam with the depth gradient "
+                         "(gs_project_bwd_adam_depth: project_bwd_depth_kernel) does not exist in the antialiased mode yet")
+    if rounds == "on":
+        raise ValueError(f"{what} with rounds='on' -- the antialiased mode runs in one depth round: the fused projection backward over "
+                         "the two row ranges of a two-round step (project_bwd_kernel with ProjBwdArgs.rblk) is not instantiated for it yet")
+    return rasterize_mode
+
+
 class TrainStepGraph:
     def __init__(self, model, optimizer: FusedAdam, loss_computer, data: Dict[str, Any], gt_img: Tensor,
                  mask: Optional[Tensor] = None, margin: float = 1.3, use_graph: bool = True, check_every: int = 16,
@@ -160,7 +193,8 @@ class TrainStepGraph:
                  pose_lr: float = 1e-3, pose_betas: Tuple[float, float] = (0.9, 0.999), pose_eps: float = 1e-15, exposure=None,
                  exposure_lr: float = 1e-2, exposure_betas: Tuple[float, float] = (0.9, 0.999), exposure_eps: float = 1e-15, bilagrid=None,
                  bilagrid_lr: float = 2e-3, bilagrid_betas: Tuple[float, float] = (0.9, 0.999), bilagrid_eps: float = 1e-15,
-                 bilagrid_tv: float = 10.0, depth=None, gt_depth: Optional[Tensor] = None, camera_model: str = "pinhole"):
+                 bilagrid_tv: float = 10.0, depth=None, gt_depth: Optional[Tensor] = None, camera_model: str = "pinhole",
+                 rasterize_mode: Optional[str] = None):
         """`mcmc`: an `mcmc.MCMCStrategy(model, ..., noise="counter")` -- the step then trains under its Gaussian budget: `mcmc_reg` =
         (opacity_reg, scale_reg) of `strategy.regularization()` enters the loss (out["mcmc_reg"]) and the update, and the strategy's
         noise runs behind Adam inside the step, at noise_lr x the means learning rate of that step.  None (default): nothing changes.
@@ -217,9 +251,18 @@ class TrainStepGraph:
         with a mask, the scale regulariser, `exposure`, `bilagrid` and `HostFeed` (none of them touches the projection backward), always
         in one depth round ("auto" resolves to off).  Refused before any device work (`ValueError`): `mcmc`, `poses`, `depth`,
         `rounds="on"` and `ViewParallelGraphStep` -- each needs a variant of the fused projection backward that exists for the
-        pinhole model only."""
+        pinhole model only.
+        `rasterize_mode`: None (default: the model's `rasterize_mode` attribute), "classic" (nothing changes, launch for launch) or
+        "antialiased" (`rasterization(rasterize_mode=...)`); a value other than the model's attribute raises `ValueError` -- the model
+        renders its evaluations with the attribute.  The antialiased step projects with gs_project_fwd_aa and updates with
+        gs_project_bwd_adam_aa / gs_project_bwd_adam_reg_aa.  Works with a mask, the scale regulariser, `exposure`, `bilagrid` and
+        `HostFeed`, always in one depth round ("auto" resolves to off).  Refused before any device work (`ValueError`): `mcmc`, `poses`,
+        `depth`, `rounds="on"`, a camera model other than pinhole and `ViewParallelGraphStep` -- each needs a variant of the fused
+        projection backward that exists for the classic mode only."""
         _refuse_camera_model_combinations(camera_model, mcmc, poses, depth, __import__("os").environ.get("GS_TG_ROUNDS", rounds))
         self.camera_model = rendering.CAMERA_MODELS[camera_model]
+        self.antialiased = _refuse_rasterize_mode_combinations(rasterize_mode, model, camera_model, mcmc, poses, depth,
+                                                                __import__("os").environ.get("GS_TG_ROUNDS", rounds)) == "antialiased"
         self.depth = depth
         if depth is not None:
             from .depth_loss import MODES, DepthSupervision
@@ -325,8 +368,8 @@ class TrainStepGraph:
         if rounds not in ("auto", "on", "off"):
             raise ValueError("rounds: 'auto', 'on' or 'off'")
         self.rounds_mode, self.round_fraction = rounds, float(__import__("os").environ.get("GS_TG_ROUND_FRACTION", round_fraction))
-        if (depth is not None or self.camera_model != nat.GS_CAMERA_PINHOLE) and rounds == "auto":
-            rounds = self.rounds_mode = "off"   # (one round: see `depth`, `camera_model`)
+        if (depth is not None or self.camera_model != nat.GS_CAMERA_PINHOLE or self.antialiased) and rounds == "auto":
+            rounds = self.rounds_mode = "off"   # (one round: see `depth`, `camera_model`, `rasterize_mode`)
         self.rounds_on = rounds == "on"
         self._live_sum = self._live_n = 0   # tiles the front round left live, summed over the polled steps since the last build
         # "auto" only: the captured step holds the FRONT round alone (gs_rounds_set phase 4), speculating that it finishes every
@@ -446,6 +489,8 @@ class TrainStepGraph:
             "sh_rest": torch.empty((N, self.K - 1, 3), **f32) if self.K > 1 else None,
             "logit_opacities": torch.empty((N,), **f32)}
         b["hyper"] = torch.zeros((16,), **f32)
+        if self.antialiased:   # gs_project_fwd_aa's rho per Gaussian (nothing in the step reads it back: the backward recomputes the chain)
+            b["compensations"] = self._take("compensations", (1, N), torch.float32)
         if self.poses is not None:
             b.update(self._pose_bufs)
             b["w2c_raw"] = b["pose_rec"][:16].view(1, 4, 4)
@@ -832,7 +877,9 @@ class TrainStepGraph:
                 _p(b["viewmats"]), _p(b["Ks"]), self.W, self.H, EPS2D, NEAR_PLANE, FAR_PLANE, RADIUS_CLIP, culling, 0, 1,
                 _p(b["radii"]), _p(b["means2d"]), _p(b["depths"]), _p(b["conics"]), _p(b["colors_post"]),
                 _p(b["rec"]), _p(b["bbox"]), _p(b["tiles_per_gauss"]), None, _p(b["sh_jac"]))
-        if self.camera_model == nat.GS_CAMERA_PINHOLE:
+        if self.antialiased:
+            self._ck(L.gs_project_fwd_aa(*args, _p(b["compensations"])), "gs_project_fwd_aa")
+        elif self.camera_model == nat.GS_CAMERA_PINHOLE:
             self._ck(L.gs_project_fwd(*args), "gs_project_fwd")
         else:
             self._ck(L.gs_project_fwd_cm(*args, self.camera_model), "gs_project_fwd_cm")
@@ -1042,6 +1089,17 @@ class TrainStepGraph:
                              "gs_project_bwd_adam_reg_cm")
                 else:
                     self._ck(L.gs_project_bwd_adam_cm(*cm_args, self.camera_model), "gs_project_bwd_adam_cm")
+            elif self.antialiased:   # (no depth, poses, mcmc or other camera model here: refused at construction)
+                # (`args`, spelt out as for the camera models: tests/test_native_header.py counts these two calls against the header)
+                aa_args = (st, N, self.K, int(m.active_sh_degree), _p(opt.flat_param), _p(opt.exp_avg), _p(opt.exp_avg_sq), offs,
+                           _p(b["viewmats"]), _p(b["Ks"]), W, H, EPS2D, NEAR_PLANE, FAR_PLANE, _p(b["radii"]), _p(b["colors_post"]),
+                           self._tpg(), _p(b["cum_tiles"]), _p(b["rows"]), _p(b["row_base"]), _p(b["qmask"]), _p(b["v_abs"]), float(b1),
+                           float(b2), float(opt.defaults["eps"]), _p(b["hyper"]), _p(b["applied"]), _p(m.max_radii),
+                           _p(m.grad_norm_accum), _p(m.collecting_counts), _p(b["sh_jac"]))
+                if self.scale_reg:
+                    self._ck(L.gs_project_bwd_adam_reg_aa(*aa_args, self.max_scale_ratio, self.lambda_scale), "gs_project_bwd_adam_reg_aa")
+                else:
+                    self._ck(L.gs_project_bwd_adam_aa(*aa_args), "gs_project_bwd_adam_aa")
             elif self.scale_reg:
                 self._ck(L.gs_project_bwd_adam_reg(*args, self.max_scale_ratio, self.lambda_scale), "gs_project_bwd_adam_reg")
             else:
@@ -1057,6 +1115,9 @@ class TrainStepGraph:
                 self._ck(L.gs_project_bwd_cam(*bwd_args, _p(b["v_means2d"]), _p(b["v_conics"]), _p(b["v_colors_post"]), None,
                                                _p(m.logit_opacities), 1, _p(b["sh_jac"]), None, None, None, _p(b["cam_partials"]),
                                                _p(b["v_viewmats"]), _p(b["v_campos"])), "gs_project_bwd_cam")
+            elif self.antialiased:
+                self._ck(L.gs_project_bwd_aa(*bwd_args, None, None, None, None, _p(m.logit_opacities), 1, _p(b["sh_jac"]), None, None, None),
+                         "gs_project_bwd_aa")
             elif self.camera_model != nat.GS_CAMERA_PINHOLE:
                 self._ck(L.gs_project_bwd_cm(*bwd_args, None, None, None, None, _p(m.logit_opacities), 1, _p(b["sh_jac"]), None, None, None,
                                               self.camera_model), "gs_project_bwd_cm")
@@ -1494,6 +1555,9 @@ class ViewParallelGraphStep(TrainStepGraph):
             raise ValueError("ViewParallelGraphStep: camera_model='pinhole' only -- the view-parallel step's projection backward takes the "
                              "row sums (project_bwd_kernel<DEG, ADAM, SUMS = true>), a variant that does not exist for "
                              f"camera_model={kw['camera_model']!r} yet")
+        if (kw.get("rasterize_mode") or getattr(model, "rasterize_mode", "classic")) != "classic":
+            raise ValueError("ViewParallelGraphStep: rasterize_mode='classic' only -- the view-parallel step's projection backward takes the "
+                             "row sums (project_bwd_kernel<DEG, ADAM, SUMS = true>), a variant that does not exist in the antialiased mode yet")
         if kw.get("poses") is not None:
             raise ValueError("ViewParallelGraphStep: no `poses` -- pose refinement inside the captured step is single-GPU "
                              "(TrainStepGraph(poses=...)): the view-parallel step has no camera gradient")

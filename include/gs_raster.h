@@ -1104,6 +1104,59 @@ int gs_project_bwd_adam_reg_cm(void* stream, int64_t N, int K, int sh_degree, fl
                                const float* hyper_dev, int64_t* applied_dev, float* max_radii, float* grad_norm_accum, float* counts,
                                const float* sh_jac, float max_ratio, float lambda, int camera_model);
 
+/* Antialiased mode (rasterization(rasterize_mode="antialiased"); DESIGN.md "Antialiased mode").  A property of the projection alone, pinhole
+ * model only: with cov2_0 = J cov_c J^T taken BEFORE eps2d joins its diagonal and cov2 = cov2_0 + eps2d I (what the cull, the radius and the
+ * conic are formed from, unchanged),
+ *   rho = sqrt(max(0, det(cov2_0) / det(cov2)))  in [0, 1),    op_eff = opacity * rho   (the activated opacity with activations),
+ * and everything behind the projection that took the opacity takes op_eff: the blend record, the opacity-aware extents, the tight
+ * rectangle and the per-tile mask.  radii, means2d, conics, depths and the 3-sigma rectangle are those of the classic call.  rho = 0 (a
+ * rank-deficient covariance) is an opacity of 0.  Backward: the row sum's gradient of the record's opacity v_eff gives v_opacity = v_eff
+ * rho and v_rho = v_eff opacity, and v_rho joins v_cov2 in front of the chain's VJP through
+ *   d rho / d cov2_0 = (adj(cov2_0) - rho^2 adj(cov2)) / (2 (rho + 1e-6) det(cov2)).
+ * The `_aa` entry points take the arguments of the entry point they are named after; gs_project_fwd_aa additionally `compensations`
+ * ([C*N], rho, 0 where culled; never NULL; stage 2 -- colour only -- launches the classic kernel and leaves it alone).  `opacities` is
+ * never NULL in the backward entries; row_sums, stat_grad_norm and stat_count are NULL (the gradient rows are walked); one depth round.
+ * gs_project_bwd_cam_aa's cam_partials holds gs_cam_partials_doubles_aa(C, N) doubles: the block partials, and behind them the C*N
+ * record-opacity gradients the projection backward leaves for the camera kernel.  The fused backward + Adam exists plain and with the
+ * scale-ratio regulariser -- there is no budget, row-sums or depth variant of it. */
+size_t gs_cam_partials_doubles_aa(int C, int64_t N);
+int gs_project_fwd_aa(void* stream, int C, int64_t N, int K, int sh_degree, const float* means, const float* quats,
+                      const float* scales, const float* opacities, const float* colors_in, const float* sh_rest,
+                      int colors_per_camera, const float* viewmats, const float* Ks, int width, int height, float eps2d,
+                      float near_plane, float far_plane, float radius_clip, int tile_culling, int stage, int activations,
+                      int32_t* radii, float* means2d, float* depths, float* conics, float* colors_out, float* rec, uint32_t* bbox,
+                      int32_t* tiles_per_gauss, uint32_t* rect_ref, float* sh_jac, float* compensations);
+int gs_project_bwd_aa(void* stream, int C, int64_t N, int K, int sh_degree, const float* means, const float* quats,
+                      const float* scales, const float* colors_in, const float* sh_rest, int colors_per_camera,
+                      const float* viewmats, const float* Ks, int width, int height, float eps2d, float near_plane, float far_plane,
+                      const int32_t* radii, const float* colors_post, const int32_t* tiles_per_gauss, const int32_t* cum_tiles,
+                      const float* rows, const int32_t* row_base, const uint8_t* qmask, float* v_means, float* v_quats,
+                      float* v_scales, float* v_opacities, float* v_colors, float* v_sh_rest, float* v_means2d_abs,
+                      float* v_means2d, float* v_conics, float* v_colors_post, float* v_colors_pre, const float* opacities,
+                      int activations, const float* sh_jac, const float* row_sums, float* stat_grad_norm, float* stat_count);
+int gs_project_bwd_cam_aa(void* stream, int C, int64_t N, int K, int sh_degree, const float* means, const float* quats,
+                          const float* scales, const float* colors_in, const float* sh_rest, int colors_per_camera,
+                          const float* viewmats, const float* Ks, int width, int height, float eps2d, float near_plane,
+                          float far_plane, const int32_t* radii, const float* colors_post, const int32_t* tiles_per_gauss,
+                          const int32_t* cum_tiles, const float* rows, const int32_t* row_base, const uint8_t* qmask, float* v_means,
+                          float* v_quats, float* v_scales, float* v_opacities, float* v_colors, float* v_sh_rest,
+                          float* v_means2d_abs, float* v_means2d, float* v_conics, float* v_colors_post, float* v_colors_pre,
+                          const float* opacities, int activations, const float* sh_jac, const float* row_sums,
+                          float* stat_grad_norm, float* stat_count, double* cam_partials, float* v_viewmats, float* v_campos);
+int gs_project_bwd_adam_aa(void* stream, int64_t N, int K, int sh_degree, float* params, float* exp_avg, float* exp_avg_sq,
+                           const int64_t* offsets_host, const float* viewmats, const float* Ks, int width, int height, float eps2d,
+                           float near_plane, float far_plane, const int32_t* radii, const float* colors_post,
+                           const int32_t* tiles_per_gauss, const int32_t* cum_tiles, const float* rows, const int32_t* row_base,
+                           const uint8_t* qmask, float* v_means2d_abs, float beta1, float beta2, float eps, const float* hyper_dev,
+                           int64_t* applied_dev, float* max_radii, float* grad_norm_accum, float* counts, const float* sh_jac);
+int gs_project_bwd_adam_reg_aa(void* stream, int64_t N, int K, int sh_degree, float* params, float* exp_avg, float* exp_avg_sq,
+                               const int64_t* offsets_host, const float* viewmats, const float* Ks, int width, int height,
+                               float eps2d, float near_plane, float far_plane, const int32_t* radii, const float* colors_post,
+                               const int32_t* tiles_per_gauss, const int32_t* cum_tiles, const float* rows, const int32_t* row_base,
+                               const uint8_t* qmask, float* v_means2d_abs, float beta1, float beta2, float eps,
+                               const float* hyper_dev, int64_t* applied_dev, float* max_radii, float* grad_norm_accum, float* counts,
+                               const float* sh_jac, float max_ratio, float lambda);
+
 #ifdef __cplusplus
 }
 #endif
