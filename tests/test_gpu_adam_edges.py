@@ -10,6 +10,11 @@ every step.  Each test prints the worst observed error / bound per quantity.
 * the in-place update of the fused projection backward (csrc/gs_project.hip: adam_sh_tile, adam_geo_tile through
   gs_project_bwd_adam / gs_project_bwd_adam_reg): ragged N, every K / active degree, culled Gaussians, the regulariser, the
   captured path.
+
+The sibling variants of that fused kernel -- the budget, row-sums (poses), depth, ortho / fisheye and antialiased instantiations, each
+at every SH degree, and the two-range row walk of depth rounds -- are held to the same standard by tests/test_gpu_fused_variants.py,
+which generalises `_fused_case` over the variant matrix of tests/fused_variants.py and imports `_fused_setup`, `_check_step`, `Worst`
+and the small helpers from here.
 """
 import ctypes as ct
 

@@ -133,6 +133,24 @@ def test_blend_backward_arguments_land_under_their_names(train, two_level, ch):
                                     ckpt_ext=CKPT_EXT if (train and ch == 4) else None))
 
 
+def test_every_fused_projection_backward_entry_has_a_row_in_the_variant_matrix():
+    """The `VARIANTS` table of tests/fused_variants.py, which tests/test_gpu_fused_variants.py runs row by row at every SH degree,
+    against the header: every gs_project_bwd_adam* entry point is reached by at least one row, and every row names an entry point the
+    header declares -- one added later cannot arrive without a row in the matrix.  Names only."""
+    import fused_variants as FV
+    declared = {name for name in nat.SIGNATURES if name.startswith(FV.ENTRY_PREFIX)}
+    reached = {v.entry for v in FV.VARIANTS}
+    assert declared, "the header declares no fused projection backward at all"
+    assert declared - reached == set(), f"no row of fused_variants.VARIANTS reaches {sorted(declared - reached)}"
+    assert reached - declared == set(), f"fused_variants.VARIANTS names {sorted(reached - declared)}, which the header does not declare"
+    # the matrix itself: 18 rows with tags of their own, the four regulariser masks where a family has the budget kernels
+    assert len(FV.VARIANTS) == len(FV.BY_TAG) == 18
+    for family, n_masks in (("plain", 4), ("poses", 4), ("depth", 4), ("ortho", 2), ("fisheye", 2), ("aa", 2)):
+        rows = [v for v in FV.VARIANTS if v.family == family]
+        assert [(v.scale, v.budget) for v in rows] == list(FV.MASKS[:n_masks]), family
+        assert len({v.kernel for v in rows}) == n_masks, family   # (a kernel of its own per row)
+
+
 def test_the_blend_and_the_captured_step_are_spelled_in_the_stage_functions_alone():
     """The four blend entry points are named once each in the package, in rendering.py; train_graph.py names none of the eight.  (The
     list builders of rendering.py that run on exact-size tensors of their own keep their count / emit calls.)"""
