@@ -26,6 +26,14 @@ struct RefineThresholds {
 
 __device__ __forceinline__ float sigmoidf_(float x) { return 1.f / (1.f + expf(-x)); }
 
+// The largest of three the way torch's `amax` forms it: a NaN operand makes the result NaN (fmaxf alone would drop it), so
+// every comparison with it is false -- a Gaussian with a NaN log-scale is never "big": it is cloned, not split, when its
+// gradient is high, and it is never pruned by scale, exactly as on the host path and in the reference.
+__device__ __forceinline__ float amax3f_(float a, float b, float c) {
+    const float m = fmaxf(fmaxf(a, b), c);
+    return (a != a || b != b || c != c) ? __builtin_nanf("") : m;
+}
+
 __global__ __launch_bounds__(256) void refine_flags_kernel(int64_t n, RefineThresholds th, const float* __restrict__ grad_norm_accum,
                                                            const float* __restrict__ counts, const float* __restrict__ max_radii,
                                                            const float* __restrict__ log_scales, const float* __restrict__ logit_opac,
@@ -36,13 +44,15 @@ __global__ __launch_bounds__(256) void refine_flags_kernel(int64_t n, RefineThre
         float avg = grad_norm_accum[i] / (counts[i] + 1e-8f);
         if (avg != avg) avg = 0.f;
         const bool high = avg >= th.densify_grad;
-        const float smax = fmaxf(fmaxf(expf(log_scales[3 * i]), expf(log_scales[3 * i + 1])), expf(log_scales[3 * i + 2]));
+        const float smax = amax3f_(expf(log_scales[3 * i]), expf(log_scales[3 * i + 1]), expf(log_scales[3 * i + 2]));
         const bool big = smax >= th.densify_scale;
         split = big && high; clone = !big && high;
         const bool low = sigmoidf_(logit_opac[i]) < th.min_opacity;
         const bool big_r = max_radii[i] > th.prune_radii;
         const bool big_s = smax > th.prune_scale;
         // children of a split: same opacity, max_radii 0, scales / (0.8 S); the clone: same opacity and scales, max_radii 0
+        // (a new row's max_radii of 0 is taken as never above the radius threshold: prune_radii is assumed non-negative)
+        // smax is NaN when any log-scale is (amax3f_): big, big_s and child_big_s are then all false, as the reference's are
         const bool child_big_s = expf(logf(smax / (0.8f * (float)th.num_splits))) > th.prune_scale;
         flags[i] = !(low || big_r || big_s || split);
         flags[n + i] = split && !(low || child_big_s);
