@@ -513,15 +513,40 @@ def _ckpt_ext(lease, ch: int):   # the fourth channel's checkpoint plane: traini
     return lease.ckpt_ext() if (ch == 4 and lease.layout.key[7] & WS.F_TRAIN) else None
 
 
-def stage_blend_fwd(L, st, lease, C, W, H, ch, backgrounds, n_isects, colors, alphas, check=nat.check):
-    """The blend of the lists into `colors` / `alphas`; a training layout's walk (checkpoints, sublists, row bases) at its capacities."""
+def stage_blend_fwd(L, st, lease, C, W, H, ch, backgrounds, n_isects, colors, alphas, check=nat.check, walk=True):
+    """The blend of the lists into `colors` / `alphas`; a training layout's walk (checkpoints, sublists, row bases) at its capacities.
+    `walk=False`: the inference kernel whatever the layout -- the image alone, the walk the lease holds is left as it is."""
     P, lay = lease.ptr, lease.layout
-    common = (P(WS.REC), backgrounds, P(WS.ISECT_OFFSETS), P(WS.TILE_ORDER), P(WS.FLATTEN_IDS), P(WS.SLOTS), n_isects, colors, alphas, P(WS.CKPT),
-              P(WS.QLIST), P(WS.QCNT), P(WS.QMASK), P(WS.UNIT_DESC), lay.cap_units, P(WS.ROW_BASE), lay.cap_rows, P(WS.WALK_STATE))
+    Q = P if walk else (lambda slot: None)   # (the walk's outputs: none of them for the inference kernel)
+    common = (P(WS.REC), backgrounds, P(WS.ISECT_OFFSETS), P(WS.TILE_ORDER), P(WS.FLATTEN_IDS), P(WS.SLOTS), n_isects, colors, alphas, Q(WS.CKPT),
+              Q(WS.QLIST), Q(WS.QCNT), Q(WS.QMASK), Q(WS.UNIT_DESC), lay.cap_units if walk else 0, Q(WS.ROW_BASE), lay.cap_rows if walk else 0,
+              Q(WS.WALK_STATE))
     if ch == 3:
         check(L.gs_blend_fwd(st, C, W, H, *common), "gs_blend_fwd")
     else:
-        check(L.gs_blend_fwd_ch(st, C, W, H, ch, *common, _ckpt_ext(lease, ch)), "gs_blend_fwd_ch")
+        check(L.gs_blend_fwd_ch(st, C, W, H, ch, *common, _ckpt_ext(lease, ch) if walk else None), "gs_blend_fwd_ch")
+
+
+def channel_chunks(D: int):
+    """The chunks D > 4 feature channels are rendered in: [(first, count), ...] = [0:4], [4:8], ... and a tail of 1 .. 3."""
+    D = int(D)
+    if D < 1:
+        raise ValueError(f"channel_chunks: D >= 1 (got {D})")
+    return [(first, min(4, D - first)) for first in range(0, D, 4)]
+
+
+def _wide_blend_fwd(L, st, wide: dict, j: int, img, alphas, train: bool):
+    """Chunk j of a D > 4 call: its colours into the records' colour quads, then the blend of the lists into the dense
+    [C,H,W,count] `img`.  `train`: the walk of this launch replaces the one the lease holds."""
+    lease, (C, N, W, H, D), (first, count) = wide["lease"], wide["dims"], wide["chunks"][j]
+    _stage("gs_rec_colors_chunk", wide["dev"], lambda: nat.check(L.gs_rec_colors_chunk(
+        st, C, N, D, first, count, _ptr(wide["colors"]), wide["per_cam"], _ptr(wide["radii"]), lease.ptr(WS.REC)), "gs_rec_colors_chunk"))
+    wide["rec"] = j
+    if train:
+        wide["walk"] = j
+    bg = wide["bgs"][j] if wide["bgs"] is not None else None
+    _stage("gs_blend_fwd", wide["dev"], lambda: stage_blend_fwd(L, st, lease, C, W, H, count, _ptr(bg), wide["n_isects"], _ptr(img),
+                                                                _ptr(alphas), walk=train))
 
 
 def stage_blend_bwd(L, st, lease, C, W, H, ch, colors, alphas, v_colors, v_alphas, unit_classes, check=nat.check):
@@ -564,6 +589,12 @@ def _forward_stages(means, quats, scales, opacities, colors, colors_rest, viewma
     # colour channels: 3 (SH colours, and RGB features) is the RGB path as it stands; 1, 2 or 4 feature channels go through the
     # channel entry points (gs_rec_colors, gs_blend_fwd_ch / gs_blend_bwd_ch, gs_channel_grads), always in one depth round
     ch = 3 if sh_degree is not None else int(colors.shape[-1])
+    # more than 4 feature channels: one projection and one set of lists, walked once per chunk of four channels
+    # through the same entry points; `wide` also records which chunk's colours the records hold and whose walk the lease holds
+    wide = None
+    if sh_degree is None and ch > 4:
+        wide = dict(chunks=channel_chunks(ch), dims=(C, N, W, H, ch), colors=colors, per_cam=per_cam, dev=dev, rec=-1, walk=-1, n_isects=0,
+                    bgs=None if backgrounds is None else [backgrounds[:, f:f + c].contiguous() for f, c in channel_chunks(ch)])
     # depth render modes (gs_raster.h "Depth render modes"): the projection's depths as one more channel behind the dc colour
     # channels ("append": RGB+D / RGB+ED), or alone ("only": D / ED -- geometry-only projection, no SH colour); one depth round
     dmode = cfg.get("depth")
@@ -627,6 +658,8 @@ def _forward_stages(means, quats, scales, opacities, colors, colors_rest, viewma
     P = lease.ptr
     info_dev = lease.view(WS.INFO, nat.GS_INFO_WORDS)
     info_host = _pinned_info(dev)
+    if wide is not None:
+        wide.update(lease=lease, radii=radii)
 
     # training with SH colours: the forward leaves d colour / d view direction per visible Gaussian, and the backward never
     # reads the coefficients (include/gs_raster.h, gs_project_fwd: sh_jac)
@@ -655,11 +688,27 @@ def _forward_stages(means, quats, scales, opacities, colors, colors_rest, viewma
 
     def lists_and_blend():
         _stage("gs_bin_emit_sort", dev, lambda: stage_lists(L, st, lease, dims, bbox_ptr(), _ptr(depths), cap, min(cap_tile, cap)))
+        if wide is not None:
+            # every chunk but the first: the inference kernel into a dense scratch image, placed into its channels of the image
+            wide["n_isects"] = cap
+            dense = torch.empty((C, H, W, 4), **f32)
+
+            def place(j):
+                first, count = wide["chunks"][j]
+                _stage("gs_chunk_scatter", dev, lambda: nat.check(L.gs_chunk_scatter(st, C * H * W, ch, first, count, _ptr(dense),
+                                                                                     _ptr(render_colors)), "gs_chunk_scatter"))
+            for j in range(1, len(wide["chunks"])):
+                _wide_blend_fwd(L, st, wide, j, dense, render_alphas, False)
+                place(j)
         if walk is not None:
             nat.check(L.gs_walk_mirror_set(walk.host.data_ptr()), "gs_walk_mirror_set")
         try:
-            _stage("gs_blend_fwd", dev, lambda: stage_blend_fwd(L, st, lease, C, W, H, ch, _ptr(backgrounds), cap, _ptr(render_colors),
-                                                                _ptr(render_alphas)))
+            if wide is not None:   # ... and the first chunk last: in training mode, its walk and its colours are what the backward finds
+                _wide_blend_fwd(L, st, wide, 0, dense, render_alphas, walk is not None)
+                place(0)
+            else:
+                _stage("gs_blend_fwd", dev, lambda: stage_blend_fwd(L, st, lease, C, W, H, ch, _ptr(backgrounds), cap, _ptr(render_colors),
+                                                                    _ptr(render_alphas)))
         finally:
             if walk is not None:
                 L.gs_walk_mirror_set(None)
@@ -674,7 +723,7 @@ def _forward_stages(means, quats, scales, opacities, colors, colors_rest, viewma
         project(1 if split_project else 0, "gs_project_fwd")
     else:   # geometry, then the colour quad of the records from the D-channel features
         project(1, "gs_project_fwd")
-        if dc > 0:
+        if dc > 0 and wide is None:   # (D > 4: per chunk, in front of each blend)
             _stage("gs_rec_colors", dev, lambda: nat.check(L.gs_rec_colors(st, C, N, dc, _ptr(colors), per_cam, _ptr(radii), P(WS.REC)),
                                                            "gs_rec_colors"))
     if dmode:   # lane dc of the colour quad: the depth
@@ -881,7 +930,7 @@ def _forward_stages(means, quats, scales, opacities, colors, colors_rest, viewma
         meta._lease = ref   # (the list lazies above read the arenas; in the "gsplat" mode nothing in meta does)
     state = dict(C=C, N=N, K=K, deg=deg, per_cam=per_cam, ch=ch, dc=dc, dmode=dmode, sh_jac=use_jac, n_isects=n_isects, n_buckets=n_buckets, radii=radii, lease=lease,
                  lease_ref=WS.LeaseRef(lease) if need_grad else None, factorised=factorised, pending=pending, late=state_late,
-                 walk=walk, hint_key=hint_key, backgrounds=backgrounds)
+                 walk=walk, hint_key=hint_key, backgrounds=backgrounds, wide=wide)
     if pending is not None:
         pending.lease_ref = WS.LeaseRef(lease)   # (a repair needs the arenas: leased until the check has run)
     del ref   # (the lease goes back to its pool here unless meta or the autograd node holds it)
@@ -921,7 +970,11 @@ def _settle_walk(s: dict, cfg: dict, render_colors: Tensor, render_alphas: Tenso
             nat.check(L.gs_walk_mirror_set(walk.host.data_ptr()), "gs_walk_mirror_set")
             try:
                 # (the capacities -- and the fourth channel's checkpoint plane -- are the new layout's)
-                stage_blend_fwd(L, st, lease, C, W, H, s["ch"], _ptr(s["backgrounds"]), s["n_isects"], _ptr(sc), _ptr(sa))
+                if s.get("wide") is not None:   # D > 4: the chunk whose colours the records hold (the one that walked)
+                    s["wide"]["n_isects"] = s["n_isects"]
+                    _wide_blend_fwd(L, st, s["wide"], s["wide"]["rec"], torch.empty((C, H, W, 4), dtype=torch.float32, device=dev), sa, True)
+                else:
+                    stage_blend_fwd(L, st, lease, C, W, H, s["ch"], _ptr(s["backgrounds"]), s["n_isects"], _ptr(sc), _ptr(sa))
             finally:
                 L.gs_walk_mirror_set(None)
             torch.cuda.current_stream(dev).synchronize()   # (rare: the capacities follow the largest recent frame)
@@ -1011,8 +1064,11 @@ class _Rasterize(torch.autograd.Function):
             _stage("gs_expected_depth_bwd", dev, lambda: nat.check(L.gs_expected_depth_bwd(
                 st, render_alphas.numel(), ch, _ptr(render_colors), _ptr(render_alphas), _ptr(v_out), _ptr(v_ra_in), _ptr(v_rc), _ptr(v_ra)),
                 "gs_expected_depth_bwd"))
-        _stage("gs_blend_bwd", dev, lambda: stage_blend_bwd(L, st, lease, C, W, H, ch, _ptr(render_colors), _ptr(render_alphas), _ptr(v_rc), _ptr(v_ra),
-                                                            _ptr(ucls)))
+        wide = s.get("wide")
+        if wide is None:
+            _stage("gs_blend_bwd", dev, lambda: stage_blend_bwd(L, st, lease, C, W, H, ch, _ptr(render_colors), _ptr(render_alphas), _ptr(v_rc),
+                                                                _ptr(v_ra), _ptr(ucls)))
+        rows_ptr = P(WS.ROWS)
         go = holder.grad_out or {}   # (`_grad_out`: caller-owned gradient tensors; autograd then receives None for those inputs)
         for k_, shp in (("means", (N, 3)), ("quats", (N, 4)), ("scales", (N, 3)), ("opacities", (N,)), ("grad_norm", (N,)), ("count", (N,))):
             if k_ in go and not (go[k_].shape == shp and go[k_].is_contiguous() and go[k_].dtype == torch.float32 and go[k_].device == dev):
@@ -1030,6 +1086,36 @@ class _Rasterize(torch.autograd.Function):
         v_pc, pc_cam = (v_colors, s["per_cam"]) if dc == 3 else (torch.empty((C, N, 3), **f32), 1)
         v_rest = torch.empty(colors_rest.shape, **f32) if (ctx.split and not factorised and dmode != "only") else None
         v_pre = row_sums = None
+        if wide is not None and N > 0:   # (no Gaussian: no rows, and the empty v_colors is complete)
+            # D > 4: the blend backward once per chunk over that chunk's own walk -- the one the lease holds, or the training blend
+            # repeated (a walk is valid with the checkpoints of its launch only) --, the geometry part of its rows folded into an
+            # accumulator the projection backward then takes as its rows, the colour quads summed into the chunk's slice of v_colors.
+            # v_render_alphas goes to the first chunk alone.  Fixed chunk order: a repeated backward adds in the same order.
+            wide["n_isects"] = s["n_isects"]
+            acc = torch.empty((max(n_rows, 1), nat.GS_ROW_FLOATS), **f32)
+            img_d, v_d, alphas_d = torch.empty((C, H, W, 4), **f32), torch.empty((C, H, W, 4), **f32), None
+            for j, (first, count) in enumerate(wide["chunks"]):
+                al = render_alphas
+                if wide["walk"] != j:
+                    al = alphas_d = torch.empty_like(render_alphas) if alphas_d is None else alphas_d
+                    _wide_blend_fwd(L, st, wide, j, img_d, alphas_d, True)
+                else:
+                    if wide["rec"] != j:
+                        nat.check(L.gs_rec_colors_chunk(st, C, N, ch, first, count, _ptr(colors), s["per_cam"], _ptr(s["radii"]), P(WS.REC)),
+                                  "gs_rec_colors_chunk")
+                        wide["rec"] = j
+                    _stage("gs_chunk_gather", dev, lambda: nat.check(L.gs_chunk_gather(st, C * H * W, ch, first, count, _ptr(render_colors),
+                                                                                       _ptr(img_d)), "gs_chunk_gather"))
+                _stage("gs_chunk_gather", dev, lambda: nat.check(L.gs_chunk_gather(st, C * H * W, ch, first, count, _ptr(v_rc), _ptr(v_d)),
+                                                                 "gs_chunk_gather"))
+                _stage("gs_blend_bwd", dev, lambda: stage_blend_bwd(L, st, lease, C, W, H, count, _ptr(img_d), _ptr(al), _ptr(v_d),
+                                                                    _ptr(v_ra) if j == 0 else None, _ptr(ucls)))
+                _stage("gs_rows_accumulate", dev, lambda: nat.check(L.gs_rows_accumulate(st, n_rows, P(WS.ROWS), _ptr(acc), 1 if j == 0 else 0),
+                                                                    "gs_rows_accumulate"))
+                _stage("gs_channel_grads_chunk", dev, lambda: nat.check(L.gs_channel_grads_chunk(
+                    st, C, N, ch, first, count, s["per_cam"], _ptr(s["radii"]), P(WS.TILES_PER_GAUSS), P(WS.CUM_TILES), P(WS.ROWS), P(WS.ROW_BASE),
+                    P(WS.QMASK), _ptr(v_colors)), "gs_channel_grads_chunk"))
+            rows_ptr = _ptr(acc)
         if factorised:
             # Row sums as a pass of their own (gs_row_sums): they yield the colour gradient other ranks need -- and, with
             # `_view_payload`, this rank's whole all-gather record [3N colour gradients | N normalised radii | view matrix] --
@@ -1065,7 +1151,7 @@ class _Rasterize(torch.autograd.Function):
                             _ptr(colors_rest), pc_cam, _ptr(viewmats), _ptr(Ks), W, H, cfg["eps2d"],
                             cfg["near_plane"], cfg["far_plane"], _ptr(s["radii"]),
                             P(WS.COLORS_POST), P(WS.TILES_PER_GAUSS), P(WS.CUM_TILES),
-                            P(WS.ROWS), P(WS.ROW_BASE), P(WS.QMASK), _ptr(v_means), _ptr(v_quats), _ptr(v_scales), _ptr(v_opac),
+                            rows_ptr, P(WS.ROW_BASE), P(WS.QMASK), _ptr(v_means), _ptr(v_quats), _ptr(v_scales), _ptr(v_opac),
                             _ptr(v_pc), _ptr(v_rest), _ptr(v_abs), _ptr(v_m2), _ptr(v_cn), _ptr(v_cp), None,
                             _ptr(opacities), cfg.get("activations", 0), P(WS.SH_JAC) if s.get("sh_jac") else None,
                             _ptr(row_sums), _ptr(go.get("grad_norm")), _ptr(go.get("count")))
@@ -1095,7 +1181,7 @@ class _Rasterize(torch.autograd.Function):
             _stage("gs_project_bwd", dev, lambda: nat.check(L.gs_project_bwd(*bwd_args()), "gs_project_bwd"))
         else:
             _stage("gs_project_bwd", dev, lambda: nat.check(L.gs_project_bwd_cm(*bwd_args(), cam_model), "gs_project_bwd_cm"))
-        if dc != 3 and dc > 0:
+        if dc != 3 and dc > 0 and wide is None:
             _stage("gs_channel_grads", dev, lambda: nat.check(L.gs_channel_grads(
                 st, C, N, dc, s["per_cam"], _ptr(s["radii"]), P(WS.TILES_PER_GAUSS), P(WS.CUM_TILES), P(WS.ROWS), P(WS.ROW_BASE),
                 P(WS.QMASK), _ptr(v_colors)), "gs_channel_grads"))
@@ -1113,7 +1199,8 @@ class _Rasterize(torch.autograd.Function):
             holder.grad_out["_written"] = True   # (the caller's own dict: it can tell that its tensors were filled by THIS backward)
         if dbg is not None:
             dbg.update(v_means2d=v_m2, v_conics=v_cn, v_colors_post=v_cp,
-                       rows=lease.view(WS.ROWS, max(n_rows, 1) * nat.GS_ROW_FLOATS)[: n_rows * nat.GS_ROW_FLOATS].clone().view(-1, nat.GS_ROW_FLOATS))
+                       rows=acc[:n_rows] if (wide is not None and N > 0) else   # (D > 4: the chunks' geometry sums; colour quads zero)
+                       lease.view(WS.ROWS, max(n_rows, 1) * nat.GS_ROW_FLOATS)[: n_rows * nat.GS_ROW_FLOATS].clone().view(-1, nat.GS_ROW_FLOATS))
         if m2_out is not None:
             if holder.absgrad:
                 m2_out.absgrad = v_abs
@@ -1193,7 +1280,7 @@ def rasterization(
     quats: Tensor,  # [N, 4]  wxyz, need not be normalised
     scales: Tensor,  # [N, 3]
     opacities: Tensor,  # [N]
-    colors,  # Tensor [N, K, 3] SH coefficients (sh_degree given) or features [N, D] / [C, N, D], D = 1..4; or (sh_0, sh_rest)
+    colors,  # Tensor [N, K, 3] SH coefficients (sh_degree given) or features [N, D] / [C, N, D], D >= 1; or (sh_0, sh_rest)
     viewmats: Tensor,  # [C, 4, 4] world -> camera
     Ks: Tensor,  # [C, 3, 3]
     width: int,
@@ -1231,7 +1318,17 @@ def rasterization(
     Colour features (`sh_degree=None`): `colors` [N,D] or [C,N,D] with D in 1..4, `backgrounds` [C,D]; gsplat's semantics -- no
     clamp, background added as (1 - alpha) * bg per channel, gradients to means, quats, scales, opacities, colours and `.absgrad`.
     D = 3 is the RGB path; D = 1, 2, 4 go through the channel entry points (include/gs_raster.h), always in ONE depth round
-    whatever `_rounds` / GS_ROUNDS say.  D > 4 raises `NotImplementedError` (no `channel_chunk` splitting).
+    whatever `_rounds` / GS_ROUNDS say.
+
+    D > 4 (`render_mode="RGB"`): the channels are rendered in fixed chunks of four -- `channel_chunks(D)`: [0:4], [4:8], ... and a tail of
+    1 .. 3 -- over ONE projection and ONE set of tile lists (INTEGRATION.md "More than four feature channels").  Chunk j
+    of the image, the alphas and (without an upstream gradient on the alphas) of the colour gradient are bit for bit what the call on
+    `colors[..., first:first+count]`, `backgrounds[:, first:first+count]` returns; the geometry gradients are the sum over the chunks.
+    `camera_model`, `rasterize_mode`, `_activations`, `_camera_grads` and every `_tile_culling` work as for D <= 4, always in one depth
+    round.  `channel_chunk` is accepted and ignored: chunks are always 4 wide.  Refused with `NotImplementedError`: D > 4 with a depth
+    render mode, on CPU tensors, and with `absgrad=True` -- the per-pixel |v_means2d| behind `.absgrad` is not additive over chunks
+    (gsplat's own chunked path leaves the last chunk's value there -- as remembered from its source, not checked against a run of it),
+    and no definition is invented here.
 
     `render_mode` (gsplat's): "RGB+D" / "RGB+ED" append the projection's camera-space depth (`meta["depths"]`) as one last channel
     to the colours -- SH colours after the clamp, or Dc <= 3 feature channels -- and return [C,H,W,Dc+1]; `backgrounds` stays
@@ -1343,9 +1440,12 @@ def rasterization(
         assert (colors.dim() == 2 and colors.shape[0] == N) or (
             colors.dim() == 3 and colors.shape[:2] == (C, N)), colors.shape
         assert colors.shape[-1] >= 1, colors.shape
-        if colors.shape[-1] > 4:
-            raise NotImplementedError(f"colour features of at most 4 channels are implemented on the HIP path (got {colors.shape[-1]}; "
-                                      "channel_chunk splitting is not implemented)")
+        if colors.shape[-1] > 4 and render_mode != "RGB":
+            raise NotImplementedError(f"colour features of more than 4 channels (got {colors.shape[-1]}) are rendered in chunks of 4 in "
+                                      f"render_mode='RGB' only: render_mode={render_mode!r} has no chunked path (depth as a chunk is not implemented)")
+        if colors.shape[-1] > 4 and absgrad:
+            raise NotImplementedError(f"absgrad=True with more than 4 colour channels (got {colors.shape[-1]}) is not implemented: the per-pixel "
+                                      "|v_means2d| is not additive over the chunks of 4 the channels are rendered in")
     else:
         assert colors.dim() == 3 and colors.shape[0] == N and colors.shape[2] == 3, colors.shape
         k_store = colors.shape[1] + (0 if colors_rest is None else colors_rest.shape[1])
@@ -1398,6 +1498,9 @@ def rasterization(
         if depth:   # (a NotImplementedError, which is a RuntimeError: callers that probed for the depth modes keep their handler)
             raise NotImplementedError(f"render_mode={render_mode!r} runs on the GPU only: tensors must live on a HIP device "
                                       "(there is no CPU fallback in this package)")
+        if sh_degree is None and colors.shape[-1] > 4:   # (a NotImplementedError, as before chunks existed: callers' handlers keep working)
+            raise NotImplementedError(f"more than 4 colour channels (got {colors.shape[-1]}; rendered in chunks of 4) run on the GPU only: "
+                                      "tensors must live on a HIP device (there is no CPU fallback in this package)")
         raise RuntimeError("rasterization() runs on the GPU only: tensors must live on a HIP device "
                            "(there is no CPU fallback in this package)")
     nat.lib()  # fail loudly here if the extension is missing

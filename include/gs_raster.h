@@ -420,6 +420,36 @@ int gs_channel_grads(void* stream, int C, int64_t N, int channels, int colors_pe
                      const int32_t* tiles_per_gauss, const int32_t* cum_tiles, const float* rows, const int32_t* row_base,
                      const uint8_t* qmask, float* v_colors);
 
+/* Colour features of more than four channels (colors[N,D] / [C,N,D], D >= 5): rendered in chunks of four channels -- [0,4), [4,8),
+ * ... and a tail of 1 .. 3 -- over ONE projection and ONE set of tile lists, through the 1 .. 4 channel blend above.  A chunk is
+ * (first, count): first a multiple of 4, 1 <= count <= 4, first + count <= D.  A call sequence:
+ *   forward   gs_project_fwd(sh_degree = -1, stage = 1), the list stages; per chunk: gs_rec_colors_chunk, gs_blend_fwd_ch(count)
+ *             into a dense [C,H,W,count] image, gs_chunk_scatter into [C,H,W,D].  Only a chunk blended in training mode leaves a
+ *             walk (checkpoints, sublists, row bases), and a walk is valid with the checkpoints of its own launch alone.
+ *   backward  per chunk: (gs_rec_colors_chunk + gs_blend_fwd_ch in training mode unless the walk at hand is this chunk's,)
+ *             gs_chunk_gather of v_render_colors (and of the image), gs_blend_bwd_ch(count) -- v_render_alphas to ONE chunk, NULL
+ *             to the others --, gs_rows_accumulate, gs_channel_grads_chunk; then gs_project_bwd(rows = the accumulator).
+ * The row bases and quadrant masks depend on the footprints and alphas alone, so the rows of every chunk's backward are the same
+ * rows.  Every entry point checks its chunk, its pointers (non-NULL; 4-byte aligned, 16-byte where whole quads move: rec, rows,
+ * acc, qmask always, a D-wide or dense array when count = 4 and D is a multiple of 4) before it launches anything, and honours the
+ * step guard -- gs_chunk_scatter / gs_chunk_gather its list flags alone: GS_FLAG_UNITS / GS_FLAG_ROWS, which the training blend in
+ * front of a scatter raises, void the walk and not the image that launch completed.
+ * gs_rec_colors_chunk: gs_rec_colors from channels [first, first + count) of colors[.., D]; the quad is zero above count.
+ * gs_channel_grads_chunk: gs_channel_grads' sums (same order), stored to v_colors[.., D] at channels [first, first + count); the
+ *   other channels are not touched.
+ * gs_rows_accumulate: acc[n_rows*12] floats 0..7 of each row = (first_chunk ? 0 : acc) + rows; first_chunk also zeroes floats 8..11,
+ *   which later calls leave alone.  rows and acc are two buffers.
+ * gs_chunk_scatter: dst[p*D + first + k] = src[p*count + k]; gs_chunk_gather: dst[p*count + k] = src[p*D + first + k];
+ *   p < n_pixels, k < count. */
+int gs_rec_colors_chunk(void* stream, int C, int64_t N, int D, int first, int count, const float* colors, int colors_per_camera,
+                        const int32_t* radii, float* rec);
+int gs_channel_grads_chunk(void* stream, int C, int64_t N, int D, int first, int count, int colors_per_camera, const int32_t* radii,
+                           const int32_t* tiles_per_gauss, const int32_t* cum_tiles, const float* rows, const int32_t* row_base,
+                           const uint8_t* qmask, float* v_colors);
+int gs_rows_accumulate(void* stream, int64_t n_rows, const float* rows, float* acc, int first_chunk);
+int gs_chunk_scatter(void* stream, int64_t n_pixels, int D, int first, int count, const float* src, float* dst);
+int gs_chunk_gather(void* stream, int64_t n_pixels, int D, int first, int count, const float* src, float* dst);
+
 /* Row reduction + SH-bwd + P-bwd fused (replaces the atomics of the blend backward,
  * spherical_harmonics backward and fully_fused_projection backward).  Sums each Gaussian's rows
  * (slots [cum_tiles[f], cum_tiles[f]+tiles_per_gauss[f]) = rows [rows_before(first slot), rows_before(last slot + 1)): row_base + qmask) and

@@ -2,8 +2,9 @@
 """Kernel times of the rasterizer's stages on a FIXED scene (no optimizer in the loop): rasterization forward + backward of the
 bench workload, HIP events around every stage (rendering.profile_stages), 30 repetitions.  For A/B runs of library variants
 whose backward may be numerically wrong on purpose (timing experiments):  GS_LIB_PATH=... tools/blend_time.py [n_gauss]
-`--channels D` (D = 1 .. 4): non-SH colour features [N, D] with backgrounds [1, D] instead of the SH colours (D = 3: the RGB path
-with pre-activated colours; D = 1, 2, 4: the channel entry points).
+`--channels D`: non-SH colour features [N, D] with backgrounds [1, D] instead of the SH colours (D = 3: the RGB path
+with pre-activated colours; D = 1, 2, 4: the channel entry points; D > 4: chunks of four over one set of lists, without `absgrad`,
+which such a call refuses -- a stage that runs once per chunk is reported as the median of all its launches).
 `--render-mode M[,M...]` (RGB, D, ED, RGB+D, RGB+ED): the render modes to time; several are interleaved step by step in this one
 process (an A/B on one box) and reported one JSON line each."""
 import json, os, sys
@@ -39,7 +40,7 @@ def step(mode="RGB"):
         params = ins + [sh0, shr]
     else:
         img, _, meta = rendering.rasterization(*ins, feats, t["viewmats"], t["Ks"], 1920, 1080, sh_degree=None, packed=False,
-                                               backgrounds=bg, absgrad=True, _tile_culling="tight", render_mode=mode)
+                                               backgrounds=bg, absgrad=channels <= 4, _tile_culling="tight", render_mode=mode)
         params = ins + [feats]
     if mode not in vcs:
         vcs[mode] = torch.randn_like(img) / (1920 * 1080)
