@@ -14,6 +14,8 @@ import torch
 import torch.nn.functional as F
 from torch import Tensor, nn
 
+from .optim import DenseAdamState
+
 LUMA = (0.299, 0.587, 0.114)
 
 
@@ -164,25 +166,10 @@ class BilateralGrids(nn.Module):
         return tv_reference(self.grids)
 
 
-class BilagridAdamState:
+class BilagridAdamState(DenseAdamState):
     """Adam's state for `BilateralGrids` stepped inside the captured train step (`TrainStepGraph(bilagrid=...)` makes one:
     `runner.bilagrid_state`): the two moments, shaped like `grids`, on its device and the number of steps taken -- dense Adam, every
     step counts for every view.  `state_dict()` / `load_state_dict()` let a checkpoint carry it next to `grids.state_dict()`."""
 
     def __init__(self, grids: BilateralGrids):
-        g = grids.grids
-        self.exp_avg = torch.zeros(tuple(g.shape), dtype=torch.float32, device=g.device)
-        self.exp_avg_sq = torch.zeros(tuple(g.shape), dtype=torch.float32, device=g.device)
-        self.step = 0
-
-    def state_dict(self):
-        return {"exp_avg": self.exp_avg.clone(), "exp_avg_sq": self.exp_avg_sq.clone(), "step": int(self.step)}
-
-    def load_state_dict(self, state) -> None:
-        """In place: the captured step keeps reading the same buffers."""
-        for name in ("exp_avg", "exp_avg_sq"):
-            src, dst = state[name], getattr(self, name)
-            if tuple(src.shape) != tuple(dst.shape):
-                raise ValueError(f"BilagridAdamState.load_state_dict: {name} of shape {tuple(src.shape)}, expected {tuple(dst.shape)}")
-            dst.copy_(src)
-        self.step = int(state["step"])
+        super().__init__(grids.grids)

@@ -11,6 +11,8 @@ from __future__ import annotations
 import torch
 from torch import Tensor, nn
 
+from .optim import DenseAdamState
+
 
 class _ExposureApply(torch.autograd.Function):
     """HIP path (csrc/gs_exposure.hip): one streaming kernel forward; backward one more that turns dL/d out into dL/d image in place
@@ -72,26 +74,11 @@ class ExposureTable(nn.Module):
         return image @ a[i, :, :3].to(image.dtype).T + a[i, :, 3].to(image.dtype)
 
 
-class ExposureAdamState:
+class ExposureAdamState(DenseAdamState):
     """Adam's state for an `ExposureTable` stepped inside the captured train step (`TrainStepGraph(exposure=...)` makes one:
     `runner.exposure_state`): the two moments [n_views, 3, 4] on the table's device and the number of exposure steps taken -- dense
     Adam, every step counts for every row.  `state_dict()` / `load_state_dict()` let a checkpoint carry it next to
     `table.state_dict()`."""
 
     def __init__(self, table: ExposureTable):
-        a = table.affine
-        self.exp_avg = torch.zeros(tuple(a.shape), dtype=torch.float32, device=a.device)
-        self.exp_avg_sq = torch.zeros(tuple(a.shape), dtype=torch.float32, device=a.device)
-        self.step = 0
-
-    def state_dict(self):
-        return {"exp_avg": self.exp_avg.clone(), "exp_avg_sq": self.exp_avg_sq.clone(), "step": int(self.step)}
-
-    def load_state_dict(self, state) -> None:
-        """In place: the captured step keeps reading the same buffers."""
-        for name in ("exp_avg", "exp_avg_sq"):
-            src, dst = state[name], getattr(self, name)
-            if tuple(src.shape) != tuple(dst.shape):
-                raise ValueError(f"ExposureAdamState.load_state_dict: {name} of shape {tuple(src.shape)}, expected {tuple(dst.shape)}")
-            dst.copy_(src)
-        self.step = int(state["step"])
+        super().__init__(table.affine)

@@ -207,3 +207,26 @@ class FusedAdam(torch.optim.Optimizer):
                 p.grad = None
             elif p.grad is not None:
                 p.grad.zero_()
+
+
+class DenseAdamState:
+    """Adam's state for one dense table stepped inside the captured train step (`pose.PoseAdamState`, `exposure.ExposureAdamState`,
+    `bilagrid.BilagridAdamState`): the two moments, shaped like the table, on its device and the number of steps taken -- dense
+    Adam, every step counts for every row.  `state_dict()` / `load_state_dict()` let a checkpoint carry it next to the table's own."""
+
+    def __init__(self, table: torch.Tensor):
+        self.exp_avg = torch.zeros(tuple(table.shape), dtype=torch.float32, device=table.device)
+        self.exp_avg_sq = torch.zeros(tuple(table.shape), dtype=torch.float32, device=table.device)
+        self.step = 0
+
+    def state_dict(self):
+        return {"exp_avg": self.exp_avg.clone(), "exp_avg_sq": self.exp_avg_sq.clone(), "step": int(self.step)}
+
+    def load_state_dict(self, state) -> None:
+        """In place: the captured step keeps reading the same buffers."""
+        for name in ("exp_avg", "exp_avg_sq"):
+            src, dst = state[name], getattr(self, name)
+            if tuple(src.shape) != tuple(dst.shape):
+                raise ValueError(f"{type(self).__name__}.load_state_dict: {name} of shape {tuple(src.shape)}, expected {tuple(dst.shape)}")
+            dst.copy_(src)
+        self.step = int(state["step"])

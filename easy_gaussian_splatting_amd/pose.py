@@ -8,6 +8,8 @@ from __future__ import annotations
 import torch
 from torch import Tensor, nn
 
+from .optim import DenseAdamState
+
 
 class CameraDeltas(nn.Module):
     """One 6-vector per training view: axis-angle `omega` (3) and translation `tau` (3), zero-initialised, applied on the camera
@@ -34,25 +36,10 @@ class CameraDeltas(nn.Module):
         return torch.cat([top, bottom], dim=0) @ w2c.to(d.dtype)
 
 
-class PoseAdamState:
+class PoseAdamState(DenseAdamState):
     """Adam's state for a `CameraDeltas` stepped inside the captured train step (`TrainStepGraph(poses=...)` makes one:
     `runner.pose_state`): the two moments [n_views, 6] on the deltas' device and the number of pose steps taken -- dense Adam, every
     step counts for every row.  `state_dict()` / `load_state_dict()` let a checkpoint carry it next to `poses.state_dict()`."""
 
     def __init__(self, poses: CameraDeltas):
-        d = poses.deltas
-        self.exp_avg = torch.zeros(tuple(d.shape), dtype=torch.float32, device=d.device)
-        self.exp_avg_sq = torch.zeros(tuple(d.shape), dtype=torch.float32, device=d.device)
-        self.step = 0
-
-    def state_dict(self):
-        return {"exp_avg": self.exp_avg.clone(), "exp_avg_sq": self.exp_avg_sq.clone(), "step": int(self.step)}
-
-    def load_state_dict(self, state) -> None:
-        """In place: the captured step keeps reading the same buffers."""
-        for name in ("exp_avg", "exp_avg_sq"):
-            src, dst = state[name], getattr(self, name)
-            if tuple(src.shape) != tuple(dst.shape):
-                raise ValueError(f"PoseAdamState.load_state_dict: {name} of shape {tuple(src.shape)}, expected {tuple(dst.shape)}")
-            dst.copy_(src)
-        self.step = int(state["step"])
+        super().__init__(poses.deltas)

@@ -62,10 +62,12 @@ from __future__ import annotations
 
 import ctypes as ct
 import math
+import os
 import time
 from collections import deque
 from collections.abc import Mapping
-from typing import Any, Dict, Optional, Tuple
+from dataclasses import dataclass
+from typing import Any, Dict, List, Optional, Tuple
 
 import torch
 from torch import Tensor
@@ -122,39 +124,52 @@ def _pose_view(poses, view_index, exposure=None, bilagrid=None) -> Optional[int]
         raise ValueError("TrainStepGraph.step: the runner refines poses (poses=CameraDeltas): every step needs view_index=i, the row of "
                          "`poses.deltas` that corrects data['w2c']")
     i = int(view_index)
-    for what, table in (("poses", None if poses is None else poses.deltas), ("exposure", None if exposure is None else exposure.affine),
-                        ("bilagrid", None if bilagrid is None else bilagrid.grids)):
-        if table is not None and not 0 <= i < int(table.shape[0]):
-            raise ValueError(f"TrainStepGraph.step: view_index {i} outside the {int(table.shape[0])} views of `{what}`")
+    for what, owner, table in (("poses", poses, "deltas"), ("exposure", exposure, "affine"), ("bilagrid", bilagrid, "grids")):
+        if owner is not None and not 0 <= i < int(getattr(owner, table).shape[0]):
+            raise ValueError(f"TrainStepGraph.step: view_index {i} outside the {int(getattr(owner, table).shape[0])} views of `{what}`")
     return i
 
 
-def _refuse_camera_model_combinations(camera_model, mcmc, poses, depth, rounds) -> None:
-    """TrainStepGraph(camera_model=...): what the non-pinhole models cannot be combined with, before any device work."""
+# The variants of the fused projection backward + Adam exist one at a time: (option, the entry or kernel that a combination with it
+# lacks), in the order in which the refusals fire.  `{where}`: the non-default setting the option was combined with.
+_ONE_VARIANT = (
+    ("`mcmc`", "the fused projection backward + Adam with the budget regulariser (gs_project_bwd_adam_mcmc: project_bwd_budget_kernel) "
+               "does not exist {where} yet"),
+    ("`poses`", "the fused projection backward + Adam from the row sums and the camera gradient from them (gs_project_bwd_adam_sums, "
+                "gs_cam_grad_sums: project_cam_kernel<DEG, SUMS = true>) do not exist {where} yet; refine poses in the eager loop "
+                "(rasterization(..., _camera_grads=True))"),
+    ("`depth`", "the fused projection backward + Adam with the depth gradient (gs_project_bwd_adam_depth: project_bwd_depth_kernel) "
+                "does not exist {where} yet"),
+    ("rounds='on'", "one depth round only: the fused projection backward over the two row ranges of a two-round step (project_bwd_kernel "
+                    "with ProjBwdArgs.rblk) is not instantiated {where} yet"))
+# What is non-default -> (where its variant stands, what it cannot be combined with)
+_REFUSED = {
+    "camera_model": ("for this camera model", _ONE_VARIANT),
+    "rasterize_mode": ("in the antialiased mode", (("camera_model", "the antialiased projection and its fused backward + Adam (gs_project_fwd_aa, "
+                                                    "gs_project_bwd_adam_aa: project_bwd_aa_kernel) exist for the pinhole model only"),) + _ONE_VARIANT),
+    "depth": ("", (("`poses`", "the camera gradient of the depth term is not formed inside the captured step; supervise depth on fixed "
+                               "cameras, or refine poses in the eager loop"),
+                   ("rounds='on'", "the depth lane's gradient gather is one-round only (gs_rec_depth / gs_depth_grads); leave rounds at "
+                                   "'auto' (it resolves to off) or 'off'")))}
+
+
+def _refuse_combinations(model, camera_model, rasterize_mode, mcmc, poses, depth, rounds) -> str:
+    """TrainStepGraph(camera_model=..., rasterize_mode=..., depth=...): validates the three, resolves the mode against the model's
+    attribute and refuses, before any device work, what `_REFUSED` lists for each that is not at its default.  Returns the mode."""
+    given = {"camera_model": camera_model != "pinhole", "`mcmc`": mcmc is not None, "`poses`": poses is not None, "`depth`": depth is not None,
+             "rounds='on'": rounds == "on"}
+
+    def refuse(setting: str, what: str) -> None:
+        where, options = _REFUSED[setting]
+        for option, missing in options:
+            if given[option]:
+                option = f"camera_model={camera_model!r}" if option == "camera_model" else option
+                raise ValueError(f"TrainStepGraph({what}) with {option} -- " + missing.format(where=where))
+
     if camera_model not in rendering.CAMERA_MODELS:
         raise ValueError(f"TrainStepGraph: camera_model: one of {sorted(rendering.CAMERA_MODELS)} (got {camera_model!r})")
-    if camera_model == "pinhole":
-        return
-    what = f"TrainStepGraph(camera_model={camera_model!r})"
-    if mcmc is not None:
-        raise ValueError(f"{what} with `mcmc` -- the fused projection backward + Adam with the budget regulariser "
-                         "(gs_project_bwd_adam_mcmc: project_bwd_budget_kernel) does not exist for this camera model yet")
-    if poses is not None:
-        raise ValueError(f"{what} with `poses` -- the fused projection backward + Adam from the row sums and the camera gradient from "
-                         "them (gs_project_bwd_adam_sums, gs_cam_grad_sums: project_cam_kernel<DEG, SUMS = true>) do not exist for this "
-                         "camera model yet; refine poses in the eager loop (rasterization(camera_model=..., _camera_grads=True))")
-    if depth is not None:
-        raise ValueError(f"{what} with `depth` -- the fused projection backward + Adam with the depth gradient "
-                         "(gs_project_bwd_adam_depth: project_bwd_depth_kernel) does not exist for this camera model yet")
-    if rounds == "on":
-        raise ValueError(f"{what} with rounds='on' -- the camera models other than pinhole run in one depth round: the fused projection "
-                         "backward over the two row ranges of a two-round step (project_bwd_kernel with ProjBwdArgs.rblk) is not "
-                         "instantiated for this camera model yet")
-
-
-def _refuse_rasterize_mode_combinations(rasterize_mode, model, camera_model, mcmc, poses, depth, rounds) -> str:
-    """TrainStepGraph(rasterize_mode=...): resolves the mode against the model's attribute and refuses, before any device work, what the
-    antialiased mode cannot be combined with.  Returns the mode."""
+    if camera_model != "pinhole":
+        refuse("camera_model", f"camera_model={camera_model!r}")
     model_mode = getattr(model, "rasterize_mode", "classic")
     if rasterize_mode is None:
         rasterize_mode = model_mode
@@ -163,29 +178,41 @@ def _refuse_rasterize_mode_combinations(rasterize_mode, model, camera_model, mcm
     if rasterize_mode != model_mode:   # (what model(data) would render with in the eager loop, and every evaluation of the model)
         raise ValueError(f"TrainStepGraph: the model's rasterize_mode is {model_mode!r}, but the runner was asked for "
                          f"rasterize_mode={rasterize_mode!r}; set model.rasterize_mode first")
-    if rasterize_mode == "classic":
-        return rasterize_mode
-    what = "TrainStepGraph(rasterize_mode='antialiased')"
-    if camera_model != "pinhole":
-        raise ValueError(f"{what} with camera_model={camera_model!r} -- the antialiased projection and its fused backward + Adam "
-                         "(gs_project_fwd_aa, gs_project_bwd_adam_aa: project_bwd_aa_kernel) exist for the pinhole model only")
-    if mcmc is not None:
-        raise ValueError(f"{what} with `mcmc` -- the fused projection backward + Adam with the budget regulariser "
-                         "(gs_project_bwd_adam_mcmc: project_bwd_budget_kernel) does not exist in the antialiased mode yet")
-    if poses is not None:
-        raise ValueError(f"{what} with `poses` -- the fused projection backward + Adam from the row sums and the camera gradient from "
-                         "them (gs_project_bwd_adam_sums, gs_cam_grad_sums: project_cam_kernel<DEG, SUMS = true>) do not exist in the "
-                         "antialiased mode yet; refine poses in the eager loop (rasterization(rasterize_mode='antialiased', _camera_grads=True))")
+    if rasterize_mode != "classic":
+        refuse("rasterize_mode", "rasterize_mode='antialiased'")
     if depth is not None:
-        raise ValueError(f"{what} with `depth` -- the fused projection backward + Adam with the depth gradient "
-                         "(gs_project_bwd_adam_depth: project_bwd_depth_kernel) does not exist in the antialiased mode yet")
-    if rounds == "on":
-        raise ValueError(f"{what} with rounds='on' -- the antialiased mode runs in one depth round: the fused projection backward over "
-                         "the two row ranges of a two-round step (project_bwd_kernel with ProjBwdArgs.rblk) is not instantiated for it yet")
+        from .depth_loss import DepthSupervision
+        if not isinstance(depth, DepthSupervision):
+            raise TypeError("TrainStepGraph(depth=...): a depth_loss.DepthSupervision")
+        refuse("depth", "depth=...")
     return rasterize_mode
 
 
+@dataclass(slots=True)
+class _Pending:
+    """One step as it is queued: what `_stage_inputs` hands to the device in front of the graph, and what an overflow recovery
+    replays.  `self.pending` holds the steps issued but not yet confirmed applied; `self._staged` is the one staged last -- the
+    defaults of a later `step()` that brings no `data`, `gt_img` or `gt_depth`.  Inputs are kept by reference (`step`)."""
+    t: int                       # Adam's step count
+    lrs: List[float]             # the learning rates of the optimizer's groups as they stood at the call
+    w2c: Tensor
+    K: Tensor
+    gt: Tensor                   # the target image: the tensor the loss kernels read in place, kept alive until the step is applied
+    mask: Optional[Tensor]
+    inputs_ready: bool = False   # `step(inputs_ready=)`
+    conv: Any = None             # an event behind the runner's own conversion / copy of a target on the caller's stream
+    ready_event: Any = None      # `step(ready_event=)`
+    host_src: Any = None         # `step(host_src=)`
+    # the per-feature values a replay re-stages like t and the learning rates; None: the runner was built without the feature
+    pose: Optional[Tuple[int, int]] = None               # (view, pose step count)
+    exposure: Optional[Tuple[int, int, float]] = None    # (view, exposure step count, learning rate)
+    bilagrid: Optional[Tuple[int, int, float]] = None    # (view, the grids' step count, learning rate)
+    depth: Optional[Tuple[Tensor, float]] = None         # (target, lambda_depth)
+
+
 class TrainStepGraph:
+    poses = exposure = bilagrid = depth = mcmc = None   # the optional features: off until the constructor is handed one
+
     def __init__(self, model, optimizer: FusedAdam, loss_computer, data: Dict[str, Any], gt_img: Tensor,
                  mask: Optional[Tensor] = None, margin: float = 1.3, use_graph: bool = True, check_every: int = 16,
                  fuse_adam: bool = True, handback: str = "eager", copy_targets: bool = False, rounds: str = "auto",
@@ -259,21 +286,12 @@ class TrainStepGraph:
         `HostFeed`, always in one depth round ("auto" resolves to off).  Refused before any device work (`ValueError`): `mcmc`, `poses`,
         `depth`, `rounds="on"`, a camera model other than pinhole and `ViewParallelGraphStep` -- each needs a variant of the fused
         projection backward that exists for the classic mode only."""
-        _refuse_camera_model_combinations(camera_model, mcmc, poses, depth, __import__("os").environ.get("GS_TG_ROUNDS", rounds))
+        rounds = os.environ.get("GS_TG_ROUNDS", rounds)
+        self.antialiased = _refuse_combinations(model, camera_model, rasterize_mode, mcmc, poses, depth, rounds) == "antialiased"
         self.camera_model = rendering.CAMERA_MODELS[camera_model]
-        self.antialiased = _refuse_rasterize_mode_combinations(rasterize_mode, model, camera_model, mcmc, poses, depth,
-                                                                __import__("os").environ.get("GS_TG_ROUNDS", rounds)) == "antialiased"
         self.depth = depth
         if depth is not None:
-            from .depth_loss import MODES, DepthSupervision
-            if not isinstance(depth, DepthSupervision):
-                raise TypeError("TrainStepGraph(depth=...): a depth_loss.DepthSupervision")
-            if poses is not None:
-                raise ValueError("TrainStepGraph: `depth` with `poses` -- the camera gradient of the depth term is not formed inside the "
-                                 "captured step; supervise depth on fixed cameras, or refine poses in the eager loop")
-            if __import__("os").environ.get("GS_TG_ROUNDS", rounds) == "on":
-                raise ValueError("TrainStepGraph: `depth` with rounds='on' -- the depth lane's gradient gather is one-round only "
-                                 "(gs_rec_depth / gs_depth_grads); leave rounds at 'auto' (it resolves to off) or 'off'")
+            from .depth_loss import MODES
             if gt_depth is None:
                 raise ValueError("TrainStepGraph(depth=...): the runner needs its first target, gt_depth=[H, W] float32")
             if tuple(gt_depth.shape) != (int(data["height"]), int(data["width"])):
@@ -337,12 +355,12 @@ class TrainStepGraph:
             f32d = dict(dtype=torch.float32, device=d.device)
             self._pose_bufs = {"pose_rec": torch.zeros((nat.GS_POSE_REC_FLOATS,), **f32d), "v_viewmats": torch.zeros((1, 4, 4), **f32d),
                                "v_campos": torch.zeros((1, 3), **f32d), "v_delta": torch.zeros((6,), **f32d)}
-            self._pose_cur = (_pose_view(poses, data.get("view_index", 0)), self.pose_state.step + 1)
         self.poses = poses
-        if exposure is not None:   # (view, exposure step count, learning rate) of the step about to be staged: the build's own
-            self._exposure_cur = (_pose_view(poses, data.get("view_index", 0), exposure), self.exposure_state.step + 1, self.exposure_lr)
-        if bilagrid is not None:   # likewise (view, the grids' step count, learning rate)
-            self._bilagrid_cur = (_pose_view(poses, data.get("view_index", 0), None, bilagrid), self.bilagrid_state.step + 1, self.bilagrid_lr)
+        # (option, prefix of its `<prefix>_lr` / `<prefix>_state`, table, Adam state) of the per-view tables the step updates
+        self._tables = [(option, prefix, getattr(owner, table), getattr(self, prefix + "_state")) for option, prefix, owner, table in
+                        (("poses", "pose", poses, "deltas"), ("exposure", "exposure", exposure, "affine"), ("bilagrid", "bilagrid", bilagrid, "grids"))
+                        if owner is not None]
+        build_view = _pose_view(poses, data.get("view_index", 0) if self._tables else None, exposure, bilagrid)   # the build's own view
         self.mcmc = mcmc
         if mcmc is not None:
             if getattr(mcmc, "noise", None) != "counter":
@@ -364,10 +382,9 @@ class TrainStepGraph:
         # (realistic footprints: 20-50 x) -- the two-round pipeline costs ~0.1 ms of extra launches, which a scene that walks most
         # of what it lists never earns back; "on" / "off" force it.  round_fraction: the share of the listed intersections in
         # front of the depth split.
-        rounds = __import__("os").environ.get("GS_TG_ROUNDS", rounds)
-        if rounds not in ("auto", "on", "off"):
+        if rounds not in ("auto", "on", "off"):   # (GS_TG_ROUNDS in the environment overrides the argument: read at the top)
             raise ValueError("rounds: 'auto', 'on' or 'off'")
-        self.rounds_mode, self.round_fraction = rounds, float(__import__("os").environ.get("GS_TG_ROUND_FRACTION", round_fraction))
+        self.rounds_mode, self.round_fraction = rounds, float(os.environ.get("GS_TG_ROUND_FRACTION", round_fraction))
         if (depth is not None or self.camera_model != nat.GS_CAMERA_PINHOLE or self.antialiased) and rounds == "auto":
             rounds = self.rounds_mode = "off"   # (one round: see `depth`, `camera_model`, `rasterize_mode`)
         self.rounds_on = rounds == "on"
@@ -421,7 +438,7 @@ class TrainStepGraph:
         self.binning = None
         self.probed = (0, 0)
         self.cap_tile = _sort_class(0)
-        self.pending: deque = deque()     # steps issued but not yet confirmed applied: (t, lrs, w2c, K, gt, mask)
+        self.pending: deque = deque()     # steps issued but not yet confirmed applied: `_Pending` records
         # {I, n_buckets, max tile, flags, applied} of the latest finished step, written by the device (gs_step_status)
         self.status = torch.zeros((8,), dtype=torch.int64, pin_memory=True)
         self.confirmed = 0                # steps known to be applied
@@ -432,13 +449,15 @@ class TrainStepGraph:
         self._warm = set()     # (binning mode, tile-sort class) pairs that have run EAGERLY in this runner (warm-up steps)
         self._key = None
         self.confirmed_at_build = 0
-        self._last_inputs = (data["w2c"], data["K"], gt_img, mask)
         if depth is not None:
-            # runner-owned, alive across re-builds: the record {lambda, mode, target address, value, 1 / sum(w)}; the target and the
-            # weight of the step about to be staged: the build's own
+            # runner-owned, alive across re-builds: the record {lambda, mode, target address, value, 1 / sum(w)}
             self._depth_bufs = {"depth_rec": torch.zeros((nat.GS_DEPTH_REC_FLOATS,), dtype=torch.float32, device=self.dev)}
-            self._depth_cur = (self._depth_image(gt_depth, (self.H, self.W)), self.lambda_depth)
-        self._build(data, gt_img, mask)
+        # the build's own step: the view of `data`, each table's step count + 1 and its rate, the first depth target and its weight
+        self._build(self._next_step(data["w2c"], data["K"], gt_img, mask,
+                                    pose=(build_view, self.pose_state.step + 1) if poses is not None else None,
+                                    exposure=(build_view, self.exposure_state.step + 1, self.exposure_lr) if exposure is not None else None,
+                                    bilagrid=(build_view, self.bilagrid_state.step + 1, self.bilagrid_lr) if bilagrid is not None else None,
+                                    depth=(self._depth_image(gt_depth, (self.H, self.W)), self.lambda_depth) if depth is not None else None))
 
     # ------------------------------------------------------------------------------------------ workspace
     def _state_key(self, W: Optional[int] = None, H: Optional[int] = None):
@@ -449,8 +468,16 @@ class TrainStepGraph:
                 m.collecting_counts.data_ptr(), m.active_sh_degree, getattr(m, "tile_culling", "tight"),
                 self.W if W is None else int(W), self.H if H is None else int(H))
 
-    def _build(self, data, gt_img, mask, min_cap: int = 0, min_cap_tile: int = 0, projected=None, min_walk=(0, 0)):
-        """(Re-)allocates the workspace for the model as it is now, learns the capacities from one blocking probe
+    def _lrs(self) -> List[float]:
+        return [float(grp["lr"]) for grp, _ in self.opt._plist]
+
+    def _next_step(self, w2c: Tensor, K: Tensor, gt: Tensor, mask: Optional[Tensor], **staged) -> _Pending:
+        """The record a (re-)build stages for its probe and warm-up: the step that would come next, at t = the optimizer's step
+        count + 1 and the learning rates as they stand -- consumed by nobody."""
+        return _Pending(max(self.opt._step, 0) + 1, self._lrs(), w2c, K, gt, mask if self.has_mask else None, **staged)
+
+    def _build(self, staged: _Pending, min_cap: int = 0, min_cap_tile: int = 0, projected=None, min_walk=(0, 0)):
+        """(Re-)allocates the workspace for the model as it is now, stages `staged`, learns the capacities from one blocking probe
         of the list sizes if needed, warms every kernel up eagerly and captures the step.
         `projected` = (I, longest tile list, storage units, gradient rows) carried over from the steps before a refinement (`step()`): no probe, no
         warm-up step -- the re-build is allocation + capture and never touches the device's queue.  (A projection that
@@ -534,7 +561,7 @@ class TrainStepGraph:
             b["mcmc_reg"] = self._take("mcmc_reg", (int(L.gs_mcmc_reg_workspace_floats(N)),), torch.float32)
             b["mcmc_rec"] = torch.zeros((nat.GS_MCMC_REC_WORDS,), dtype=torch.int64, device=dev)
             self._means_seg = [grp["name"] for grp, _ in self.opt._plist].index("means")
-        self._stage_inputs(max(self.opt._step, 0) + 1, [float(grp["lr"]) for grp, _ in self.opt._plist], data["w2c"], data["K"], gt_img, mask)
+        self._stage_inputs(staged)
         probe_walk = False
         front_before, self.front_only = self.front_only, False   # (the probes below run both rounds)
         if projected is not None:
@@ -664,7 +691,7 @@ class TrainStepGraph:
     ROUNDS_MIN_LISTED = 4_000_000   # "auto": below this the list stages are too short for a second round to pay
     ROUNDS_MIN_RATIO = 4.0          # ... and so they are when the frame lists less than this many entries per gradient row
     ROUNDS_MAX_LIVE = 0.05          # ... and rounds stay off where the front slab leaves more than this share of the tiles live
-    speculate_front = __import__('os').environ.get('GS_TG_FRONT_ONLY', '1') != '0'   # 0: "auto" never captures the front round alone
+    speculate_front = os.environ.get('GS_TG_FRONT_ONLY', '1') != '0'   # 0: "auto" never captures the front round alone
     _back_needed = False
 
     def _alloc_rounds(self):
@@ -712,11 +739,12 @@ class TrainStepGraph:
         with "same as the buffer holds" get a snapshot of it first (enqueued ahead of the overwrite on the same stream)."""
         snap = None
         for e in self.pending:
-            for i in range(2, 6):
-                if isinstance(e[i], Tensor) and e[i].data_ptr() == static.data_ptr():
+            for name in ("w2c", "K", "gt", "mask"):   # (the fields that can alias a static buffer)
+                x = getattr(e, name)
+                if isinstance(x, Tensor) and x.data_ptr() == static.data_ptr():
                     if snap is None:
                         snap = static.clone()
-                    e[i] = snap[0] if (e[i].dim() < static.dim()) else snap
+                    setattr(e, name, snap[0] if (x.dim() < static.dim()) else snap)
 
     def _image(self, t: Tensor, shape) -> Tensor:
         """The caller's image as the loss kernels read it: float32, contiguous, on the runner's device (a tensor that already is
@@ -737,12 +765,13 @@ class TrainStepGraph:
         """The step's static camera INPUT [1,4,4]: the view matrix the projection reads, or (poses) the raw matrix in the pose record."""
         return self.buf["w2c_raw"] if self.poses is not None else self.buf["viewmats"]
 
-    def _stage_inputs(self, t: int, lrs, w2c: Tensor, K: Tensor, gt: Tensor, mask: Optional[Tensor], pose=None, exposure=None,
-                      bilagrid=None, depth=None):
+    def _stage_inputs(self, e: _Pending):
         """Everything that differs from the previous step, in ONE launch on the current stream (gs_step_inputs): Adam's bias
         corrections / learning rates, the camera into the static buffers, and the POINTERS to the target image and mask.
-        Returns the (gt, mask) tensors whose pointers went in -- the caller keeps them alive until the step is applied."""
+        Leaves in the record the (gt, mask) tensors whose pointers went in -- it keeps them alive until the step is applied --
+        and the record in `self._staged`."""
         L, b, opt = nat.lib(), self.buf, self.opt
+        t, lrs, w2c, K = e.t, e.lrs, e.w2c, e.K
         ok = lambda x, n: x.device == self.dev and x.dtype == torch.float32 and x.is_contiguous() and x.numel() == n   # noqa: E731
         vm_src = k_src = None
         static_vm = self._static_w2c()
@@ -758,38 +787,34 @@ class TrainStepGraph:
                 k_src = K
             else:
                 b["Ks"][0].copy_(K, non_blocking=True)
-        gt = self._image(gt, (self.H, self.W, 3))
-        if self.has_mask:
-            if mask is None:
-                raise ValueError("this runner was built with a mask; pass one every step")
-            mask = self._image(mask, (self.H, self.W))
-        else:
-            mask = None
+        gt = e.gt = self._image(e.gt, (self.H, self.W, 3))
+        if self.has_mask and e.mask is None:
+            raise ValueError("this runner was built with a mask; pass one every step")
+        mask = e.mask = self._image(e.mask, (self.H, self.W)) if self.has_mask else None
         ns = len(opt._plist)
         b1, b2 = opt.defaults["betas"]
         nat.check(L.gs_step_inputs(self._st(), ns, (ct.c_float * ns)(*lrs), float(b1), float(b2), int(t), _p(b["hyper"]),
                                    None if self.poses is not None else _p(vm_src), _p(b["viewmats"]), _p(k_src), _p(b["Ks"]), _p(gt), _p(mask),
                                    _p(b["img_slots"])), "gs_step_inputs")
         if self.poses is not None:   # the view, its raw matrix into the record, the pose Adam's bias corrections at ITS step count
-            view, pose_t = pose if pose is not None else self._pose_cur
+            view, pose_t = e.pose
             nat.check(L.gs_pose_step_inputs(self._st(), int(view), int(self.poses.deltas.shape[0]), _p(vm_src), None, self.pose_lr,
                                             self.pose_betas[0], self.pose_betas[1], int(pose_t), _p(b["pose_rec"])), "gs_pose_step_inputs")
         if self.exposure is not None:   # the view and the exposure Adam's bias corrections at ITS step count and the step's own rate
-            view, exp_t, exp_lr = exposure if exposure is not None else self._exposure_cur
+            view, exp_t, exp_lr = e.exposure
             nat.check(L.gs_exposure_step_inputs(self._st(), int(view), int(self.exposure.affine.shape[0]), float(exp_lr), self.exposure_betas[0],
                                                 self.exposure_betas[1], int(exp_t), _p(b["exposure_rec"])), "gs_exposure_step_inputs")
         if self.bilagrid is not None:   # the view and the grids' Adam's bias corrections at ITS step count and the step's own rate
-            view, bg_t, bg_lr = bilagrid if bilagrid is not None else self._bilagrid_cur
+            view, bg_t, bg_lr = e.bilagrid
             nat.check(L.gs_bilagrid_step_inputs(self._st(), int(view), int(self.bilagrid.grids.shape[0]), float(bg_lr), self.bilagrid_betas[0],
                                                 self.bilagrid_betas[1], int(bg_t), _p(b["bilagrid_rec"])), "gs_bilagrid_step_inputs")
         if self.depth is not None:   # the step's depth target (its address: read in place) and the weight as it stood at the call
-            gd, lam = depth if depth is not None else self._depth_cur
+            gd, lam = e.depth
             nat.check(L.gs_depth_step_inputs(self._st(), float(lam), self._depth_mode, _p(gd), _p(b["depth_rec"])), "gs_depth_step_inputs")
         if self.mcmc is not None:   # the step's noise: its strength at the means learning rate this step's Adam uses, its counter, the seed
             nat.check(L.gs_mcmc_step_inputs(self._st(), self.mcmc.noise_lr * float(lrs[self._means_seg]), int(t), self.mcmc.seed,
                                             _p(b["mcmc_rec"])), "gs_mcmc_step_inputs")
-        self._cur_images = (gt, mask)
-        return gt, mask
+        self._staged = e
 
     def _st(self) -> int:
         return torch.cuda.current_stream(self.dev).cuda_stream
@@ -849,8 +874,8 @@ class TrainStepGraph:
         def __len__(self):
             return len(self._items)
 
-    stop_after = int(__import__('os').environ.get('GS_TG_STOP_AFTER', '0'))
-    project_rebuilds = __import__('os').environ.get('GS_TG_PROJECT_REBUILDS', '1') != '0'   # 0: every re-build probes and warms up
+    stop_after = int(os.environ.get('GS_TG_STOP_AFTER', '0'))
+    project_rebuilds = os.environ.get('GS_TG_PROJECT_REBUILDS', '1') != '0'   # 0: every re-build probes and warms up
     debug_sync = False   # set True to synchronise after every stage (locates a faulting kernel; never under capture)
 
     class _Stop(Exception):
@@ -1047,63 +1072,38 @@ class TrainStepGraph:
                                              FAR_PLANE, _p(b["radii"]), _p(b["colors_post"]), 1, _p(b["sh_jac"]), _p(b["pose_row_sums"]),
                                              _p(b["cam_partials"]), _p(b["v_viewmats"]), _p(b["v_campos"])), "gs_cam_grad_sums")
             offs = (ct.c_int64 * 6)(*opt._offs)
-            head = (st, N, self.K, int(m.active_sh_degree), _p(opt.flat_param), _p(opt.exp_avg),
-                    _p(opt.exp_avg_sq), offs, _p(b["viewmats"]), _p(b["Ks"]), W, H, EPS2D, NEAR_PLANE, FAR_PLANE,
-                    _p(b["radii"]), _p(b["colors_post"]), self._tpg(), _p(b["cum_tiles"]))
-            tail = (_p(b["v_abs"]), float(b1), float(b2),
-                    float(opt.defaults["eps"]), _p(b["hyper"]), _p(b["applied"]), _p(m.max_radii),
-                    _p(m.grad_norm_accum), _p(m.collecting_counts), _p(b["sh_jac"]))
-            args = head + (_p(b["rows"]), _p(b["row_base"]), _p(b["qmask"])) + tail
+            # what every row-walking entry takes, once -- a plain tuple literal: tests/test_native_header.py counts the calls below against
+            # the header with it; [19:22]: the gradient rows, in whose place gs_project_bwd_adam_sums takes the sums
+            row_args = (st, N, self.K, int(m.active_sh_degree), _p(opt.flat_param), _p(opt.exp_avg), _p(opt.exp_avg_sq), offs,
+                        _p(b["viewmats"]), _p(b["Ks"]), W, H, EPS2D, NEAR_PLANE, FAR_PLANE, _p(b["radii"]), _p(b["colors_post"]),
+                        self._tpg(), _p(b["cum_tiles"]), _p(b["rows"]), _p(b["row_base"]), _p(b["qmask"]), _p(b["v_abs"]), float(b1),
+                        float(b2), float(opt.defaults["eps"]), _p(b["hyper"]), _p(b["applied"]), _p(m.max_radii),
+                        _p(m.grad_norm_accum), _p(m.collecting_counts), _p(b["sh_jac"]))
+            reg_on, ratio, lam = (1, self.max_scale_ratio, self.lambda_scale) if self.scale_reg else (0, 0.0, 0.0)
+            mcmc_on, (bud_a, bud_b) = int(self.mcmc is not None), self.mcmc_reg if self.mcmc is not None else (0.0, 0.0)
             if self.depth is not None:
                 # v_z per Gaussian from lane 3 of its gradient rows (gs_depth_grads' gather), then the fused kernel adds v_z times row 2
                 # of the view matrix to the means gradient where gs_depth_grads would: the same update bit for bit
                 self._ck(L.gs_depth_grads_z(st, 1, N, 3, _p(b["radii"]), self._tpg(), _p(b["cum_tiles"]), _p(b["rows"]), _p(b["row_base"]),
                                              _p(b["qmask"]), _p(b["v_depths"])), "gs_depth_grads_z")
-                bud_a, bud_b = self.mcmc_reg if self.mcmc is not None else (0.0, 0.0)
-                self._ck(L.gs_project_bwd_adam_depth(st, N, self.K, int(m.active_sh_degree), _p(opt.flat_param), _p(opt.exp_avg),
-                                                      _p(opt.exp_avg_sq), offs, _p(b["viewmats"]), _p(b["Ks"]), W, H, EPS2D, NEAR_PLANE,
-                                                      FAR_PLANE, _p(b["radii"]), _p(b["colors_post"]), self._tpg(), _p(b["cum_tiles"]),
-                                                      _p(b["rows"]), _p(b["row_base"]), _p(b["qmask"]), _p(b["v_abs"]), float(b1), float(b2),
-                                                      float(opt.defaults["eps"]), _p(b["hyper"]), _p(b["applied"]), _p(m.max_radii),
-                                                      _p(m.grad_norm_accum), _p(m.collecting_counts), _p(b["sh_jac"]), int(self.scale_reg),
-                                                      self.max_scale_ratio if self.scale_reg else 0.0,
-                                                      self.lambda_scale if self.scale_reg else 0.0, int(self.mcmc is not None), bud_a, bud_b,
-                                                      _p(b["v_depths"])), "gs_project_bwd_adam_depth")
+                self._ck(L.gs_project_bwd_adam_depth(*row_args, reg_on, ratio, lam, mcmc_on, bud_a, bud_b, _p(b["v_depths"])), "gs_project_bwd_adam_depth")
             elif poses:   # (the sums in place of rows, row_base, qmask; one entry for the three variants)
-                self._ck(L.gs_project_bwd_adam_sums(*head, _p(b["pose_row_sums"]), *tail, int(self.scale_reg),
-                                                     self.max_scale_ratio if self.scale_reg else 0.0, self.lambda_scale if self.scale_reg else 0.0,
-                                                     int(self.mcmc is not None), *(self.mcmc_reg if self.mcmc is not None else (0.0, 0.0))),
+                self._ck(L.gs_project_bwd_adam_sums(*row_args[:19], _p(b["pose_row_sums"]), *row_args[22:], reg_on, ratio, lam, mcmc_on, bud_a, bud_b),
                          "gs_project_bwd_adam_sums")
             elif self.mcmc is not None:
-                self._ck(L.gs_project_bwd_adam_mcmc(*args, int(self.scale_reg), self.max_scale_ratio if self.scale_reg else 0.0,
-                                                     self.lambda_scale if self.scale_reg else 0.0, *self.mcmc_reg), "gs_project_bwd_adam_mcmc")
-            elif self.camera_model != nat.GS_CAMERA_PINHOLE:   # (no depth, poses or mcmc here: refused at construction)
-                # (`args`, spelt out: a tuple literal, so that tests/test_native_header.py can count these two calls against the header)
-                cm_args = (st, N, self.K, int(m.active_sh_degree), _p(opt.flat_param), _p(opt.exp_avg), _p(opt.exp_avg_sq), offs,
-                           _p(b["viewmats"]), _p(b["Ks"]), W, H, EPS2D, NEAR_PLANE, FAR_PLANE, _p(b["radii"]), _p(b["colors_post"]),
-                           self._tpg(), _p(b["cum_tiles"]), _p(b["rows"]), _p(b["row_base"]), _p(b["qmask"]), _p(b["v_abs"]), float(b1),
-                           float(b2), float(opt.defaults["eps"]), _p(b["hyper"]), _p(b["applied"]), _p(m.max_radii),
-                           _p(m.grad_norm_accum), _p(m.collecting_counts), _p(b["sh_jac"]))
-                if self.scale_reg:
-                    self._ck(L.gs_project_bwd_adam_reg_cm(*cm_args, self.max_scale_ratio, self.lambda_scale, self.camera_model),
-                             "gs_project_bwd_adam_reg_cm")
-                else:
-                    self._ck(L.gs_project_bwd_adam_cm(*cm_args, self.camera_model), "gs_project_bwd_adam_cm")
-            elif self.antialiased:   # (no depth, poses, mcmc or other camera model here: refused at construction)
-                # (`args`, spelt out as for the camera models: tests/test_native_header.py counts these two calls against the header)
-                aa_args = (st, N, self.K, int(m.active_sh_degree), _p(opt.flat_param), _p(opt.exp_avg), _p(opt.exp_avg_sq), offs,
-                           _p(b["viewmats"]), _p(b["Ks"]), W, H, EPS2D, NEAR_PLANE, FAR_PLANE, _p(b["radii"]), _p(b["colors_post"]),
-                           self._tpg(), _p(b["cum_tiles"]), _p(b["rows"]), _p(b["row_base"]), _p(b["qmask"]), _p(b["v_abs"]), float(b1),
-                           float(b2), float(opt.defaults["eps"]), _p(b["hyper"]), _p(b["applied"]), _p(m.max_radii),
-                           _p(m.grad_norm_accum), _p(m.collecting_counts), _p(b["sh_jac"]))
-                if self.scale_reg:
-                    self._ck(L.gs_project_bwd_adam_reg_aa(*aa_args, self.max_scale_ratio, self.lambda_scale), "gs_project_bwd_adam_reg_aa")
-                else:
-                    self._ck(L.gs_project_bwd_adam_aa(*aa_args), "gs_project_bwd_adam_aa")
+                self._ck(L.gs_project_bwd_adam_mcmc(*row_args, reg_on, ratio, lam, bud_a, bud_b), "gs_project_bwd_adam_mcmc")
+            elif self.camera_model != nat.GS_CAMERA_PINHOLE and self.scale_reg:   # (no depth, poses or mcmc here: refused at construction)
+                self._ck(L.gs_project_bwd_adam_reg_cm(*row_args, ratio, lam, self.camera_model), "gs_project_bwd_adam_reg_cm")
+            elif self.camera_model != nat.GS_CAMERA_PINHOLE:
+                self._ck(L.gs_project_bwd_adam_cm(*row_args, self.camera_model), "gs_project_bwd_adam_cm")
+            elif self.antialiased and self.scale_reg:   # (no depth, poses, mcmc or other camera model here: refused at construction)
+                self._ck(L.gs_project_bwd_adam_reg_aa(*row_args, ratio, lam), "gs_project_bwd_adam_reg_aa")
+            elif self.antialiased:
+                self._ck(L.gs_project_bwd_adam_aa(*row_args), "gs_project_bwd_adam_aa")
             elif self.scale_reg:
-                self._ck(L.gs_project_bwd_adam_reg(*args, self.max_scale_ratio, self.lambda_scale), "gs_project_bwd_adam_reg")
+                self._ck(L.gs_project_bwd_adam_reg(*row_args, ratio, lam), "gs_project_bwd_adam_reg")
             else:
-                self._ck(L.gs_project_bwd_adam(*args), "gs_project_bwd_adam")
+                self._ck(L.gs_project_bwd_adam(*row_args), "gs_project_bwd_adam")
         else:
             g = self.grads
             bwd_args = (st, 1, N, self.K, int(m.active_sh_degree), _p(m.means), _p(m.quats), _p(m.log_scales),
@@ -1213,13 +1213,10 @@ class TrainStepGraph:
             if warm_up:
                 self._warm.add((self.binning, self.cap_tile))
                 saved = [opt.flat_param.clone(), opt.exp_avg.clone(), opt.exp_avg_sq.clone()] + [getattr(m, n).clone() for n in names]
-                pose_live = (self.poses.deltas.data, self.pose_state.exp_avg, self.pose_state.exp_avg_sq) if self.poses is not None else ()
-                if self.exposure is not None:   # (the table and its moments are throw-away state of the warm-up step like the deltas)
-                    pose_live += (self.exposure.affine.data, self.exposure_state.exp_avg, self.exposure_state.exp_avg_sq)
-                if self.bilagrid is not None:
-                    pose_live += (self.bilagrid.grids.data, self.bilagrid_state.exp_avg, self.bilagrid_state.exp_avg_sq)
+                # (the per-view tables and their moments are throw-away state of the warm-up step like the model's)
+                pose_live = [x for _, _, table, state in self._tables for x in (table.data, state.exp_avg, state.exp_avg_sq)]
                 pose_saved = [x.clone() for x in pose_live]
-                self._hyper(max(opt._step, 0) + 1, [float(grp["lr"]) for grp, _ in opt._plist])
+                self._hyper(max(opt._step, 0) + 1, self._lrs())
                 self._enqueue_step()
                 self.stream.synchronize()
                 info = self.buf["info"].tolist()
@@ -1246,16 +1243,7 @@ class TrainStepGraph:
         self.confirmed_at_build = self.confirmed
 
     # ------------------------------------------------------------------------------------------ stepping
-    _ENTRY_DEPTH = 13   # where a pending entry keeps (depth target, lambda_depth): behind pose [10], exposure [11], bilagrid [12]
-
-    def _issue(self, entry):
-        t, lrs, w2c, K, gt, mask, ready = entry[:7]
-        conv = entry[7] if len(entry) > 7 else None
-        after = entry[8] if len(entry) > 8 else None
-        pose = entry[10] if len(entry) > 10 else None   # (view index, pose step count): poses
-        expo = entry[11] if len(entry) > 11 else None   # (view index, exposure step count, learning rate): exposure
-        bgrid = entry[12] if len(entry) > 12 else None  # (view index, the grids' step count, learning rate): bilagrid
-        dep = entry[self._ENTRY_DEPTH] if len(entry) > self._ENTRY_DEPTH else None   # (target, lambda_depth): depth
+    def _issue(self, entry: _Pending):
         # The step waits for the caller's stream on entry: that orders it behind pending WRITERS of the inputs handed in and
         # behind pending READERS of what the replay overwrites -- the static outputs the previous `step()` returned, the
         # parameters and moments (fused Adam), the statistics.  (Round 3 skipped the wait for steps that take no input from
@@ -1263,22 +1251,23 @@ class TrainStepGraph:
         # then run concurrently with replay i+1: ADVICE r3.)  Only `inputs_ready=True` -- the caller's promise that its
         # stream holds neither -- skips it.  The wait is free when the caller's stream is idle, i.e. with handback="lazy" in a
         # loop that reads nothing between steps; behind an eager hand-back it costs two cross-queue signal hops.
-        with torch.cuda.device(self.dev), self._on_stream(wait_outer=not ready, hand_back=self.handback == "eager"):
-            if conv is not None:
+        with torch.cuda.device(self.dev), self._on_stream(wait_outer=not entry.inputs_ready, hand_back=self.handback == "eager"):
+            if entry.conv is not None:
                 # the runner's OWN conversion / copy of a target was enqueued on the caller's stream (`step`): the promise
                 # `inputs_ready=True` covers the caller's writers, not this one
-                self.stream.wait_event(conv)
-                entry[7] = None
+                self.stream.wait_event(entry.conv)
+                entry.conv = None
+            after = entry.ready_event
             if after is not None:   # (`step(ready_event=...)`: the upload of this step's inputs on the caller's copy stream(s))
                 for ev in (after if isinstance(after, (list, tuple)) else (after,)):
                     self.stream.wait_event(ev)
-                entry[8] = None
-            entry[4], entry[5] = self._stage_inputs(t, lrs, w2c, K, gt, mask, pose, expo, bgrid, dep)   # (the tensors the step reads: kept by the entry)
+                entry.ready_event = None
+            self._stage_inputs(entry)   # (the tensors the step reads: kept by the entry)
             if self.graph is not None:
                 self.graph.replay()
             else:
                 self._enqueue_step()
-            self._tail(t, lrs)   # (ViewParallelGraphStep: the collectives and what applies the step; nothing here)
+            self._tail(entry.t, entry.lrs)   # (ViewParallelGraphStep: the collectives and what applies the step; nothing here)
         self.pending.append(entry)
         self.issued += 1
 
@@ -1304,14 +1293,14 @@ class TrainStepGraph:
         previous step's raw matrix); with `exposure`, required -- the row of `exposure.affine` of this step's target image.
         `gt_depth`: with `depth`, this step's depth target [H, W] (default: the previous step's; `gt_img`'s lifetime rules)."""
         _refuse_camera_grads(data)
-        depth_on = getattr(self, "depth", None) is not None
+        depth_on = self.depth is not None
         if gt_depth is not None and not depth_on:
             raise ValueError("TrainStepGraph.step: gt_depth given, but the runner was built without `depth`")
-        exposure, bilagrid = getattr(self, "exposure", None), getattr(self, "bilagrid", None)
-        view = _pose_view(self.poses, view_index, exposure, bilagrid)
+        view = _pose_view(self.poses, view_index, self.exposure, self.bilagrid)
         W, H = (self.W, self.H) if data is None else (int(data["width"]), int(data["height"]))
         if self._state_key(W, H) != self._key:
             self.finish()
+            prev, dep = self._staged, self._staged.depth
             size_changed = (W, H) != (self.W, self.H)
             if size_changed:
                 # another frame size: the static image buffers are re-allocated, so the frame must bring its own target
@@ -1319,11 +1308,11 @@ class TrainStepGraph:
                     raise ValueError("TrainStepGraph.step: a change of image size needs gt_img (and mask, and gt_depth) of the new size")
                 cur = (data["w2c"], data["K"], gt_img, mask)
                 if depth_on:   # (validated against the new size before anything is re-built)
-                    self._depth_cur = (self._depth_image(gt_depth, (H, W)), float(self.lambda_depth))
+                    dep = (self._depth_image(gt_depth, (H, W)), float(self.lambda_depth))
                 self.W, self.H = W, H
             else:
-                cur = self._last_inputs if data is None else (data["w2c"], data["K"], gt_img if gt_img is not None else self._last_inputs[2],
-                                                              mask if mask is not None else self._last_inputs[3])
+                cur = (prev.w2c, prev.K, prev.gt, prev.mask) if data is None else (data["w2c"], data["K"], gt_img if gt_img is not None else prev.gt,
+                                                                                   mask if mask is not None else prev.mask)
                 # (old static buffers named here stay alive through `cur` until the new ones have been filled from them)
             # the largest list the status words showed since the last build, scaled to the new model size: a refinement
             # re-captures on whichever view comes next, and a capacity learnt from that one view alone overflows on the first
@@ -1357,16 +1346,17 @@ class TrainStepGraph:
                     carried, projected = projected, None
             self.seen_isects = self.seen_tile = self.seen_units = self.seen_rows = 0
             self.cap = self.cap_units = self.cap_rows = 0
+            # (the tables' views, step counts and rates: the previous step's, as a re-build has always staged them)
+            staged = self._next_step(*cur, pose=prev.pose, exposure=prev.exposure, bilagrid=prev.bilagrid, depth=dep)
             if projected is None and carried is not None:
-                self._build({"w2c": cur[0], "K": cur[1]}, cur[2], cur[3] if self.has_mask else None, min_cap=carried[0], min_cap_tile=carried[1],
-                            min_walk=carried[2:4])
+                self._build(staged, min_cap=carried[0], min_cap_tile=carried[1], min_walk=carried[2:4])
             else:
-                self._build({"w2c": cur[0], "K": cur[1]}, cur[2], cur[3] if self.has_mask else None, projected=projected)
+                self._build(staged, projected=projected)
         b = self.buf
         w2c = self._static_w2c()[0] if data is None else data["w2c"]
         K = b["Ks"][0] if data is None else data["K"]
-        gt = self._last_inputs[2] if gt_img is None else gt_img   # (the previous step's own tensors, by reference)
-        mk = (self._last_inputs[3] if mask is None else mask) if self.has_mask else None
+        gt = self._staged.gt if gt_img is None else gt_img   # (the previous step's own tensors, by reference)
+        mk = (self._staged.mask if mask is None else mask) if self.has_mask else None
         gt_in, mk_in = gt, mk
         gt = self._image(gt, (self.H, self.W, 3))   # (validated / converted BEFORE the step is counted)
         if self.has_mask:
@@ -1378,7 +1368,7 @@ class TrainStepGraph:
             mk = (mk.clone() if mk is mk_in else mk) if mk is not None else None
         gd = gd_in = None
         if depth_on:
-            gd_in = self._depth_cur[0] if gt_depth is None else gt_depth   # (the previous step's own tensor, by reference)
+            gd_in = self._staged.depth[0] if gt_depth is None else gt_depth   # (the previous step's own tensor, by reference)
             gd = self._depth_image(gd_in, (self.H, self.W))
             if self.copy_targets and gt_depth is not None and gd is gd_in:
                 gd = gd.clone()
@@ -1388,7 +1378,6 @@ class TrainStepGraph:
             # waits for exactly that, whatever `inputs_ready` promises about the caller's own work
             conv = torch.cuda.Event()
             conv.record(torch.cuda.current_stream(self.dev))
-        self._last_inputs = (w2c, K, gt, mk)
         opt = self.opt
         opt._step += 1
         # The queued entry is what an overflow recovery replays.  Inputs are kept by reference: a caller must not write
@@ -1396,24 +1385,20 @@ class TrainStepGraph:
         # target and the mask are not even copied: the step reads them where they lie (`_stage_inputs`).  Entries that alias the
         # runner's OWN static camera buffers (data=None steps) are snapshotted right before a later step overwrites those
         # buffers (`_protect_pending`), so a skipped step is always replayed with its own inputs.
-        entry = [opt._step, [float(grp["lr"]) for grp, _ in opt._plist], w2c, K, gt, mk, bool(inputs_ready), conv, ready_event, host_src]
-        if view is not None:   # the view and the pose step count travel with the step, like t and the learning rates: a replay re-stages them
-            if self.poses is not None:
-                self.pose_state.step += 1
-                self._pose_cur = (view, self.pose_state.step)
-            entry.append(self._pose_cur if self.poses is not None else None)
-            if exposure is not None:   # ... and so do the exposure step count and the rate as it stands at this call
-                self.exposure_state.step += 1
-                self._exposure_cur = (view, self.exposure_state.step, float(self.exposure_lr))
-                entry.append(self._exposure_cur)
-            if bilagrid is not None:   # (entry[12]; entry[11] stays the exposure's place)
-                self.bilagrid_state.step += 1
-                self._bilagrid_cur = (view, self.bilagrid_state.step, float(self.bilagrid_lr))
-                entry.extend([None, self._bilagrid_cur])
-        if depth_on:   # the target and the weight as it stands at this call travel with the step: entry[13]
-            self._depth_cur = (gd, float(self.lambda_depth))
-            assert len(entry) <= self._ENTRY_DEPTH, len(entry)   # (a later optional slot goes behind this one, never in front)
-            entry.extend([None] * (self._ENTRY_DEPTH - len(entry)) + [self._depth_cur])
+        entry = _Pending(opt._step, self._lrs(), w2c, K, gt, mk, bool(inputs_ready), conv, ready_event, host_src)
+        # the view and each table's step count travel with the step, like t and the learning rates: a replay re-stages them -- and so do
+        # the rates of the exposure and the grids, and the depth target with its weight, as they stand at this call
+        if self.poses is not None:
+            self.pose_state.step += 1
+            entry.pose = (view, self.pose_state.step)
+        if self.exposure is not None:
+            self.exposure_state.step += 1
+            entry.exposure = (view, self.exposure_state.step, float(self.exposure_lr))
+        if self.bilagrid is not None:
+            self.bilagrid_state.step += 1
+            entry.bilagrid = (view, self.bilagrid_state.step, float(self.bilagrid_lr))
+        if depth_on:
+            entry.depth = (gd, float(self.lambda_depth))
         self._issue(entry)
         if self.issued % self.check_every == 0:
             self._poll(block=False)
@@ -1425,10 +1410,10 @@ class TrainStepGraph:
         if self.poses is not None:
             outs["viewmat"] = b["viewmats"][0]    # the corrected matrix the step rendered with
             outs["v_delta"] = b["v_delta"]        # dL / d poses.deltas[view_index] of the step (unchanged by a step the guard skipped)
-        if exposure is not None:
+        if self.exposure is not None:
             outs["exposed"] = b["exposed"]        # the image the loss read: the view's affine of render_img
             outs["v_affine"] = b["v_affine"]      # dL / d exposure.affine[view_index], 12 floats row-major [3][4]
-        if bilagrid is not None:
+        if self.bilagrid is not None:
             outs["exposed"] = b["exposed"]          # the image the loss read: the slice of the view's grid applied to render_img
             outs["v_grids"] = b["v_grids"]          # dL / d bilagrid.grids of the step, dense: the view's slab + the TV gradient
             outs["bilagrid_tv"] = b["bilagrid_tv"]  # the total variation of all grids (the loss total holds bilagrid_tv times it)
@@ -1476,22 +1461,14 @@ class TrainStepGraph:
             "step": self.confirmed + 1, "flags": int(self.status[nat.GS_INFO_FLAGS]), "isects": n_isects, "longest_list": max_tile, "work_units": walk[0], "rows": walk[1],
             "capacities": [self.cap, self.cap_tile, self.cap_units, self.cap_rows]})
         for e in redo:   # steps fed from recycled device slots (HostFeed): upload their own inputs again
-            src = e[9] if len(e) > 9 else None
+            src = e.host_src
             if src is not None:
-                e[2], e[3] = src["w2c"].to(self.dev, torch.float32), src["K"].to(self.dev, torch.float32)
-                e[4] = HostFeed.to_target(src["image"], self.dev)
-                e[5] = src["mask"].to(self.dev, torch.float32) if (self.has_mask and src.get("mask") is not None) else e[5]
-        first = redo[0]
-        if self.poses is not None:
-            self._pose_cur = first[10]   # (the probe of the re-build runs on the first skipped step's own view)
-        if self.exposure is not None:
-            self._exposure_cur = first[11]
-        if self.bilagrid is not None:
-            self._bilagrid_cur = first[12]
-        if self.depth is not None:
-            self._depth_cur = first[self._ENTRY_DEPTH]   # (the probe and the warm-up of the re-build read the first skipped step's own target)
+                e.w2c, e.K = src["w2c"].to(self.dev, torch.float32), src["K"].to(self.dev, torch.float32)
+                e.gt = HostFeed.to_target(src["image"], self.dev)
+                e.mask = src["mask"].to(self.dev, torch.float32) if (self.has_mask and src.get("mask") is not None) else e.mask
+        # the probe and the warm-up of the re-build run on the first skipped step's own record: its camera and view, its targets
         # (min_cap >= 1 forces a fresh probe even when only a coarse-bin capacity was exceeded and the list sizes read 0)
-        self._build({"w2c": first[2], "K": first[3]}, first[4], first[5], min_cap=max(n_isects, 1), min_cap_tile=max_tile, min_walk=walk)
+        self._build(redo[0], min_cap=max(n_isects, 1), min_cap_tile=max_tile, min_walk=walk)
         for e in redo:
             self._issue(e)
 
@@ -1515,12 +1492,10 @@ class TrainStepGraph:
         extra = dict(scale_reg=True, max_scale_ratio=self.max_scale_ratio, lambda_scale=self.lambda_scale) if self.scale_reg else {}
         if self.mcmc is not None:
             extra.update(mcmc=True, mcmc_reg=self.mcmc_reg, mcmc_seed=self.mcmc.seed, mcmc_noise_lr=self.mcmc.noise_lr)
-        if self.poses is not None:   # (like the two above: a runner without the feature reports what it always reported)
-            extra.update(poses=True, pose_lr=self.pose_lr, pose_steps=self.pose_state.step)
-        if self.exposure is not None:
-            extra.update(exposure=True, exposure_lr=self.exposure_lr, exposure_steps=self.exposure_state.step)
+        for option, prefix, _, state in self._tables:   # (like the two above: a runner without the feature reports what it always reported)
+            extra.update({option: True, prefix + "_lr": getattr(self, prefix + "_lr"), prefix + "_steps": state.step})
         if self.bilagrid is not None:
-            extra.update(bilagrid=True, bilagrid_lr=self.bilagrid_lr, bilagrid_tv=self.bilagrid_tv, bilagrid_steps=self.bilagrid_state.step)
+            extra.update(bilagrid_tv=self.bilagrid_tv)
         if self.depth is not None:
             extra.update(depth=True, lambda_depth=self.lambda_depth, depth_mode=self.depth.mode)
         return dict(self.stats, **extra, binning=self.binning, probed_isects=self.probed[0], probed_longest_list=self.probed[1],
@@ -1677,7 +1652,7 @@ class HostFeed:
     def __init__(self, runner: "TrainStepGraph", n_slots: int = 2, inputs_ready: bool = False):
         """`inputs_ready`: the caller's promise of `TrainStepGraph.step` (its stream holds no pending reader of the outputs, the
         parameters or the statistics) -- the uploads themselves are ordered by events either way."""
-        if getattr(runner, "depth", None) is not None:
+        if runner.depth is not None:
             raise NotImplementedError("HostFeed: a runner built with `depth` -- the feed uploads image, mask and camera, not a depth "
                                       "target; hand device depth maps to runner.step(..., gt_depth=...)")
         self.r, self.n = runner, max(2, int(n_slots))
@@ -1727,7 +1702,7 @@ class HostFeed:
                 self.mask[j].copy_(batch["mask"], non_blocking=True)
             ev = torch.cuda.Event()
             ev.record(cs)
-        per_view = any(getattr(r, what, None) is not None for what in ("poses", "exposure", "bilagrid"))
+        per_view = r.poses is not None or r.exposure is not None or r.bilagrid is not None
         view = batch.get("view_index") if per_view else None   # (poses / exposure / bilagrid: the batch names its row of the tables)
         out = r.step({"w2c": self.w2c[j], "K": self.K[j], "width": r.W, "height": r.H}, self.gt[j], self.mask[j] if r.has_mask else None,
                      inputs_ready=self.inputs_ready, ready_event=ev, host_src=batch, view_index=view)

@@ -18,6 +18,7 @@ from easy_gaussian_splatting_amd.exposure import ExposureTable
 from easy_gaussian_splatting_amd.loss import LossComputer
 from easy_gaussian_splatting_amd.pose import CameraDeltas
 from easy_gaussian_splatting_amd.train_graph import HostFeed, TrainStepGraph
+from test_gpu_pose_step import _assert_same_poses
 from test_gpu_train_graph import _assert_same, _setup
 
 pytestmark = pytest.mark.gpu
@@ -248,7 +249,9 @@ def test_the_update_is_dense_adam_on_all_rows():
 
 
 # 5. the guard covers the table
-def test_overflow_voids_the_exposure_update_and_the_replay_applies_it_once():
+@pytest.mark.parametrize("with_poses", [False, True])
+def test_overflow_voids_the_exposure_update_and_the_replay_applies_it_once(with_poses):
+    """with_poses: a replayed step re-stages two tables' (view, step count, rate) from its one queued record."""
     dev, make, datas, gts = _setup(n=30000, n_views=3, dist=4.0)
     far = dict(datas[0])
     w2c = far["w2c"].clone()
@@ -259,8 +262,9 @@ def test_overflow_voids_the_exposure_update_and_the_replay_applies_it_once():
     done = []
     for (first, view), margin in (((far, 0), 1.02), ((datas[1], 1), 4.0)):
         m, o = make()
+        kw = dict(poses=CameraDeltas(N_VIEWS).to(dev), pose_lr=1e-3) if with_poses else {}
         r = TrainStepGraph(m, o, lc, {**first, "view_index": view}, gts[0], margin=margin, check_every=4, exposure=_table(dev, seed=5),
-                           exposure_lr=EXP_LR)
+                           exposure_lr=EXP_LR, **kw)
         for it, (d, v) in enumerate(seq):   # no finish() in between: the host keeps enqueueing behind the overflow
             r.exposure_lr = EXP_LR * 0.8 ** it   # a schedule: every pending step keeps the rate it was issued with
             r.step(d, gts[it % 3], view_index=v)
@@ -273,6 +277,9 @@ def test_overflow_voids_the_exposure_update_and_the_replay_applies_it_once():
     assert ra.report()["overflows"] == 0 and ra.report()["steps"] == len(seq)
     _assert_same(mt, ot, ma, oa, "replayed != never overflowed")
     _assert_same_exposure(rt, ra, "replayed != never overflowed")
+    if with_poses:
+        assert rt.pose_state.step == len(seq) and rt.poses.deltas.detach().abs().max() > 0   # (the pose table did move)
+        _assert_same_poses(rt, ra, "replayed != never overflowed")
 
 
 # 6. combinations

@@ -504,7 +504,7 @@ def test_targets_are_read_in_place_through_pointer_slots():
     for v, gt in seq:
         _eager_step(ma, oa, lc, datas[v], gt.to(dev, torch.float32).contiguous(), mask)
         runner.step(datas[v], gt, mask)
-        staged = runner._cur_images[0]
+        staged = runner._staged.gt
         if gt.device == dev and gt.dtype == torch.float32 and gt.is_contiguous():
             assert staged.data_ptr() == gt.data_ptr()                   # read where it lies
         assert int(runner.buf["img_slots"][0]) == staged.data_ptr() and int(runner.buf["img_slots"][1]) == mask.data_ptr()

@@ -162,7 +162,7 @@ def test_every_python_call_site_passes_the_headers_parameter_count():
     """ctypes checks the count of a call against argtypes only when the call runs, and most of these calls run only on a GPU:
     count the positional arguments of every `<lib>.gs_*(...)` call in the package, the tests, the tools and bench.py against the
     header.  A call with a starred argument cannot be counted as it stands; where the starred name is a tuple literal of the same
-    file (the package's `args` / `bwd_args()`) its length is added, otherwise the call is left out -- and only a few may be."""
+    file (the package's `args` / `row_args` / `bwd_args()`) its length is added, otherwise the call is left out -- and only a few may be."""
     checked, left_out, wrong, starred_package = 0, [], [], 0
     for path in _python_sources():
         tree = ast.parse(open(path).read(), filename=path)
@@ -188,5 +188,9 @@ def test_every_python_call_site_passes_the_headers_parameter_count():
                 wrong.append(f"{where}: {name} called with {n} arguments, the header declares {len(nat.PARAMS[name])}: {', '.join(nat.PARAMS[name])}")
     print(f"call sites: {checked} checked, {len(left_out)} left out {left_out}; starred package calls resolved: {starred_package}")
     assert not wrong, "\n".join(wrong)
-    assert checked >= 200 and len(left_out) <= 10, (checked, left_out)
-    assert starred_package >= 4   # rendering.py: gs_project_bwd[_cam](*bwd_args(), ...); train_graph.py: gs_project_bwd_adam[_reg](*args, ...)
+    assert checked >= 200 and len(left_out) <= 7, (checked, left_out)
+    # train_graph.py leaves out one call: gs_project_bwd_adam_sums takes the tuple in two slices around the sums
+    assert sum(w.startswith("easy_gaussian_splatting_amd/train_graph.py") for w in left_out) <= 1, left_out
+    # rendering.py: gs_project_bwd[_cam | _aa | _cm](*bwd_args(), ...); train_graph.py: the same over `bwd_args`, gs_project_fwd[_aa | _cm](*args, ...)
+    # and every row-walking gs_project_bwd_adam* entry (*row_args, ...)
+    assert starred_package >= 20

@@ -166,3 +166,31 @@ def test_the_blend_and_the_captured_step_are_spelled_in_the_stage_functions_alon
     for name in ("gs_blend_fwd", "gs_blend_fwd_ch", "gs_blend_bwd", "gs_blend_bwd_ch"):
         assert named[name] == ["rendering.py"], (name, named[name])
     assert all(files.count("train_graph.py") == 0 for files in named.values()), named
+
+
+def test_protect_pending_snapshots_the_named_fields_that_alias_a_static_buffer():
+    """A queued step that was issued with "the camera the static buffer holds" keeps that camera when a later step overwrites the buffer:
+    `_protect_pending` gives every pending record whose `w2c`, `K`, `gt` or `mask` is the buffer (or its row) ONE shared snapshot, in the
+    shape the record had, and touches nothing else.  CPU tensors, a runner without its constructor."""
+    import torch
+    from easy_gaussian_splatting_amd import train_graph as TG
+    static = torch.arange(16, dtype=torch.float32).reshape(1, 4, 4)
+    old = static.clone()
+    own = {name: torch.full(shape, fill) for name, shape, fill in (("w2c", (4, 4), 7.0), ("K", (3, 3), 2.0), ("gt", (6, 8, 3), 0.5), ("mask", (6, 8), 1.0))}
+    whole = TG._Pending(1, [1e-3], static, own["K"], own["gt"], own["mask"])
+    row = TG._Pending(2, [1e-3], static[0], own["K"], own["gt"], None, pose=(1, 2))
+    apart = TG._Pending(3, [1e-3], own["w2c"], own["K"], own["gt"], own["mask"])
+    runner = object.__new__(TG.TrainStepGraph)
+    runner.pending = TG.deque([whole, row, apart])
+    runner._protect_pending(static)
+    static.fill_(-1.0)
+    assert whole.w2c.shape == (1, 4, 4) and row.w2c.shape == (4, 4)
+    assert torch.equal(whole.w2c, old) and torch.equal(row.w2c, old[0])
+    assert whole.w2c.data_ptr() == row.w2c.data_ptr() != static.data_ptr()   # one snapshot for both
+    assert apart.w2c is own["w2c"] and torch.equal(apart.w2c, torch.full((4, 4), 7.0))
+    for e in (whole, row, apart):   # what does not alias the buffer stays the caller's own tensor
+        assert e.K is own["K"] and e.gt is own["gt"] and e.mask is (None if e is row else own["mask"])
+    assert (whole.t, row.t, apart.t) == (1, 2, 3) and row.pose == (1, 2) and whole.pose is None
+    runner._protect_pending(own["K"])   # ... and so for a buffer that another field names: every record's K, nothing else
+    assert whole.K is row.K is apart.K and whole.K is not own["K"] and torch.equal(whole.K, own["K"])
+    assert apart.w2c is own["w2c"] and whole.gt is own["gt"]
