@@ -16,6 +16,7 @@
 // the view-parallel step uses that to update the SH segments and the geometry segments in two
 // launches of the same step (distributed.py).  `grad_scale` folds the 1/world of a mean over ranks in.
 #include "gs_common.h"
+#include "gs_visible_index.h"
 
 namespace gs {
 
@@ -85,22 +86,98 @@ __global__ __launch_bounds__(256) void adam_step_kernel(const AdamArgs a) {
     }
 }
 
+// The same step over the Gaussians a step SAW (gs_adam_step_visible; DESIGN.md "Updating only what a step saw"): every segment holds
+// n_rows Gaussians of width[s] floats, and a Gaussian whose radii entry is <= 0 keeps the bits of its parameters and of both moments
+// whatever its gradient holds.  A quad none of whose Gaussians is visible issues no load of g, p, m or v and no store; a mixed quad
+// loads as above and selects per element between the updated and the loaded value; the quad that reaches into a segment's pad is
+// walked element by element, so the pad is never written.  Same arithmetic (adam1) and bias corrections for the visible ones.
+struct VisibleAdamArgs {
+    AdamArgs a;
+    const int32_t* radii;         // [n_rows]
+    int64_t n_rows;
+    uint32_t width[kMaxSeg];      // floats per Gaussian of each segment
+};
+
+__device__ __forceinline__ void adam1_if(bool on, float& p, float g, float& m, float& v, float b1, float b2, float eps, float isbc2, float ss) {
+    float pn = p, mn = m, vn = v;
+    adam1(pn, g, mn, vn, b1, b2, eps, isbc2, ss);
+    p = on ? pn : p; m = on ? mn : m; v = on ? vn : v;
+}
+
+__global__ __launch_bounds__(256) void adam_step_visible_kernel(const VisibleAdamArgs va) {
+    const AdamArgs& a = va.a;
+    if (guard_tripped(a.guard)) return;
+    if (a.applied != nullptr && blockIdx.x == 0 && threadIdx.x == 0) a.applied[0] += 1;
+    const float isbc2 = a.hyper ? a.hyper[0] : a.inv_sqrt_bc2;
+    for (int64_t j = (int64_t)blockIdx.x * blockDim.x + threadIdx.x; j < a.n_act4; j += (int64_t)gridDim.x * blockDim.x) {
+        int s = 0;
+#pragma unroll
+        for (int k = 0; k < kMaxSeg - 1; ++k) s += (k < a.nseg - 1 && j >= a.act_end4[k]) ? 1 : 0;
+        const float* gp = a.g[s];
+        const int64_t q = j - (s > 0 ? a.act_end4[s - 1] : 0);   // quad inside the segment
+        const int64_t len = a.seg_len[s];
+        const int64_t e = q << 2;                                // element index inside the segment
+        if (gp == nullptr || e >= len) continue;                 // (a quad wholly behind the segment's end belongs to nobody)
+        const uint32_t w = va.width[s];
+        int64_t first, last;
+        uint32_t r;
+        const bool pad = quad_rows(q, w, va.n_rows, &first, &last, &r);
+        // who of the quad's (at most four) Gaussians is visible: two radii for w >= 3, one per element below that
+        bool on[4];
+        if (w >= 3) {
+            const bool vf = va.radii[first] > 0, vl = last != first ? va.radii[last] > 0 : vf;
+#pragma unroll
+            for (int i = 0; i < 4; ++i) on[i] = e + i < len && (quad_row_step(r, i, w) ? vl : vf);
+        } else {
+#pragma unroll
+            for (int i = 0; i < 4; ++i) {
+                const int64_t row = first + quad_row_step(r, i, w);
+                on[i] = row <= last && va.radii[row] > 0;
+            }
+        }
+        if (!(on[0] || on[1] || on[2] || on[3])) continue;       // nobody saw them: not loaded, not stored
+        const int64_t i4 = a.seg_begin4[s] + q;                  // quad inside the flat buffers
+        const float ss = a.hyper ? a.hyper[1 + s] : a.step_size[s];
+        if (pad) {   // the segment's last quad: its 1-3 real elements one by one, the pad behind them stays untouched
+            float* pp = reinterpret_cast<float*>(a.p + i4); float* mm = reinterpret_cast<float*>(a.m + i4); float* vv = reinterpret_cast<float*>(a.v + i4);
+            for (int i = 0; i < 3; ++i) {
+                if (!on[i]) continue;
+                float p = pp[i], m = mm[i], v = vv[i];
+                adam1(p, gp[e + i] * a.grad_scale, m, v, a.beta1, a.beta2, a.eps, isbc2, ss);
+                pp[i] = p; mm[i] = m; vv[i] = v;
+            }
+            continue;
+        }
+        float4 g = nt_load4(reinterpret_cast<const float4*>(gp + e));   // read once, then dead
+        g.x *= a.grad_scale; g.y *= a.grad_scale; g.z *= a.grad_scale; g.w *= a.grad_scale;
+        float4 p = a.p[i4], m = nt_load4(a.m + i4), v = nt_load4(a.v + i4);
+        adam1_if(on[0], p.x, g.x, m.x, v.x, a.beta1, a.beta2, a.eps, isbc2, ss);
+        adam1_if(on[1], p.y, g.y, m.y, v.y, a.beta1, a.beta2, a.eps, isbc2, ss);
+        adam1_if(on[2], p.z, g.z, m.z, v.z, a.beta1, a.beta2, a.eps, isbc2, ss);
+        adam1_if(on[3], p.w, g.w, m.w, v.w, a.beta1, a.beta2, a.eps, isbc2, ss);
+        a.p[i4] = p;   // re-read by the next forward
+        nt_store4(m, a.m + i4); nt_store4(v, a.v + i4);   // streamed once per step
+    }
+}
+
 }  // namespace gs
 
 using namespace gs;
 
-static int adam_launch(void* stream, int64_t n, float* params, float* exp_avg, float* exp_avg_sq,
-                       int n_segments, const int64_t* seg_ends_host, const int64_t* seg_lens_host,
-                       const float* const* seg_grads_host, const float* seg_lrs_host, float beta1,
-                       float beta2, float eps, int64_t step, float grad_scale, const float* hyper_dev, int64_t* applied_dev,
-                       int64_t stat_n = 0, const float* stat_src0 = nullptr, const float* stat_src1 = nullptr,
-                       float* stat_dst0 = nullptr, float* stat_dst1 = nullptr) {
+// Checks the arguments of a step and fills its argument block; *work = the quads and statistics the launch has to cover (0: nothing to
+// launch -- an empty buffer, or no segment with a gradient).
+static int adam_prepare(AdamArgs& a, int64_t* work_out, int64_t n, float* params, float* exp_avg, float* exp_avg_sq,
+                        int n_segments, const int64_t* seg_ends_host, const int64_t* seg_lens_host,
+                        const float* const* seg_grads_host, const float* seg_lrs_host, float beta1,
+                        float beta2, float eps, int64_t step, float grad_scale, const float* hyper_dev, int64_t* applied_dev,
+                        int64_t stat_n = 0, const float* stat_src0 = nullptr, const float* stat_src1 = nullptr,
+                        float* stat_dst0 = nullptr, float* stat_dst1 = nullptr) {
+    *work_out = 0;
     GS_REQUIRE(n >= 0 && (n & 3) == 0, "flat length must be a multiple of 4 (pad the buffers)");
     GS_REQUIRE(n_segments >= 1 && n_segments <= kMaxSeg, "1..8 segments");
     GS_REQUIRE(step >= 1, "step counts from 1");
     if (n == 0) return GS_OK;
     GS_REQUIRE(params && exp_avg && exp_avg_sq && seg_ends_host && seg_lens_host && seg_grads_host && seg_lrs_host, "null pointer");
-    AdamArgs a;
     a.hyper = hyper_dev; a.applied = applied_dev; a.guard = current_guard().info;
     a.n4 = n >> 2;
     a.p = reinterpret_cast<float4*>(params);
@@ -130,12 +207,55 @@ static int adam_launch(void* stream, int64_t n, float* params, float* exp_avg, f
     a.n_act4 = act;
     GS_REQUIRE(stat_n >= 0 && (stat_n == 0 || (stat_src0 && stat_src1 && stat_dst0 && stat_dst1)), "statistics: four pointers or none");
     a.stat_n = stat_n; a.stat_src[0] = stat_src0; a.stat_src[1] = stat_src1; a.stat_dst[0] = stat_dst0; a.stat_dst[1] = stat_dst1;
-    const int64_t work = a.n_act4 > stat_n ? a.n_act4 : stat_n;
-    if (work == 0) return GS_OK;
+    *work_out = a.n_act4 > stat_n ? a.n_act4 : stat_n;
+    return GS_OK;
+}
+
+static unsigned adam_grid(int64_t work) {
     const int64_t want = (work + 255) / 256;
-    const unsigned grid = (unsigned)(want < 256 * 16 ? want : 256 * 16);
-    hipLaunchKernelGGL(adam_step_kernel, dim3(grid), dim3(256), 0, (hipStream_t)stream, a);
+    return (unsigned)(want < 256 * 16 ? want : 256 * 16);
+}
+
+static int adam_launch(void* stream, int64_t n, float* params, float* exp_avg, float* exp_avg_sq,
+                       int n_segments, const int64_t* seg_ends_host, const int64_t* seg_lens_host,
+                       const float* const* seg_grads_host, const float* seg_lrs_host, float beta1,
+                       float beta2, float eps, int64_t step, float grad_scale, const float* hyper_dev, int64_t* applied_dev,
+                       int64_t stat_n = 0, const float* stat_src0 = nullptr, const float* stat_src1 = nullptr,
+                       float* stat_dst0 = nullptr, float* stat_dst1 = nullptr) {
+    AdamArgs a;
+    int64_t work;
+    if (int rc = adam_prepare(a, &work, n, params, exp_avg, exp_avg_sq, n_segments, seg_ends_host, seg_lens_host, seg_grads_host, seg_lrs_host,
+                              beta1, beta2, eps, step, grad_scale, hyper_dev, applied_dev, stat_n, stat_src0, stat_src1, stat_dst0, stat_dst1)) return rc;
+    if (work == 0) return GS_OK;
+    hipLaunchKernelGGL(adam_step_kernel, dim3(adam_grid(work)), dim3(256), 0, (hipStream_t)stream, a);
     GS_LAUNCH_CHECK("adam_step_kernel");
+    return GS_OK;
+}
+
+// gs_adam_step[_dev] over the visible Gaussians: the segments' widths and the step's radii on top of the dense arguments
+static int adam_visible_launch(void* stream, int64_t n, float* params, float* exp_avg, float* exp_avg_sq,
+                               int n_segments, const int64_t* seg_ends_host, const int64_t* seg_lens_host,
+                               const float* const* seg_grads_host, const float* seg_lrs_host, float beta1,
+                               float beta2, float eps, int64_t step, float grad_scale, const float* hyper_dev, int64_t* applied_dev,
+                               int64_t n_rows, const int64_t* seg_widths_host, const int32_t* radii) {
+    GS_REQUIRE(n_rows >= 0, "n_rows >= 0");
+    VisibleAdamArgs va;
+    int64_t work;
+    if (int rc = adam_prepare(va.a, &work, n, params, exp_avg, exp_avg_sq, n_segments, seg_ends_host, seg_lens_host, seg_grads_host, seg_lrs_host,
+                              beta1, beta2, eps, step, grad_scale, hyper_dev, applied_dev)) return rc;
+    if (n == 0 || n_rows == 0) return GS_OK;
+    GS_REQUIRE(seg_widths_host && radii, "null pointer");
+    GS_REQUIRE(((uintptr_t)radii & 3) == 0, "radii must be 4-byte aligned");
+    for (int k = 0; k < kMaxSeg; ++k) va.width[k] = 1u;
+    for (int k = 0; k < n_segments; ++k) {
+        GS_REQUIRE(seg_widths_host[k] >= 0 && seg_widths_host[k] <= 0x7fffffff, "segment widths: 0 (an empty segment) .. 2^31 - 1 floats per Gaussian");
+        GS_REQUIRE(seg_lens_host[k] == n_rows * seg_widths_host[k], "every segment holds n_rows Gaussians: seg_lens[k] == n_rows * seg_widths[k]");
+        va.width[k] = seg_widths_host[k] > 0 ? (uint32_t)seg_widths_host[k] : 1u;
+    }
+    va.radii = radii; va.n_rows = n_rows;
+    if (work == 0) return GS_OK;
+    hipLaunchKernelGGL(adam_step_visible_kernel, dim3(adam_grid(work)), dim3(256), 0, (hipStream_t)stream, va);
+    GS_LAUNCH_CHECK("adam_step_visible_kernel");
     return GS_OK;
 }
 
@@ -164,6 +284,26 @@ extern "C" int gs_adam_step_dev(void* stream, int64_t n, float* params, float* e
     const float zero_lrs[kMaxSeg] = {0.f, 0.f, 0.f, 0.f, 0.f, 0.f, 0.f, 0.f};
     return adam_launch(stream, n, params, exp_avg, exp_avg_sq, n_segments, seg_ends_host, seg_lens_host, seg_grads_host,
                        zero_lrs, beta1, beta2, eps, 1, grad_scale, hyper_dev, applied_dev);
+}
+
+extern "C" int gs_adam_step_visible(void* stream, int64_t n, float* params, float* exp_avg, float* exp_avg_sq,
+                                    int n_segments, const int64_t* seg_ends_host, const int64_t* seg_lens_host,
+                                    const float* const* seg_grads_host, const float* seg_lrs_host, float beta1,
+                                    float beta2, float eps, int64_t step, float grad_scale, int64_t n_rows,
+                                    const int64_t* seg_widths_host, const int32_t* radii) {
+    return adam_visible_launch(stream, n, params, exp_avg, exp_avg_sq, n_segments, seg_ends_host, seg_lens_host, seg_grads_host,
+                               seg_lrs_host, beta1, beta2, eps, step, grad_scale, nullptr, nullptr, n_rows, seg_widths_host, radii);
+}
+
+extern "C" int gs_adam_step_visible_dev(void* stream, int64_t n, float* params, float* exp_avg, float* exp_avg_sq,
+                                        int n_segments, const int64_t* seg_ends_host, const int64_t* seg_lens_host,
+                                        const float* const* seg_grads_host, float beta1, float beta2, float eps, float grad_scale,
+                                        const float* hyper_dev, int64_t* applied_dev, int64_t n_rows,
+                                        const int64_t* seg_widths_host, const int32_t* radii) {
+    GS_REQUIRE(hyper_dev != nullptr, "hyper_dev (gs_adam_hyper) is required");
+    const float zero_lrs[kMaxSeg] = {0.f, 0.f, 0.f, 0.f, 0.f, 0.f, 0.f, 0.f};
+    return adam_visible_launch(stream, n, params, exp_avg, exp_avg_sq, n_segments, seg_ends_host, seg_lens_host, seg_grads_host,
+                               zero_lrs, beta1, beta2, eps, 1, grad_scale, hyper_dev, applied_dev, n_rows, seg_widths_host, radii);
 }
 
 namespace gs {

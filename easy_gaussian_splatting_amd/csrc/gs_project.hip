@@ -397,8 +397,15 @@ __device__ __forceinline__ float* adam_m(const ProjBwdArgs& a, int t);
 __device__ __forceinline__ float* adam_v(const ProjBwdArgs& a, int t);
 __device__ __forceinline__ float sh_adam_isbc2(const ProjBwdArgs& a);
 __device__ __forceinline__ float sh_adam_ss(const ProjBwdArgs& a, int t);
-template <int KC, class A>
-__device__ __forceinline__ void adam_sh_tile(const float* tile, int rows, int Krt, int64_t n0, const A& a) {
+// SEL (project_bwd_selective_kernel): vis_s[g] says whether Gaussian g of the block was seen -- a culled one keeps its bits, a 16-byte
+// group none of whose (at most two: rest_f >= 9) Gaussians was seen is neither loaded nor stored, a mixed one selects per element.
+__device__ __forceinline__ void adam1_sel(bool on, float& p, float g, float& m, float& v, float b1, float b2, float eps, float isbc2, float ss) {
+    float pn = p, mn = m, vn = v;
+    adam1(pn, g, mn, vn, b1, b2, eps, isbc2, ss);
+    p = on ? pn : p; m = on ? mn : m; v = on ? vn : v;
+}
+template <int KC, bool SEL = false, class A>
+__device__ __forceinline__ void adam_sh_tile(const float* tile, int rows, int Krt, int64_t n0, const A& a, const int* vis_s = nullptr) {
     const int K = KC > 0 ? KC : Krt;
     const int row_f = 3 * K, stride = row_f + 1;
     const float isbc2 = sh_adam_isbc2(a), ss0 = sh_adam_ss(a, 3), ssr = sh_adam_ss(a, 4);
@@ -406,6 +413,7 @@ __device__ __forceinline__ void adam_sh_tile(const float* tile, int rows, int Kr
         float *p0 = adam_p(a, 3) + n0 * 3, *m0 = adam_m(a, 3) + n0 * 3, *v0 = adam_v(a, 3) + n0 * 3;
         for (int e = threadIdx.x; e < rows * 3; e += blockDim.x) {
             const int g = e / 3;
+            if (SEL && !vis_s[g]) continue;
             float p = p0[e], m = m0[e], v = v0[e];
             adam1(p, tile[g * stride + (e - 3 * g)], m, v, a.ad_b1, a.ad_b2, a.ad_eps, isbc2, ss0);
             p0[e] = p; m0[e] = m; v0[e] = v;
@@ -426,31 +434,44 @@ __device__ __forceinline__ void adam_sh_tile(const float* tile, int rows, int Kr
         const int n4 = vec_end >> 2;
         for (int e0 = threadIdx.x; e0 < n4; e0 += kAdamBatch * (int)blockDim.x) {
             float4 p[kAdamBatch], m[kAdamBatch], v[kAdamBatch];
+            bool seen[kAdamBatch];   // (SEL) somebody saw one of the group's Gaussians
 #pragma unroll
             for (int u = 0; u < kAdamBatch; ++u) {
                 const int e4 = e0 + u * (int)blockDim.x;
-                if (e4 < n4) { p[u] = pr4[e4]; m[u] = nt_load4(mr4 + e4); v[u] = nt_load4(vr4 + e4); }
+                seen[u] = e4 < n4;
+                if (SEL && seen[u]) seen[u] = (vis_s[(e4 << 2) / rest_f] | vis_s[((e4 << 2) + 3) / rest_f]) != 0;
+                if (seen[u]) { p[u] = pr4[e4]; m[u] = nt_load4(mr4 + e4); v[u] = nt_load4(vr4 + e4); }
             }
 #pragma unroll
             for (int u = 0; u < kAdamBatch; ++u) {
                 const int e4 = e0 + u * (int)blockDim.x;
-                if (e4 < n4) {
+                if (seen[u]) {
                     float gg[4];
+                    bool on[4];
 #pragma unroll
                     for (int i = 0; i < 4; ++i) {
                         const int e = (e4 << 2) + i, g = e / rest_f;
                         gg[i] = tile[g * stride + 3 + (e - g * rest_f)];
+                        on[i] = !SEL || vis_s[g] != 0;
                     }
-                    adam1(p[u].x, gg[0], m[u].x, v[u].x, a.ad_b1, a.ad_b2, a.ad_eps, isbc2, ssr);
-                    adam1(p[u].y, gg[1], m[u].y, v[u].y, a.ad_b1, a.ad_b2, a.ad_eps, isbc2, ssr);
-                    adam1(p[u].z, gg[2], m[u].z, v[u].z, a.ad_b1, a.ad_b2, a.ad_eps, isbc2, ssr);
-                    adam1(p[u].w, gg[3], m[u].w, v[u].w, a.ad_b1, a.ad_b2, a.ad_eps, isbc2, ssr);
+                    if (SEL) {
+                        adam1_sel(on[0], p[u].x, gg[0], m[u].x, v[u].x, a.ad_b1, a.ad_b2, a.ad_eps, isbc2, ssr);
+                        adam1_sel(on[1], p[u].y, gg[1], m[u].y, v[u].y, a.ad_b1, a.ad_b2, a.ad_eps, isbc2, ssr);
+                        adam1_sel(on[2], p[u].z, gg[2], m[u].z, v[u].z, a.ad_b1, a.ad_b2, a.ad_eps, isbc2, ssr);
+                        adam1_sel(on[3], p[u].w, gg[3], m[u].w, v[u].w, a.ad_b1, a.ad_b2, a.ad_eps, isbc2, ssr);
+                    } else {
+                        adam1(p[u].x, gg[0], m[u].x, v[u].x, a.ad_b1, a.ad_b2, a.ad_eps, isbc2, ssr);
+                        adam1(p[u].y, gg[1], m[u].y, v[u].y, a.ad_b1, a.ad_b2, a.ad_eps, isbc2, ssr);
+                        adam1(p[u].z, gg[2], m[u].z, v[u].z, a.ad_b1, a.ad_b2, a.ad_eps, isbc2, ssr);
+                        adam1(p[u].w, gg[3], m[u].w, v[u].w, a.ad_b1, a.ad_b2, a.ad_eps, isbc2, ssr);
+                    }
                     pr4[e4] = p[u]; nt_store4(m[u], mr4 + e4); nt_store4(v[u], vr4 + e4);
                 }
             }
         }
         for (int e = vec_end + threadIdx.x; e < total; e += blockDim.x) {
             const int g = e / rest_f;
+            if (SEL && !vis_s[g]) continue;
             float p = pr[e], m = mr[e], v = vr[e];
             adam1(p, tile[g * stride + 3 + (e - g * rest_f)], m, v, a.ad_b1, a.ad_b2, a.ad_eps, isbc2, ssr);
             pr[e] = p; mr[e] = m; vr[e] = v;
@@ -460,7 +481,9 @@ __device__ __forceinline__ void adam_sh_tile(const float* tile, int rows, int Kr
 
 // In-place Adam of one block's slice of the four geometry tensors (groups 0 means[N,3], 1 log_scales[N,3], 2 quats[N,4],
 // 5 logit_opacities[N]) from gradients staged in LDS in element order: tile + {0, 3, 6, 10} * kProjThreads.
-__device__ __forceinline__ void adam_geo_tile(const float* tile, int rows, int64_t n0, const ProjBwdArgs& a) {
+// SEL: as in adam_sh_tile -- vis_s[g] selects per element (the Gaussian of element e of a tensor: e / width), a group nobody saw is skipped.
+template <bool SEL = false>
+__device__ __forceinline__ void adam_geo_tile(const float* tile, int rows, int64_t n0, const ProjBwdArgs& a, const int* vis_s = nullptr) {
     constexpr int kSeg = 4;
     const int group[kSeg] = {0, 1, 2, 5}, width[kSeg] = {3, 3, 4, 1}, goff[kSeg] = {0, 3 * kProjThreads, 6 * kProjThreads, 10 * kProjThreads};
     const float isbc2 = a.ad_hyper[0];
@@ -473,6 +496,10 @@ __device__ __forceinline__ void adam_geo_tile(const float* tile, int rows, int64
         float *pp = adam_p(a, t) + n0 * width[sgi], *mm = adam_m(a, t) + n0 * width[sgi], *vv = adam_v(a, t) + n0 * width[sgi];
         const bool aligned = ((((uintptr_t)pp | (uintptr_t)mm | (uintptr_t)vv) & 15) == 0);
         has[sgi] = aligned && e4 < (total >> 2);
+        if (SEL && has[sgi]) {   // (two Gaussians at most for the widths 3 and 4, four for the opacities)
+            has[sgi] = width[sgi] == 1 ? (vis_s[4 * e4] | vis_s[4 * e4 + 1] | vis_s[4 * e4 + 2] | vis_s[4 * e4 + 3]) != 0
+                                       : (vis_s[(4 * e4) / width[sgi]] | vis_s[(4 * e4 + 3) / width[sgi]]) != 0;
+        }
         if (has[sgi]) {
             p[sgi] = reinterpret_cast<const float4*>(pp)[e4];
             m[sgi] = nt_load4(reinterpret_cast<const float4*>(mm) + e4);
@@ -487,10 +514,18 @@ __device__ __forceinline__ void adam_geo_tile(const float* tile, int rows, int64
         const float* g = tile + goff[sgi];
         if (has[sgi]) {
             const float4 g4 = *reinterpret_cast<const float4*>(g + 4 * e4);
-            adam1(p[sgi].x, g4.x, m[sgi].x, v[sgi].x, a.ad_b1, a.ad_b2, a.ad_eps, isbc2, ss);
-            adam1(p[sgi].y, g4.y, m[sgi].y, v[sgi].y, a.ad_b1, a.ad_b2, a.ad_eps, isbc2, ss);
-            adam1(p[sgi].z, g4.z, m[sgi].z, v[sgi].z, a.ad_b1, a.ad_b2, a.ad_eps, isbc2, ss);
-            adam1(p[sgi].w, g4.w, m[sgi].w, v[sgi].w, a.ad_b1, a.ad_b2, a.ad_eps, isbc2, ss);
+            if (SEL) {
+                const int w = width[sgi];
+                adam1_sel(vis_s[(4 * e4) / w] != 0, p[sgi].x, g4.x, m[sgi].x, v[sgi].x, a.ad_b1, a.ad_b2, a.ad_eps, isbc2, ss);
+                adam1_sel(vis_s[(4 * e4 + 1) / w] != 0, p[sgi].y, g4.y, m[sgi].y, v[sgi].y, a.ad_b1, a.ad_b2, a.ad_eps, isbc2, ss);
+                adam1_sel(vis_s[(4 * e4 + 2) / w] != 0, p[sgi].z, g4.z, m[sgi].z, v[sgi].z, a.ad_b1, a.ad_b2, a.ad_eps, isbc2, ss);
+                adam1_sel(vis_s[(4 * e4 + 3) / w] != 0, p[sgi].w, g4.w, m[sgi].w, v[sgi].w, a.ad_b1, a.ad_b2, a.ad_eps, isbc2, ss);
+            } else {
+                adam1(p[sgi].x, g4.x, m[sgi].x, v[sgi].x, a.ad_b1, a.ad_b2, a.ad_eps, isbc2, ss);
+                adam1(p[sgi].y, g4.y, m[sgi].y, v[sgi].y, a.ad_b1, a.ad_b2, a.ad_eps, isbc2, ss);
+                adam1(p[sgi].z, g4.z, m[sgi].z, v[sgi].z, a.ad_b1, a.ad_b2, a.ad_eps, isbc2, ss);
+                adam1(p[sgi].w, g4.w, m[sgi].w, v[sgi].w, a.ad_b1, a.ad_b2, a.ad_eps, isbc2, ss);
+            }
             reinterpret_cast<float4*>(pp)[e4] = p[sgi];
             nt_store4(m[sgi], reinterpret_cast<float4*>(mm) + e4);
             nt_store4(v[sgi], reinterpret_cast<float4*>(vv) + e4);
@@ -498,6 +533,7 @@ __device__ __forceinline__ void adam_geo_tile(const float* tile, int rows, int64
         // what the 16-byte groups do not cover: the whole slice when a tensor is not 16-byte aligned, else its last 0-3 floats
         const bool aligned = ((((uintptr_t)pp | (uintptr_t)mm | (uintptr_t)vv) & 15) == 0);
         for (int e = (aligned ? (total & ~3) : 0) + (int)threadIdx.x; e < total; e += blockDim.x) {
+            if (SEL && !vis_s[e / width[sgi]]) continue;
             float ps = pp[e], ms = mm[e], vs = vv[e];
             adam1(ps, g[e], ms, vs, a.ad_b1, a.ad_b2, a.ad_eps, isbc2, ss);
             pp[e] = ps; mm[e] = ms; vv[e] = vs;
@@ -644,13 +680,13 @@ __device__ __forceinline__ void row_sum_wave(const A& a, int nr, int r0, int bas
 template <int DEG, bool ADAM, bool SUMS = false, bool SCALE_REG = false>
 __global__ __launch_bounds__(kProjThreads) void project_bwd_kernel(const ProjBwdArgs a) {
     constexpr int REG = SCALE_REG ? 1 : 0, CAM = kCamPinhole;
-    constexpr bool AA = false;
+    constexpr bool AA = false, SELECT = false;
 #include "gs_project_bwd_body.h"
 }
 // the fused form under a Gaussian budget (gs_project_bwd_adam_mcmc): REG = 2 the budget term alone, 3 behind the scale-ratio term
 template <int DEG, int REG, bool SUMS = false>
 __global__ __launch_bounds__(kProjThreads) void project_bwd_budget_kernel(const ProjBwdArgs a) {
-    constexpr bool ADAM = true, AA = false;
+    constexpr bool ADAM = true, AA = false, SELECT = false;
     constexpr int CAM = kCamPinhole;
 #include "gs_project_bwd_body.h"
 }
@@ -658,7 +694,7 @@ __global__ __launch_bounds__(kProjThreads) void project_bwd_budget_kernel(const 
 // the fused form with a depth gradient (gs_project_bwd_adam_depth): REG = 4 | the two regularisers' bits
 template <int DEG, int REG>
 __global__ __launch_bounds__(kProjThreads) void project_bwd_depth_kernel(const ProjBwdArgs a) {
-    constexpr bool ADAM = true, SUMS = false, AA = false;
+    constexpr bool ADAM = true, SUMS = false, AA = false, SELECT = false;
     constexpr int CAM = kCamPinhole;
 #include "gs_project_bwd_body.h"
 }
@@ -669,7 +705,7 @@ __global__ __launch_bounds__(kProjThreads) void project_bwd_depth_kernel(const P
 template <int DEG, bool ADAM, int REG, int CAM>
 __global__ __launch_bounds__(kProjThreads) void project_bwd_cm_kernel(const ProjBwdArgs a) {
     static_assert(CAM != kCamPinhole && (REG == 0 || (ADAM && REG == 1)), "pinhole: project_bwd_kernel; REG: the scale-ratio term, fused form only");
-    constexpr bool SUMS = false, AA = false;
+    constexpr bool SUMS = false, AA = false, SELECT = false;
 #include "gs_project_bwd_body.h"
 }
 
@@ -679,7 +715,18 @@ __global__ __launch_bounds__(kProjThreads) void project_bwd_cm_kernel(const Proj
 template <int DEG, bool ADAM, int REG>
 __global__ __launch_bounds__(kProjThreads) void project_bwd_aa_kernel(const ProjBwdArgs a) {
     static_assert(REG == 0 || (ADAM && REG == 1), "REG: the scale-ratio term, fused form only");
-    constexpr bool SUMS = false, AA = true;
+    constexpr bool SUMS = false, AA = true, SELECT = false;
+    constexpr int CAM = kCamPinhole;
+#include "gs_project_bwd_body.h"
+}
+
+// the fused form over the Gaussians the step saw (gs_project_bwd_selective; REG = 0, or 1: the scale-ratio regulariser; pinhole, classic
+// mode, gradient rows): a culled Gaussian keeps the bits of its parameters and moments, 16-byte groups nobody saw are neither loaded
+// nor stored, and a block without a visible Gaussian leaves behind the row sum (DESIGN.md "Updating only what a step saw")
+template <int DEG, int REG>
+__global__ __launch_bounds__(kProjThreads) void project_bwd_selective_kernel(const ProjBwdArgs a) {
+    static_assert(REG == 0 || REG == 1, "REG: the scale-ratio term");
+    constexpr bool ADAM = true, SUMS = false, AA = false, SELECT = true;
     constexpr int CAM = kCamPinhole;
 #include "gs_project_bwd_body.h"
 }
@@ -1470,8 +1517,10 @@ static int project_bwd_adam(void* stream, int64_t N, int K, int sh_degree, float
                             int64_t* applied_dev, float* max_radii, float* grad_norm_accum, float* counts,
                             const float* sh_jac, int reg, float max_ratio, float lambda, double bud_a, double bud_b,
                             const float* row_sums = nullptr, const float* v_depths = nullptr, int camera_model = GS_CAMERA_PINHOLE,
-                            bool aa = false) {
+                            bool aa = false, bool selective = false) {
     GS_REQUIRE_CAMERA(camera_model);
+    GS_REQUIRE(!selective || (!aa && camera_model == GS_CAMERA_PINHOLE && !(reg & 2) && !row_sums && !v_depths),
+               "the selective fused backward: pinhole, classic mode, gradient rows; no budget, row-sums or depth variant of it exists");
     GS_REQUIRE(!aa || (camera_model == GS_CAMERA_PINHOLE && !(reg & 2) && !row_sums && !v_depths),
                "the antialiased mode: the pinhole model; no budget, row-sums or depth variant of the fused backward exists for it");
     GS_REQUIRE(!aa || current_rounds().phase == 0, "the antialiased mode is one-round only");
@@ -1523,6 +1572,7 @@ static int project_bwd_adam(void* stream, int64_t N, int K, int sh_degree, float
     if (reg == 1) GS_PBK(project_bwd_cm_kernel<D, true, 1, ((D) == 4 && (M) == kCamFisheye) ? kCamFisheyeSelect : (M)>)                   \
     else GS_PBK(project_bwd_cm_kernel<D, true, 0, M>)
 #define GS_PB(D)                                                                                                        \
+    if (selective) { if (reg == 1) GS_PBK(project_bwd_selective_kernel<D, 1>) else GS_PBK(project_bwd_selective_kernel<D, 0>) } else \
     if (aa) { if (reg == 1) GS_PBK(project_bwd_aa_kernel<D, true, 1>) else GS_PBK(project_bwd_aa_kernel<D, true, 0>) } else \
     if (camera_model == GS_CAMERA_ORTHO) { GS_PBC(D, kCamOrtho) } else if (camera_model == GS_CAMERA_FISHEYE) { GS_PBC(D, kCamFisheye) } else \
     if (v_depths) {                                                                                                     \
@@ -1625,6 +1675,22 @@ extern "C" int gs_project_bwd_adam_reg_aa(void* stream, int64_t N, int K, int sh
                             near_plane, far_plane, radii, colors_post, tiles_per_gauss, cum_tiles, rows, row_base, qmask, v_means2d_abs,
                             beta1, beta2, eps, hyper_dev, applied_dev, max_radii, grad_norm_accum, counts, sh_jac, 1, max_ratio, lambda, 0.0, 0.0,
                             nullptr, nullptr, GS_CAMERA_PINHOLE, true);
+}
+
+// gs_project_bwd_adam (reg_on = 0) / gs_project_bwd_adam_reg (reg_on = 1) over the Gaussians the step saw: project_bwd_selective_kernel
+extern "C" int gs_project_bwd_selective(void* stream, int64_t N, int K, int sh_degree, float* params, float* exp_avg, float* exp_avg_sq,
+                                        const int64_t* offsets_host, const float* viewmats, const float* Ks, int width, int height,
+                                        float eps2d, float near_plane, float far_plane, const int32_t* radii, const float* colors_post,
+                                        const int32_t* tiles_per_gauss, const int32_t* cum_tiles, const float* rows, const int32_t* row_base,
+                                        const uint8_t* qmask, float* v_means2d_abs, float beta1, float beta2, float eps, const float* hyper_dev,
+                                        int64_t* applied_dev, float* max_radii, float* grad_norm_accum, float* counts,
+                                        const float* sh_jac, int reg_on, float max_ratio, float lambda) {
+    GS_REQUIRE(((uintptr_t)params & 3) == 0, "params must be 4-byte aligned");
+    GS_REQUIRE(reg_on == 0 || reg_on == 1, "reg_on is 0 or 1");
+    return project_bwd_adam(stream, N, K, sh_degree, params, exp_avg, exp_avg_sq, offsets_host, viewmats, Ks, width, height, eps2d,
+                            near_plane, far_plane, radii, colors_post, tiles_per_gauss, cum_tiles, rows, row_base, qmask, v_means2d_abs,
+                            beta1, beta2, eps, hyper_dev, applied_dev, max_radii, grad_norm_accum, counts, sh_jac, reg_on, max_ratio, lambda, 0.0, 0.0,
+                            nullptr, nullptr, GS_CAMERA_PINHOLE, false, true);
 }
 
 // ... with the budget regulariser's gradients in v_opacity and v_scale (its value: gs_mcmc_reg in front of this call), behind the

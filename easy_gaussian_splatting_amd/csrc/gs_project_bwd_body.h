@@ -1,5 +1,5 @@
 // The body of project_bwd_kernel / project_bwd_budget_kernel / project_bwd_depth_kernel / project_bwd_cm_kernel (gs_project.hip), which define DEG, ADAM,
-// SUMS, the mask REG, the camera model CAM and the antialiased mode AA around it.
+// SUMS, the mask REG, the camera model CAM, the antialiased mode AA and SELECT (the fused form over the visible Gaussians only) around it.
 // Included once per kernel template, inside its braces: no include guard, nothing but the body.
     extern __shared__ __attribute__((aligned(16))) float smem[];
     if (guard_tripped(a.guard)) return;
@@ -65,6 +65,16 @@
         }
         vis_s[threadIdx.x] = vis ? 1 : 0;
         __syncthreads();   // (every wave is done with its row-sum scratch in `tile`)
+        if (SELECT) {
+            // Nobody in the block was seen: no parameter of it moves.  What the dense kernel leaves behind for culled Gaussians is the
+            // absgrad side channel alone (the fused entry hands out no other per-Gaussian output) -- no SH staging, no Adam walk.
+            const int l = threadIdx.x & 63;
+            static_assert(kProjThreads == 256, "the block-wide OR below reads four flags per lane");
+            if (__ballot(vis_s[l] | vis_s[l + 64] | vis_s[l + 128] | vis_s[l + 192]) == 0) {
+                if (in_range) reinterpret_cast<float2*>(a.v_means2d_abs)[f] = make_float2(s.v[2], s.v[3]);
+                return;
+            }
+        }
         const int rows = (int)min((int64_t)kProjThreads, a.N - n0);
         if (!use_jac) {
             if (a.sh_rest) {
@@ -95,9 +105,9 @@
         }
         if (ADAM) {
             __syncthreads();
-            if (DEG == 4) adam_sh_tile<25>(tile, rows, 25, n0, a);
-            else if (a.K == 16) adam_sh_tile<16>(tile, rows, 16, n0, a);
-            else adam_sh_tile<0>(tile, rows, a.K, n0, a);
+            if (DEG == 4) adam_sh_tile<25, SELECT>(tile, rows, 25, n0, a, vis_s);
+            else if (a.K == 16) adam_sh_tile<16, SELECT>(tile, rows, 16, n0, a, vis_s);
+            else adam_sh_tile<0, SELECT>(tile, rows, a.K, n0, a, vis_s);
         } else if (a.v_colors) {  // NULL: the caller rebuilds the SH gradients from v_colors_pre (gs_sh_grad_views)
             __syncthreads();
             if (DEG == 4) write_sh_tile_k<25>(tile, rows, 25, n0, a.v_colors, a.v_sh_rest, a.accumulate);
@@ -144,7 +154,9 @@
     if (in_range) {
         if (a.activations && vis) { const float o = act_opacity(p_opac[n], 1); op_fac = o * (1.f - o); }
         v_scale[0] *= sc_fac[0]; v_scale[1] *= sc_fac[1]; v_scale[2] *= sc_fac[2];
-        if (REG & 1) {   // + the regulariser's gradient (culled Gaussians too: every Gaussian has a term), from the parameters before the update
+        // + the regulariser's gradient (culled Gaussians too: every Gaussian has a term), from the parameters before the update
+        // (SELECT: a culled Gaussian's term is not formed -- nothing reads it)
+        if ((REG & 1) && (!SELECT || vis)) {
             float gl[3];
             scale_reg_term(p_scales[3 * n], p_scales[3 * n + 1], p_scales[3 * n + 2], a.reg_ratio, a.reg_grad, gl);
             v_scale[0] = fp_opaque(v_scale[0]) + gl[0]; v_scale[1] = fp_opaque(v_scale[1]) + gl[1]; v_scale[2] = fp_opaque(v_scale[2]) + gl[2];
@@ -203,5 +215,5 @@
         gq[4 * tid] = v_quat[0]; gq[4 * tid + 1] = v_quat[1]; gq[4 * tid + 2] = v_quat[2]; gq[4 * tid + 3] = v_quat[3];
         go[tid] = geo_op;
         __syncthreads();
-        adam_geo_tile(tile, (int)min((int64_t)kProjThreads, a.N - n0), n0, a);
+        adam_geo_tile<SELECT>(tile, (int)min((int64_t)kProjThreads, a.N - n0), n0, a, vis_s);
     }

@@ -157,15 +157,49 @@ class FusedAdam(torch.optim.Optimizer):
                                    "after the optimizer was built); rebuild the optimizer")
 
     @torch.no_grad()
-    def step(self, closure=None, *, only=None, grad_scale: float = 1.0, advance: bool = True, stats=None):
+    def _visible_rows(self, visible, stats):
+        """`step(visible=)`: validates the mask before anything is loaded or launched; returns (int32 [N] radii-like tensor, widths)."""
+        if not isinstance(visible, torch.Tensor):
+            raise TypeError("FusedAdam.step(visible=...): an int32 [N] or [C, N] tensor (meta['radii']) or a bool [N] tensor")
+        if stats is not None:
+            raise ValueError("FusedAdam.step(visible=..., stats=...): the step with statistics riding along (gs_adam_step_stats: the "
+                             "view-parallel step) has no visible form")
+        if visible.dtype == torch.bool:
+            if visible.dim() != 1:
+                raise ValueError("FusedAdam.step(visible=...): a bool mask is [N]")
+        elif visible.dtype != torch.int32 or visible.dim() not in (1, 2):
+            raise ValueError(f"FusedAdam.step(visible=...): int32 [N] or [C, N] radii, or bool [N] (got {visible.dtype}, "
+                             f"{tuple(visible.shape)})")
+        if visible.device != self.flat_param.device:
+            raise ValueError(f"FusedAdam.step(visible=...): on {visible.device}, the parameters are on {self.flat_param.device}")
+        n_rows = int(visible.shape[-1])
+        widths = []
+        for grp, p in self._plist:
+            if p.dim() < 1 or int(p.shape[0]) != n_rows:
+                raise ValueError(f"FusedAdam.step(visible=...): parameter {grp.get('name', '?')!r} of shape {tuple(p.shape)} does not hold "
+                                 f"one row per entry of `visible` ({n_rows})")
+            widths.append(p.numel() // n_rows if n_rows else 0)
+        if visible.dim() == 2:   # a Gaussian is visible iff some camera of the step saw it
+            visible = visible.amax(dim=0) if visible.shape[0] else visible.new_zeros((n_rows,))
+        return visible.to(torch.int32).contiguous(), widths
+
+    @torch.no_grad()
+    def step(self, closure=None, *, only=None, grad_scale: float = 1.0, advance: bool = True, stats=None, visible=None):
         """One Adam step.  `only`: iterable of group names -- update just those groups (the others are
         skipped like `grad is None`); with `advance=False` the step count is not incremented, so a
         step can be issued in two launches (`step(only=A)`, then `step(only=B, advance=False)`).
         `grad_scale` multiplies every gradient first (1/world: mean over ranks of summed gradients).
         `stats` = (src0, src1, dst0, dst1), float32 tensors of one length: `dst0 += src0; dst1 += src1` in the same launch
-        (distributed.ViewParallelStep: the all-reduced statistics of `update_statistics`)."""
+        (distributed.ViewParallelStep: the all-reduced statistics of `update_statistics`).
+        `visible`: the step's `meta["radii"]` -- int32 [N] or [C, N] (a Gaussian counts as seen when any camera's entry is > 0), or
+        a bool [N] mask: only the Gaussians the step saw are updated (gsplat's `visible_adam`; gs_adam_step_visible).  A seen
+        Gaussian receives the dense update, the bias corrections included; a culled one keeps the bits of its parameters and
+        moments whatever its gradient holds; the step count advances once for everyone.  Every parameter must hold one row per
+        Gaussian.  Not together with `stats` (`ValueError`).  None (default): the dense step."""
         if closure is not None:
             raise NotImplementedError("closures are not supported")
+        if visible is not None:
+            visible, widths = self._visible_rows(visible, stats)
         from . import _native as nat
         L = nat.lib()
         self._check_views()
@@ -196,6 +230,11 @@ class FusedAdam(torch.optim.Optimizer):
                                                self.exp_avg_sq.data_ptr(), ns, ends, lens, gptr, lrs, float(b1), float(b2),
                                                float(self.defaults["eps"]), self._step, float(grad_scale), s0.numel(), s0.data_ptr(),
                                                s1.data_ptr(), d0.data_ptr(), d1.data_ptr()), "gs_adam_step_stats")
+            elif visible is not None:
+                nat.check(L.gs_adam_step_visible(st, self.flat_param.numel(), self.flat_param.data_ptr(), self.exp_avg.data_ptr(),
+                                                 self.exp_avg_sq.data_ptr(), ns, ends, lens, gptr, lrs, float(b1), float(b2),
+                                                 float(self.defaults["eps"]), self._step, float(grad_scale), visible.numel(),
+                                                 (ct.c_int64 * ns)(*widths), visible.data_ptr()), "gs_adam_step_visible")
             else:
                 nat.check(L.gs_adam_step(st, self.flat_param.numel(), self.flat_param.data_ptr(), self.exp_avg.data_ptr(),
                                          self.exp_avg_sq.data_ptr(), ns, ends, lens, gptr, lrs, float(b1), float(b2),

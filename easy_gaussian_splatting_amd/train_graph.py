@@ -153,7 +153,13 @@ _REFUSED = {
                                    "'auto' (it resolves to off) or 'off'")))}
 
 
-def _refuse_combinations(model, camera_model, rasterize_mode, mcmc, poses, depth, rounds) -> str:
+# `visible_adam`: (what it was combined with, the variant of the selective kernel that would serve it), in the order the refusals fire
+_NO_SELECTIVE = (("`mcmc`", "budget-regulariser (project_bwd_budget_kernel)"), ("`poses`", "row-sums (project_bwd_kernel<.., SUMS = true>)"),
+                 ("`depth`", "depth-gradient (project_bwd_depth_kernel)"), ("camera_model", "camera-model (project_bwd_cm_kernel)"),
+                 ("rasterize_mode", "antialiased (project_bwd_aa_kernel)"))
+
+
+def _refuse_combinations(model, camera_model, rasterize_mode, mcmc, poses, depth, rounds, visible_adam: bool = False) -> str:
     """TrainStepGraph(camera_model=..., rasterize_mode=..., depth=...): validates the three, resolves the mode against the model's
     attribute and refuses, before any device work, what `_REFUSED` lists for each that is not at its default.  Returns the mode."""
     given = {"camera_model": camera_model != "pinhole", "`mcmc`": mcmc is not None, "`poses`": poses is not None, "`depth`": depth is not None,
@@ -185,6 +191,13 @@ def _refuse_combinations(model, camera_model, rasterize_mode, mcmc, poses, depth
         if not isinstance(depth, DepthSupervision):
             raise TypeError("TrainStepGraph(depth=...): a depth_loss.DepthSupervision")
         refuse("depth", "depth=...")
+    if visible_adam:
+        given.update({"rasterize_mode": rasterize_mode != "classic"})
+        for option, variant in _NO_SELECTIVE:
+            if given[option]:
+                option = {"camera_model": f"camera_model={camera_model!r}", "rasterize_mode": "rasterize_mode='antialiased'"}.get(option, option)
+                raise ValueError(f"TrainStepGraph(visible_adam=True) with {option} -- the fused projection backward + Adam over the visible "
+                                 f"Gaussians (gs_project_bwd_selective: project_bwd_selective_kernel) has no {variant} variant yet")
     return rasterize_mode
 
 
@@ -221,7 +234,7 @@ class TrainStepGraph:
                  exposure_lr: float = 1e-2, exposure_betas: Tuple[float, float] = (0.9, 0.999), exposure_eps: float = 1e-15, bilagrid=None,
                  bilagrid_lr: float = 2e-3, bilagrid_betas: Tuple[float, float] = (0.9, 0.999), bilagrid_eps: float = 1e-15,
                  bilagrid_tv: float = 10.0, depth=None, gt_depth: Optional[Tensor] = None, camera_model: str = "pinhole",
-                 rasterize_mode: Optional[str] = None):
+                 rasterize_mode: Optional[str] = None, visible_adam: bool = False):
         """`mcmc`: an `mcmc.MCMCStrategy(model, ..., noise="counter")` -- the step then trains under its Gaussian budget: `mcmc_reg` =
         (opacity_reg, scale_reg) of `strategy.regularization()` enters the loss (out["mcmc_reg"]) and the update, and the strategy's
         noise runs behind Adam inside the step, at noise_lr x the means learning rate of that step.  None (default): nothing changes.
@@ -285,9 +298,19 @@ class TrainStepGraph:
         gs_project_bwd_adam_aa / gs_project_bwd_adam_reg_aa.  Works with a mask, the scale regulariser, `exposure`, `bilagrid` and
         `HostFeed`, always in one depth round ("auto" resolves to off).  Refused before any device work (`ValueError`): `mcmc`, `poses`,
         `depth`, `rounds="on"`, a camera model other than pinhole and `ViewParallelGraphStep` -- each needs a variant of the fused
-        projection backward that exists for the classic mode only."""
+        projection backward that exists for the classic mode only.
+        `visible_adam`: True -- the step updates only the Gaussians it SAW, `radii > 0` under the step's camera (gsplat's
+        `visible_adam`; DESIGN.md "Updating only what a step saw"): a seen Gaussian receives the dense update, bias corrections from the
+        one step count included; a culled one keeps the bits of its six parameters and of both moments -- no decay, no move along a
+        stale first moment, no scale-regulariser term.  The loss values in `out`, the statistics and the step guard are the dense
+        step's.  With `fuse_adam` the step updates with gs_project_bwd_selective, without it with gs_adam_step_visible_dev on the step's
+        radii.  Works with a mask, the scale regulariser, `exposure`, `bilagrid`, `HostFeed`, `rounds` in any setting and a re-capture
+        after a refinement.  Refused before any device work (`ValueError`): `mcmc`, `poses`, `depth`, a camera model other than
+        pinhole, `rasterize_mode="antialiased"` and `ViewParallelGraphStep` -- each needs a selective variant of its own fused kernel.
+        False (default): nothing changes, launch for launch."""
         rounds = os.environ.get("GS_TG_ROUNDS", rounds)
-        self.antialiased = _refuse_combinations(model, camera_model, rasterize_mode, mcmc, poses, depth, rounds) == "antialiased"
+        self.visible_adam = bool(visible_adam)
+        self.antialiased = _refuse_combinations(model, camera_model, rasterize_mode, mcmc, poses, depth, rounds, self.visible_adam) == "antialiased"
         self.camera_model = rendering.CAMERA_MODELS[camera_model]
         self.depth = depth
         if depth is not None:
@@ -1081,7 +1104,9 @@ class TrainStepGraph:
                         _p(m.grad_norm_accum), _p(m.collecting_counts), _p(b["sh_jac"]))
             reg_on, ratio, lam = (1, self.max_scale_ratio, self.lambda_scale) if self.scale_reg else (0, 0.0, 0.0)
             mcmc_on, (bud_a, bud_b) = int(self.mcmc is not None), self.mcmc_reg if self.mcmc is not None else (0.0, 0.0)
-            if self.depth is not None:
+            if self.visible_adam:   # (no depth, poses, mcmc, other camera model or mode here: refused at construction)
+                self._ck(L.gs_project_bwd_selective(*row_args, reg_on, ratio, lam), "gs_project_bwd_selective")
+            elif self.depth is not None:
                 # v_z per Gaussian from lane 3 of its gradient rows (gs_depth_grads' gather), then the fused kernel adds v_z times row 2
                 # of the view matrix to the means gradient where gs_depth_grads would: the same update bit for bit
                 self._ck(L.gs_depth_grads_z(st, 1, N, 3, _p(b["radii"]), self._tpg(), _p(b["cum_tiles"]), _p(b["rows"]), _p(b["row_base"]),
@@ -1139,9 +1164,15 @@ class TrainStepGraph:
             ends = (ct.c_int64 * ns)(*opt._ends)
             lens = (ct.c_int64 * ns)(*opt._lens)
             gptr = (ct.c_void_p * ns)(*[_p(g[grp["name"]]) for grp, _ in opt._plist])
-            self._ck(L.gs_adam_step_dev(st, opt.flat_param.numel(), _p(opt.flat_param), _p(opt.exp_avg), _p(opt.exp_avg_sq), ns,
-                                        ends, lens, gptr, float(b1), float(b2), float(opt.defaults["eps"]), 1.0, _p(b["hyper"]),
-                                        _p(b["applied"])), "gs_adam_step_dev")
+            if self.visible_adam:   # the same launch over the Gaussians with radii > 0
+                widths = (ct.c_int64 * ns)(*[p.numel() // N for _, p in opt._plist])
+                self._ck(L.gs_adam_step_visible_dev(st, opt.flat_param.numel(), _p(opt.flat_param), _p(opt.exp_avg), _p(opt.exp_avg_sq), ns,
+                                                    ends, lens, gptr, float(b1), float(b2), float(opt.defaults["eps"]), 1.0, _p(b["hyper"]),
+                                                    _p(b["applied"]), N, widths, _p(b["radii"])), "gs_adam_step_visible_dev")
+            else:
+                self._ck(L.gs_adam_step_dev(st, opt.flat_param.numel(), _p(opt.flat_param), _p(opt.exp_avg), _p(opt.exp_avg_sq), ns,
+                                            ends, lens, gptr, float(b1), float(b2), float(opt.defaults["eps"]), 1.0, _p(b["hyper"]),
+                                            _p(b["applied"])), "gs_adam_step_dev")
         if self.mcmc is not None:   # the noise, on the updated parameters; a skipped step adds none
             self._ck(L.gs_mcmc_noise_step(st, N, _p(b["mcmc_rec"]), _p(m.log_scales), _p(m.quats), _p(m.logit_opacities), _p(m.means)),
                      "gs_mcmc_noise_step")
@@ -1545,6 +1576,9 @@ class ViewParallelGraphStep(TrainStepGraph):
         if kw.get("depth") is not None:
             raise ValueError("ViewParallelGraphStep: no `depth` -- depth supervision inside the captured step is single-GPU "
                              "(TrainStepGraph(depth=...)): the view-parallel exchange carries three colour channels")
+        if kw.get("visible_adam"):
+            raise ValueError("ViewParallelGraphStep: no `visible_adam` -- the view-parallel step's two Adam halves (gs_sh_adam_views, "
+                             "gs_adam_step_stats) have no form over the visible Gaussians (adam_step_visible_kernel carries no statistics)")
         if kw.get("mcmc") is not None:
             raise ValueError("ViewParallelGraphStep: no `mcmc` -- MCMCStrategy refuses torch.distributed (the replicas would need "
                              "broadcast draws)")

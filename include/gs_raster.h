@@ -688,6 +688,22 @@ int gs_adam_step_dev(void* stream, int64_t n, float* params, float* exp_avg, flo
                      const int64_t* seg_ends_host, const int64_t* seg_lens_host, const float* const* seg_grads_host,
                      float beta1, float beta2, float eps, float grad_scale, const float* hyper_dev, int64_t* applied_dev);
 
+/* gs_adam_step / gs_adam_step_dev over the Gaussians a step SAW (gsplat's visible_adam; DESIGN.md "Updating only what a step saw"):
+ * every segment holds n_rows Gaussians, seg_widths_host[k] floats each (seg_lens_host[k] == n_rows * seg_widths_host[k]; width 0: an
+ * empty segment), and radii[n_rows] (device, int32) is the step's projection verdict.  A Gaussian with radii > 0 receives the update
+ * of the dense step, same arithmetic and bias corrections; one with radii <= 0 keeps the bits of its parameters and of both moments
+ * whatever its gradient holds (it is not read).  A 16-byte quad none of whose Gaussians is visible is neither loaded nor stored; the
+ * pad behind a segment is never written.  n == 0 or n_rows == 0: nothing to do.  Honour the step guard like their dense forms. */
+int gs_adam_step_visible(void* stream, int64_t n, float* params, float* exp_avg, float* exp_avg_sq,
+                         int n_segments, const int64_t* seg_ends_host, const int64_t* seg_lens_host,
+                         const float* const* seg_grads_host, const float* seg_lrs_host, float beta1,
+                         float beta2, float eps, int64_t step, float grad_scale, int64_t n_rows,
+                         const int64_t* seg_widths_host, const int32_t* radii);
+int gs_adam_step_visible_dev(void* stream, int64_t n, float* params, float* exp_avg, float* exp_avg_sq, int n_segments,
+                             const int64_t* seg_ends_host, const int64_t* seg_lens_host, const float* const* seg_grads_host,
+                             float beta1, float beta2, float eps, float grad_scale, const float* hyper_dev, int64_t* applied_dev,
+                             int64_t n_rows, const int64_t* seg_widths_host, const int32_t* radii);
+
 /* ---- "next" row f-3: densify / prune on the device (/root/reference/model/gaussian.py:199-349) ----
  * gs_refine_flags: per Gaussian, the reference's decisions.  flags[3][n] (0/1): row 0 the old Gaussian survives the
  * prune (low opacity | max_radii > ratio | largest scale > prune_scale | it was split); row 1 it is split AND its
@@ -824,6 +840,20 @@ int gs_project_bwd_adam_reg(void* stream, int64_t N, int K, int sh_degree, float
                             const uint8_t* qmask, float* v_means2d_abs, float beta1, float beta2, float eps, const float* hyper_dev,
                             int64_t* applied_dev, float* max_radii, float* grad_norm_accum, float* counts, const float* sh_jac,
                             float max_ratio, float lambda);
+
+/* gs_project_bwd_adam (reg_on = 0) / gs_project_bwd_adam_reg (reg_on = 1) over the Gaussians the step SAW (DESIGN.md "Updating only
+ * what a step saw"): a Gaussian with radii > 0 receives the update of the dense entry, bit for bit; one the camera culled keeps the
+ * bits of its six parameters and of both moments, the regulariser's term included (it is not computed).  16-byte groups that hold
+ * culled Gaussians only are neither loaded nor stored, and a block without a visible Gaussian skips its SH staging and both Adam
+ * walks.  v_means2d_abs, the statistics, the step guard and applied_dev as in the dense entries.  Pinhole, classic mode, gradient
+ * rows (no row-sums form), SH degrees 0-4. */
+int gs_project_bwd_selective(void* stream, int64_t N, int K, int sh_degree, float* params, float* exp_avg, float* exp_avg_sq,
+                             const int64_t* offsets_host, const float* viewmats, const float* Ks, int width, int height, float eps2d,
+                             float near_plane, float far_plane, const int32_t* radii, const float* colors_post,
+                             const int32_t* tiles_per_gauss, const int32_t* cum_tiles, const float* rows, const int32_t* row_base,
+                             const uint8_t* qmask, float* v_means2d_abs, float beta1, float beta2, float eps, const float* hyper_dev,
+                             int64_t* applied_dev, float* max_radii, float* grad_norm_accum, float* counts, const float* sh_jac,
+                             int reg_on, float max_ratio, float lambda);
 
 /* Row e: this rank's contribution to the SUM all-reduce of the view-parallel step in one pass: the four
  * geometry gradients and this view's two additive statistics (|absgrad|_2 * max_hw, visibility count)
