@@ -195,11 +195,18 @@ class FusedAdam(torch.optim.Optimizer):
         a bool [N] mask: only the Gaussians the step saw are updated (gsplat's `visible_adam`; gs_adam_step_visible).  A seen
         Gaussian receives the dense update, the bias corrections included; a culled one keeps the bits of its parameters and
         moments whatever its gradient holds; the step count advances once for everyone.  Every parameter must hold one row per
-        Gaussian.  Not together with `stats` (`ValueError`).  None (default): the dense step."""
+        Gaussian.  Not together with `stats` (`ValueError`).  None (default): the dense step.
+        A sparse `.grad` (`rasterization(sparse_grad=True)`) raises `TypeError` before anything moves: it is not densified silently."""
         if closure is not None:
             raise NotImplementedError("closures are not supported")
         if visible is not None:
             visible, widths = self._visible_rows(visible, stats)
+        for grp, p in self._plist:   # (before the step count moves: a refused step changes nothing)
+            if p.grad is not None and p.grad.is_sparse:
+                raise TypeError(f"FusedAdam.step(): the gradient of {grp.get('name', '?')!r} is a sparse tensor "
+                                "(rasterization(sparse_grad=True)); it is not densified silently.  Render without sparse_grad and "
+                                "call step(visible=meta['radii']) to update only the Gaussians the step saw, or step those "
+                                "parameters with torch.optim.SparseAdam")
         from . import _native as nat
         L = nat.lib()
         self._check_views()

@@ -333,7 +333,7 @@ class _Holder:
     the node own its own output (the weak reference lets backward attach `.absgrad` to the very
     tensor object that was handed out in `meta`)."""
 
-    __slots__ = ("meta", "means2d_ref", "absgrad", "debug", "on_colors_pre", "grad_out", "view_payload", "lease_ref", "out_ptrs")
+    __slots__ = ("meta", "means2d_ref", "absgrad", "debug", "on_colors_pre", "grad_out", "view_payload", "lease_ref", "out_ptrs", "pack")
 
     def __init__(self, absgrad: bool):
         self.meta: Dict = {}
@@ -345,6 +345,7 @@ class _Holder:
         self.view_payload = None
         self.lease_ref = None
         self.out_ptrs = ()   # data pointers of the node's OUTPUTS (render_colors, render_alphas): see _lease_pack_hook
+        self.pack: Optional["_Pack"] = None   # packed=True: the compaction record (set once the forward has returned)
 
 
 class _ReferenceLists:
@@ -987,6 +988,126 @@ def _settle_walk(s: dict, cfg: dict, render_colors: Tensor, render_alphas: Tenso
     return rows
 
 
+class _Pack:
+    """The compaction of a `packed=True` call: the inclusive scan of [pair flags C*N | seen flags N] and the two totals
+    the host read once -- nnz visible (camera, Gaussian) pairs, nu Gaussians some camera saw.  The pipeline is dense; this record turns
+    what the call hands out (meta, `.grad` / `.absgrad` of means2d, the sparse gradient rows) into gsplat's packed form."""
+    __slots__ = ("C", "N", "nnz", "nu", "incl", "sparse", "dev", "_ids")
+
+    def __init__(self, radii: Tensor, C: int, N: int, sparse: bool):
+        self.C, self.N, self.sparse, self.dev, self._ids = C, N, bool(sparse), radii.device, None
+        self.nnz = self.nu = 0
+        self.incl = None
+        if C * N == 0:   # (nothing to flag: the totals are known without the device)
+            return
+        L, dev = nat.lib(), self.dev
+        total = C * N + (N if sparse else 0)
+        i32 = dict(dtype=torch.int32, device=dev)
+        flags, self.incl = torch.empty((total,), **i32), torch.empty((total,), **i32)
+        scan_ws = torch.empty((int(L.gs_scan_rows_workspace_ints(1, total)),), **i32)
+        host = getattr(_tls, "pack_totals", None)
+        if host is None:   # (page-locked int64[2] per host thread: read before the call returns, so one is enough)
+            host = _tls.pack_totals = torch.zeros((2,), dtype=torch.int64, pin_memory=True)
+        host.fill_(-1)
+        stream = torch.cuda.current_stream(dev)
+        _stage("gs_pack_flags", dev, lambda: nat.check(L.gs_pack_flags(stream.cuda_stream, C, N, _ptr(radii), int(sparse), _ptr(flags), _ptr(self.incl),
+                                                                       _ptr(scan_ws), host.data_ptr()), "gs_pack_flags"))
+        # the one host read of the packing: page-locked memory behind an event, as the list-size check does -- the stream never drains
+        ev = torch.cuda.Event()
+        ev.record(stream)
+        t_wait = time.perf_counter_ns()
+        ev.synchronize()
+        with _state_lock:
+            stats["sync_wait_ns"] += time.perf_counter_ns() - t_wait
+        self.nnz, self.nu = (int(v) for v in host.tolist())
+        if not (0 <= self.nnz <= C * N and 0 <= self.nu <= N):
+            raise nat.NativeLibraryError(f"rasterization(packed=True): the totals record holds {(self.nnz, self.nu)} for C*N = {C * N}, N = {N}")
+
+    def take_pairs(self, dense: Tensor, words: int) -> Tensor:
+        """`dense` ([C,N] or [C,N,words], 32-bit elements) at the visible pairs: [nnz] or [nnz,words]."""
+        return self._take(dense, words, self.C * self.N, self.nnz, 0, 0, dense.dim() == 2)
+
+    def take_seen(self, dense: Tensor, words: int) -> Tensor:
+        """Rows of `dense` ([N,words] float32) of the Gaussians some camera saw: [nu,words]."""
+        return self._take(dense, words, self.N, self.nu, self.C * self.N, self.nnz, False)
+
+    def _take(self, dense, words, n_src, n_out, first, base, flat):
+        assert dense.is_contiguous() and dense.element_size() == 4 and dense.numel() == n_src * words, (dense.shape, dense.dtype, n_src, words)
+        out = torch.empty((n_out,) if flat else (n_out, words), dtype=dense.dtype, device=self.dev)
+        if n_out:
+            L, st = nat.lib(), _stream(self.dev)
+            _stage("gs_pack_take", self.dev, lambda: nat.check(L.gs_pack_take(st, n_src, n_out, words, self.incl.data_ptr() + 4 * first, base,
+                                                                              _ptr(dense), _ptr(out), None), "gs_pack_take"))
+        return out
+
+    def seen_ids(self) -> Tensor:
+        """int64 [nu]: the Gaussians some camera saw, ascending (built on first use, kept)."""
+        if self._ids is None:
+            ids = torch.empty((self.nu,), dtype=torch.int64, device=self.dev)
+            if self.nu:
+                L, st, pairs = nat.lib(), _stream(self.dev), self.C * self.N
+                _stage("gs_pack_take", self.dev, lambda: nat.check(L.gs_pack_take(st, self.N, self.nu, 1, self.incl.data_ptr() + 4 * pairs, self.nnz,
+                                                                                  None, None, _ptr(ids)), "gs_pack_take"))
+            self._ids = ids
+        return self._ids
+
+    def sparse_rows(self, dense: Tensor) -> Tensor:
+        """A dense [N,w] gradient as gsplat's sparse one: the rows of the seen Gaussians, ascending ids -- coalesced as it stands."""
+        return torch.sparse_coo_tensor(self.seen_ids()[None], self.take_seen(dense, dense.shape[1]), size=tuple(dense.shape), is_coalesced=True)
+
+    def remap(self, flatten_ids: Tensor) -> Tensor:
+        """The list's dense pair indices c*N + n as packed rows."""
+        out = torch.empty_like(flatten_ids)
+        if flatten_ids.numel():
+            L, st = nat.lib(), _stream(self.dev)
+            _stage("gs_pack_remap", self.dev, lambda: nat.check(L.gs_pack_remap(st, flatten_ids.numel(), self.C * self.N, _ptr(flatten_ids),
+                                                                                _ptr(self.incl), _ptr(out)), "gs_pack_remap"))
+        return out
+
+
+def _pack_meta(meta: "_LazyMeta", C: int, N: int, opacities: Tensor, sparse: bool) -> _Pack:
+    """Turns the dense meta of a finished forward into gsplat's packed one, in place: ids, radii, means2d, depths,
+    conics and opacities in one launch; the lazily built list arrays stay lazy -- their getters are wrapped (tiles_per_gauss
+    gathered, flatten_ids renumbered to packed rows; isect_offsets and isect_ids do not change: the latter is formed from
+    `depths[flatten_ids]`, which the renumbering leaves as it was)."""
+    L = nat.lib()
+    raw = lambda k: dict.__getitem__(meta, k)
+    radii, means2d, depths, conics = (raw(k) for k in ("radii", "means2d", "depths", "conics"))
+    dev = radii.device
+    with torch.no_grad():
+        pk = _Pack(radii, C, N, sparse)
+        nnz = pk.nnz
+        # [C,N] opacities exist where the projection formed one per camera (antialiased: opacity * rho); otherwise the [N] input
+        op = raw("opacities")
+        op_src, per_cam = (op.fn().contiguous(), 1) if isinstance(op, _LazyMeta.Lazy) else (opacities, 0)
+        out = {"camera_ids": torch.empty((nnz,), dtype=torch.int64, device=dev), "gaussian_ids": torch.empty((nnz,), dtype=torch.int64, device=dev),
+               "radii": torch.empty((nnz,), dtype=torch.int32, device=dev), "means2d": torch.empty((nnz, 2), dtype=torch.float32, device=dev),
+               "depths": torch.empty((nnz,), dtype=torch.float32, device=dev), "conics": torch.empty((nnz, 3), dtype=torch.float32, device=dev),
+               "opacities": torch.empty((nnz,), dtype=torch.float32, device=dev)}
+        if nnz:
+            st = _stream(dev)
+            _stage("gs_pack_gather", dev, lambda: nat.check(L.gs_pack_gather(
+                st, C, N, nnz, _ptr(radii), _ptr(pk.incl), _ptr(means2d), _ptr(depths), _ptr(conics), _ptr(op_src), per_cam,
+                _ptr(out["camera_ids"]), _ptr(out["gaussian_ids"]), _ptr(out["radii"]), _ptr(out["means2d"]), _ptr(out["depths"]),
+                _ptr(out["conics"]), _ptr(out["opacities"])), "gs_pack_gather"))
+    for k, v in out.items():
+        dict.__setitem__(meta, k, v)
+
+    def wrapped(key, fn):
+        inner = raw(key)
+        get = inner.fn if isinstance(inner, _LazyMeta.Lazy) else (lambda: inner)
+
+        def build():
+            dense = get()
+            with torch.cuda.device(dev), torch.no_grad():
+                return fn(dense)
+        dict.__setitem__(meta, key, _LazyMeta.Lazy(build))
+
+    wrapped("tiles_per_gauss", lambda t: pk.take_pairs(t.contiguous(), 1))
+    wrapped("flatten_ids", lambda f: pk.remap(f.contiguous()))
+    return pk
+
+
 class _Rasterize(torch.autograd.Function):
     """One autograd node for the whole path (P-fwd .. B-fwd | B-bwd .. P-bwd)."""
 
@@ -1052,6 +1173,26 @@ class _Rasterize(torch.autograd.Function):
                                    "repaired only now -- the loss and the upstream gradient of this backward were computed from unwritten "
                                    "memory.  Re-run the step (the capacities have been raised), or use the default immediate size check.")
             s["n_isects"], s["n_buckets"] = s["late"]["n_isects"], s["late"]["n_buckets"]
+        if N == 0 and s.get("wide") is None:
+            # no Gaussian: there is no walk for the blend backward to take (its entry point refuses the empty workspace slots); every
+            # gradient is empty, a camera gradient zero
+            z = lambda *shape: torch.zeros(shape, **f32)
+            pk, go, ni = holder.pack, holder.grad_out or {}, ctx.needs_input_grad
+            m2_out = holder.means2d_ref() if holder.means2d_ref is not None else None
+            if m2_out is not None:
+                m2_shape = (0, 2) if pk is not None else (C, 0, 2)
+                if holder.absgrad:
+                    m2_out.absgrad = z(*m2_shape)
+                if m2_out.requires_grad and m2_out.grad is None:
+                    m2_out.grad = z(*m2_shape)
+            geo = [z(0, 3), z(0, 4), z(0, 3)]
+            if pk is not None and pk.sparse:
+                geo = [pk.sparse_rows(v) for v in geo]
+            with_colors = not (factorised or s["dmode"] == "only")
+            return (*(g if (ni[i] and k not in go) else None for i, (g, k) in enumerate(zip(geo, ("means", "quats", "scales")))),
+                    z(0) if (ni[3] and "opacities" not in go) else None, z(*colors.shape) if (ni[4] and with_colors) else None,
+                    z(*colors_rest.shape) if (ctx.split and ni[5] and with_colors) else None,
+                    z(C, 4, 4) if ctx.camera_grads else None, None, None, None, None, z(C, 3) if (len(ni) > 11 and ni[11]) else None)
         P = lease.ptr
         n_rows = _settle_walk(s, cfg, render_colors, render_alphas)
         # scratch for the backward's fill classes (gs_raster.h; a caching-allocator block, re-used stream-ordered)
@@ -1201,7 +1342,11 @@ class _Rasterize(torch.autograd.Function):
             dbg.update(v_means2d=v_m2, v_conics=v_cn, v_colors_post=v_cp,
                        rows=acc[:n_rows] if (wide is not None and N > 0) else   # (D > 4: the chunks' geometry sums; colour quads zero)
                        lease.view(WS.ROWS, max(n_rows, 1) * nat.GS_ROW_FLOATS)[: n_rows * nat.GS_ROW_FLOATS].clone().view(-1, nat.GS_ROW_FLOATS))
+        pk = holder.pack
         if m2_out is not None:
+            if pk is not None:   # packed: meta["means2d"] is [nnz,2], and so is what is deposited on it (the dense tensors gathered)
+                v_abs = pk.take_pairs(v_abs, 2) if holder.absgrad else v_abs
+                v_m2 = pk.take_pairs(v_m2, 2) if (m2_out.requires_grad and v_m2 is not None) else v_m2
             if holder.absgrad:
                 m2_out.absgrad = v_abs
             if m2_out.requires_grad and v_m2 is not None:
@@ -1210,6 +1355,10 @@ class _Rasterize(torch.autograd.Function):
                 # requires grad (retain_grad() is then a no-op) and the node deposits the same quantity itself.
                 m2_out.grad = v_m2 if m2_out.grad is None else m2_out.grad + v_m2
         ni = ctx.needs_input_grad
+        if pk is not None and pk.sparse:
+            # sparse_grad: the rows of the Gaussians some camera saw (the totals were read in the forward: no host wait here); the
+            # projection backward has summed over the cameras in camera order, so one entry per Gaussian -- coalesced as it stands
+            v_means, v_quats, v_scales = (pk.sparse_rows(v) if ni[i] else v for i, v in enumerate((v_means, v_quats, v_scales)))
         return (v_means if (ni[0] and "means" not in go) else None, v_quats if (ni[1] and "quats" not in go) else None,
                 v_scales if (ni[2] and "scales" not in go) else None,
                 v_opac if (ni[3] and "opacities" not in go) else None, v_colors if (ni[4] and v_colors is not None) else None,
@@ -1342,8 +1491,31 @@ def rasterization(
     the render does -- `.grad` = dL/d means2d ([C,N,2]; gsplat: after `meta["means2d"].retain_grad()`, a no-op here);
     `meta["radii"]` is int32 [C,N] with `> 0` marking visible Gaussians.
 
-    Only the configuration the reference exercises is implemented natively; anything else raises
-    `NotImplementedError` instead of silently computing something different.
+    Every keyword of gsplat's signature is taken; what is still refused -- `tile_size != 16`, gradients w.r.t. `Ks`, SH degree > 4 --
+    raises `NotImplementedError` instead of silently computing something different.
+
+    `packed` (gsplat's keyword, default True as upstream; DESIGN.md 27, INTEGRATION.md "gsplat's default call").  The pipeline is the
+    dense one whatever the keyword says -- projection, lists, blend, both backward passes, the [C,N] intermediates in the workspace --
+    and packing is an interface step behind it: `render_colors`, `render_alphas` and every input gradient are bit for bit those of the
+    `packed=False` call.  With nnz the number of pairs (c, n) with `radii[c, n] > 0`, taken in row-major order (camera-major, Gaussian
+    ascending): `meta["camera_ids"]` / `["gaussian_ids"]` int64 [nnz]; `["radii"]` int32 [nnz], `["means2d"]` [nnz,2], `["depths"]`
+    [nnz], `["conics"]` [nnz,3], `["opacities"]` [nnz] (antialiased: opacity * rho; `_activations`: the logits) and
+    `["tiles_per_gauss"]` int32 [nnz] are the dense arrays at `[camera_ids, gaussian_ids]`; `["flatten_ids"]` holds the same entries
+    renumbered from c*N + n to the packed row; `["isect_ids"]` and `["isect_offsets"]` do not change; the list arrays are still built on
+    first read.  During backward `meta["means2d"]` receives `.grad` and (absgrad) `.absgrad` as [nnz,2].  nnz reaches the host in ONE
+    read of page-locked memory behind an event (the mechanism of the list-size check; no stream drain); nnz = 0 gives empty tensors.
+    `packed=False` launches exactly what it launched before the keyword existed.  gsplat's semantics as remembered from its source,
+    not checked against a run of it.  HIP tensors only (`NotImplementedError` on CPU tensors); not together with
+    `_sh_grads="colors_pre"`, `_grad_out` or `_view_payload` (`ValueError`: the view-parallel record is dense).
+
+    `sparse_grad=True` (needs `packed=True`): the gradients of `means`, `quats` and `scales` are `torch.sparse_coo_tensor`s -- indices
+    [1,nu] int64, the ascending ids of the Gaussians some camera saw; values [nu,3|4|3], those rows of the dense gradient bit for bit;
+    `.to_dense()` is the dense call's gradient (a Gaussian no camera saw has a zero row there).  gsplat hands out one uncoalesced entry
+    per (camera, Gaussian) pair; here the projection backward has already summed over the cameras in camera order, so the tensor is
+    coalesced as it stands (`torch.autograd.grad` returns it so; `.backward()` leaves a copy in `.grad` whose flag torch clears).
+    The gradients of `opacities`, `colors`, a `(sh_0, sh_rest)` pair and `viewmats` stay dense, as in gsplat.  nu is read in the
+    forward, with nnz; the backward adds no host wait.  Pair it with `torch.optim.SparseAdam`; `optim.FusedAdam.step()` refuses a
+    sparse `.grad` (`TypeError`) -- its own way to the same end is `step(visible=meta["radii"])` on a dense call.
 
     `_tile_culling="gsplat"` (default): `meta["tiles_per_gauss"]`, `["isect_ids"]`, `["flatten_ids"]`, `["isect_offsets"]` are
     bit-for-bit gsplat's -- built when one of them is first read (`_ReferenceLists`): they are a function of the 3-sigma tile
@@ -1455,7 +1627,12 @@ def rasterization(
     if backgrounds is not None:
         assert backgrounds.shape == (C, 3 if sh_degree is not None else colors.shape[-1]), backgrounds.shape
     if packed:
-        raise NotImplementedError("packed=True is not implemented (the reference passes packed=False)")
+        if _sh_grads == "colors_pre" or _grad_out is not None or _view_payload is not None:
+            raise ValueError("packed=True cannot be combined with _sh_grads='colors_pre', _grad_out or _view_payload "
+                             "(the view-parallel record is dense: pass packed=False)")
+        if not means.is_cuda:   # (a NotImplementedError, as for the depth modes: callers that probed for the keyword keep their handler)
+            raise NotImplementedError("packed=True runs on the GPU only: tensors must live on a HIP device "
+                                      "(there is no CPU fallback in this package)")
     depth = {"RGB": None, "D": "only", "ED": "only", "RGB+D": "append", "RGB+ED": "append"}[render_mode]
     if depth == "append" and sh_degree is None and colors.shape[-1] + 1 > 4:
         raise NotImplementedError(f"colour features of at most 4 channels are implemented on the HIP path (got {colors.shape[-1]} plus "
@@ -1482,7 +1659,7 @@ def rasterization(
                                       "(there is no CPU fallback in this package)")
     if tile_size != _TILE:
         raise NotImplementedError(f"only tile_size={_TILE} is implemented")
-    if sparse_grad:
+    if sparse_grad and not packed:
         raise NotImplementedError("sparse_grad requires packed=True")
     if Ks.requires_grad:
         raise NotImplementedError("gradients w.r.t. Ks are not implemented (gsplat 1.0.0 has no v_Ks either)")
@@ -1538,6 +1715,10 @@ def rasterization(
         cfg["camera_model"] = CAMERA_MODELS[camera_model]
     if rasterize_mode == "antialiased":   # (likewise: the classic call's cfg carries no key for the mode)
         cfg["antialiased"] = True
+    if packed:   # (likewise: the dense call's cfg carries neither key)
+        cfg["packed"] = True
+        if sparse_grad:
+            cfg["sparse_grad"] = True
     if _sh_grads not in ("dense", "colors_pre") or (_sh_grads == "colors_pre" and sh_degree is None):
         raise ValueError("_sh_grads: 'dense', or 'colors_pre' together with sh_degree")
     holder = _Holder(absgrad)
@@ -1558,6 +1739,9 @@ def rasterization(
     holder.lease_ref = None   # (held by the saved tensors now, if anything was saved)
     meta = holder.meta
     holder.meta = {}
+    if packed:   # an interface step behind the dense pipeline: meta in gsplat's packed form, and the record the backward gathers by
+        with torch.cuda.device(means.device):
+            holder.pack = _pack_meta(meta, C, N, opac_c, bool(sparse_grad))
     if render_colors.requires_grad:
         meta["means2d"].requires_grad_(True)   # (gsplat's graph tensor: `.retain_grad()` / `.grad` work, see backward)
     holder.means2d_ref = weakref.ref(meta["means2d"])

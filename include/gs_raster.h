@@ -1217,6 +1217,35 @@ int gs_project_bwd_adam_reg_aa(void* stream, int64_t N, int K, int sh_degree, fl
                                const float* hyper_dev, int64_t* applied_dev, float* max_radii, float* grad_norm_accum, float* counts,
                                const float* sh_jac, float max_ratio, float lambda);
 
+/* Packed meta and sparse gradient rows (rasterization(packed=True, sparse_grad=True)).  The pipeline stays dense;
+ * these compact what a call hands out.  The visible pairs are the (c, n) with radii[c][n] > 0 in row-major order (camera-major,
+ * Gaussian ascending); the seen Gaussians are the n some camera saw, ascending.  Eager-path kernels: the step guard does not
+ * apply.  C*N + N < 2^31.  No atomics; every store is checked against the totals.
+ * gs_pack_flags: flags[C*N (+ N)] (0/1) = the pair flags and -- want_seen -- behind them the seen flags; incl = the inclusive
+ *   scan of flags taken as ONE row (gs_scan_rows_i32; scan_workspace: gs_scan_rows_workspace_ints(1, C*N (+ N)) int32), so
+ *   incl[i] - 1 is the packed row of visible pair i and incl[C*N + n] - nnz - 1 the rank of seen Gaussian n.  Its last kernel
+ *   writes {nnz, nu} (nu = 0 without want_seen) to totals_host_mapped -- int64[2] of page-locked, device-addressable host
+ *   memory -- followed by a system-scope fence: a caller that records an event behind the call and waits for it reads both from
+ *   plain memory.  C >= 1, N >= 1.
+ * gs_pack_gather: one launch; camera_ids / gaussian_ids (int64 [nnz]), radii_out [nnz], means2d_out [nnz][2], depths_out [nnz],
+ *   conics_out [nnz][3], opacities_out [nnz] = the dense arrays at the visible pairs.  opacities is [N] (broadcast over the
+ *   cameras) or, opacities_per_camera != 0, [C][N].  nnz as gs_pack_flags reported it.
+ * gs_pack_take: rows of `words` (1..4) 32-bit words: out[incl[i] - base - 1][:] = src[i][:] for every i < n_src at which the
+ *   scan steps (incl[i] > incl[i-1]; incl[-1] = base), ids_out[...] = i (int64; either of {src, out} / ids_out may be NULL).
+ *   Pairs: incl, base 0, n_src C*N, n_out nnz.  Seen Gaussians: incl + C*N, base nnz, n_src N, n_out nu.  Rows are aligned to
+ *   4, 8, 4, 16 bytes.
+ * gs_pack_remap: out[i] = incl[flatten_ids[i]] - 1, the packed row of the listed pair (every listed entry is a visible pair;
+ *   an index outside [0, pairs) yields -1 instead of a read). */
+int gs_pack_flags(void* stream, int C, int64_t N, const int32_t* radii, int want_seen, int32_t* flags, int32_t* incl,
+                  int32_t* scan_workspace, int64_t* totals_host_mapped);
+int gs_pack_gather(void* stream, int C, int64_t N, int64_t nnz, const int32_t* radii, const int32_t* incl, const float* means2d,
+                   const float* depths, const float* conics, const float* opacities, int opacities_per_camera,
+                   int64_t* camera_ids, int64_t* gaussian_ids, int32_t* radii_out, float* means2d_out, float* depths_out,
+                   float* conics_out, float* opacities_out);
+int gs_pack_take(void* stream, int64_t n_src, int64_t n_out, int words, const int32_t* incl, int32_t base, const void* src,
+                 void* out, int64_t* ids_out);
+int gs_pack_remap(void* stream, int64_t n, int64_t pairs, const int32_t* flatten_ids, const int32_t* incl, int32_t* out);
+
 #ifdef __cplusplus
 }
 #endif
