@@ -40,7 +40,7 @@
 // Semantics: SURVEY.md Appendix A.4 / A.5 (gsplat 1.0.0 rasterize_to_pixels fwd/bwd).
 #include <algorithm>
 
-#include "gs_common.h"
+#include "gs_blend_shared.h"
 #include "gs_math.h"
 
 namespace gs {
@@ -63,9 +63,7 @@ static BwdCheck g_bwd_check = {nullptr, nullptr, nullptr, nullptr};
 #define GS_IF_CHECK(...)
 #endif
 
-// Work unit of the backward: kUnit consecutive entries of one quadrant sublist (half a 64-entry bucket), with a
-// checkpoint of the quadrant's 64 pixel states in front of it.
-constexpr int kUnit = GS_UNIT;
+// (kUnit -- the work unit of the backward -- and the words of the walk state: gs_blend_shared.h)
 // Storage units a tile takes from its range's counter at a time (one returning atomic per kChunk work units; what a tile
 // leaves unused of its last chunk costs memory only -- the work-unit descriptors are published densely, see unit log).
 // Round 6, same box, blend_fwd stage at 1 M / 1080p: ONE counter for all tiles, chunks of 8 / 32 / 64: 0.47 / 0.395 / 0.398 ms
@@ -74,9 +72,6 @@ constexpr int kChunk = 8;
 // Work units a tile-wave has opened and not yet published, in LDS: (storage unit, position in the sublist * 4 + quadrant).
 // Published -- one atomic for the lot, descriptors dense in launch order -- when the log fills up and at the end of the tile.
 constexpr int kUnitLog = 128;
-// words of the walk state (include/gs_raster.h: GS_WALK_*)
-constexpr int kWalkUnits = GS_WALK_UNITS, kWalkStorage = GS_WALK_STORAGE, kWalkRows = GS_WALK_ROWS,
-              kWalkFlags = GS_WALK_FLAGS, kWalkSkip = GS_WALK_SKIP;
 constexpr int kScanThreads = 256, kScanPerThread = 32, kScanChunk = kScanThreads * kScanPerThread;   // 8192 slots per block
 
 struct BlendFwdArgs {
@@ -125,15 +120,7 @@ struct ClockProbe {
 #define GS_CLOCK_PROBE_SCOPE(slot)
 #endif
 
-// -DGS_EXACT_MATH (tools/acc64_ab.py; never in the product build): correctly rounded exp2 and division in BOTH blend kernels
-// instead of the hardware approximations (v_exp_f32 / v_rcp_f32: ~1 ulp) -- the other half of the A/B on rows that cancel.
-#ifdef GS_EXACT_MATH
-__device__ __forceinline__ float fast_exp2(float x) { return (float)exp2((double)x); }
-__device__ __forceinline__ float fast_rcp(float x) { return (float)(1.0 / (double)x); }
-#else
-__device__ __forceinline__ float fast_exp2(float x) { return __builtin_amdgcn_exp2f(x); }
-__device__ __forceinline__ float fast_rcp(float x) { return __builtin_amdgcn_rcpf(x); }
-#endif
+// (fast_exp2 / fast_rcp, with their -DGS_EXACT_MATH forms: gs_blend_shared.h)
 
 // One (pixel, Gaussian) pair of the forward (alpha and the take-it test come from the caller, which
 // skips entries no pixel takes); straight-line, predicated.  The entry's alpha is
@@ -646,20 +633,7 @@ struct BlendBwdArgs {
     GS_IF_CHECK(BwdCheck chk;)
 };
 
-constexpr int kBwdWaves = 4;
-constexpr int kPipeLanes = 8;                       // lanes per systolic pipeline (two pipelines share a 16-lane DPP row)
-constexpr int kPerLane = kUnit / kPipeLanes;        // 4 entries per lane in a full unit (bwd_wave<E>: E = 1 .. 4)
-static_assert(kPerLane == 4, "bwd_wave is instantiated for 1 .. 4 entries per lane");
-constexpr int kUnitsPerWave = 64 / kPipeLanes;      // 8
-// (Round 5 bounded half-quadrant -- 8 x 4 pixel -- work units with a timing build: -15 to -23 us for this kernel at the 1.55 x
-//  unit count they would have, before twice the rows in the row sum; not built.  HISTORY.md, profiles/r05_halfq_bound.txt.)
-constexpr int kUnitPixels = 64;
-constexpr int kBwdSteps = kUnitPixels + kPipeLanes - 1;      // 71
-
-__device__ __forceinline__ float dpp_row_shr1(float v) {
-    // lane r of each 16-lane row receives lane r-1's value; lane 0 keeps its own
-    return __builtin_bit_cast(float, __builtin_amdgcn_update_dpp(__builtin_bit_cast(int, v), __builtin_bit_cast(int, v), 0x111, 0xf, 0xf, false));
-}
+// (the shape of the backward's pipelines -- kBwdWaves, kPipeLanes, kUnitsPerWave, kBwdSteps -- and dpp_row_shr1: gs_blend_shared.h)
 
 // per pixel in LDS: float4 (v_r, v_g, v_b, E) and float2 (checkpoint T, P = checkpoint colour . v) in two arrays
 // (24 B; the pixel centre is recomputed from the pixel index)
@@ -885,7 +859,7 @@ __device__ __forceinline__ void bwd_wave(const BlendBwdArgs& a, const int4 ud, c
 // in regions of cls_cap descriptors (a frame has at most one tail per quadrant sublist: 4 C tiles).  One atomic per block and
 // class (a returning same-address atomic per WAVE cost 0.19 ms at 31 k waves, HISTORY.md); the order inside a class is whatever
 // the blocks' atomics make it -- every unit writes rows of its own, no result depends on it.  .w = the unit's published index.
-constexpr int kClsHdrInts = 16, kClsThreads = 1024;
+constexpr int kClsThreads = 1024;   // (kClsHdrInts: gs_blend_shared.h)
 __global__ __launch_bounds__(64) void unit_classes_clear_kernel(int32_t* __restrict__ hdr) {
     if (threadIdx.x < kClsHdrInts) hdr[threadIdx.x] = 0;
 }
@@ -1110,10 +1084,23 @@ extern "C" int gs_blend_fwd_ch(void* stream, int C, int width, int height, int c
 }
 
 // descriptors a tail region holds: one tail per quadrant sublist at most, rounded up to whole blocks of the backward
-static int64_t cls_region(int C, int width, int height) {
+int64_t gs::unit_class_region(int C, int width, int height) {
     const int64_t tiles = (int64_t)((width + GS_TILE - 1) / GS_TILE) * ((height + GS_TILE - 1) / GS_TILE);
     const int64_t per_block = kBwdWaves * kUnitsPerWave;
     return (4 * (int64_t)C * tiles + per_block - 1) / per_block * per_block;
+}
+static int64_t cls_region(int C, int width, int height) { return unit_class_region(C, width, height); }
+
+// (the counters are cleared by a launch, not by hipMemsetAsync: inside a captured step a memset node ahead of the kernel
+//  that counts ended in GPU memory faults on this ROCm -- the eager sequence of the same calls did not)
+int gs::unit_classes_launch(hipStream_t st, const int32_t* walk_state, const int4* unit_desc, const int32_t* qcnt, int cap_units,
+                            int cls_cap, int32_t* unit_classes, const int64_t* guard) {
+    hipLaunchKernelGGL(unit_classes_clear_kernel, dim3(1), dim3(64), 0, st, unit_classes);
+    hipLaunchKernelGGL(unit_classes_kernel, dim3((unsigned)((cap_units + kClsThreads - 1) / kClsThreads)), dim3(kClsThreads), 0, st,
+                       walk_state, unit_desc, qcnt, cap_units, cls_cap, unit_classes, reinterpret_cast<int4*>(unit_classes + kClsHdrInts),
+                       guard);
+    GS_LAUNCH_CHECK("unit_classes_kernel");
+    return GS_OK;
 }
 
 extern "C" size_t gs_unit_classes_ints(int64_t cap_units, int C, int width, int height) {
@@ -1153,13 +1140,8 @@ static int blend_bwd_launch(void* stream, int C, int width, int height, const fl
         GS_REQUIRE(((uintptr_t)unit_classes & 15) == 0, "unit_classes must be 16-byte aligned");
         a.cls_hdr = unit_classes; a.cls_desc = reinterpret_cast<const int4*>(unit_classes + kClsHdrInts);
         a.cls_cap = (int)cls_region(C, width, height);
-        // (the counters are cleared by a launch, not by hipMemsetAsync: inside a captured step a memset node ahead of the kernel
-        //  that counts ended in GPU memory faults on this ROCm -- the eager sequence of the same calls did not)
-        hipLaunchKernelGGL(unit_classes_clear_kernel, dim3(1), dim3(64), 0, (hipStream_t)stream, unit_classes);
-        hipLaunchKernelGGL(unit_classes_kernel, dim3((unsigned)((cap_units + kClsThreads - 1) / kClsThreads)), dim3(kClsThreads), 0, (hipStream_t)stream,
-                           walk_state, a.unit_desc, qcnt, (int)cap_units, a.cls_cap, unit_classes, reinterpret_cast<int4*>(unit_classes + kClsHdrInts),
-                           a.guard);
-        GS_LAUNCH_CHECK("unit_classes_kernel");
+        const int rc = unit_classes_launch((hipStream_t)stream, walk_state, a.unit_desc, qcnt, (int)cap_units, a.cls_cap, unit_classes, a.guard);
+        if (rc != GS_OK) return rc;
         grid += 3u * (unsigned)(a.cls_cap / (kUnitsPerWave * kBwdWaves));
     }
     if constexpr (NC == 3) hipLaunchKernelGGL(blend_bwd_kernel, dim3(grid), dim3(kBwdWaves * 64), 0, (hipStream_t)stream, a);

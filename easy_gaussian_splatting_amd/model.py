@@ -400,6 +400,73 @@ class GaussianModel(nn.Module):
                 "train/nbr_gaussians": n, "n_before": n_old}
 
     @torch.no_grad()
+    def prune(self, mask: Tensor) -> Dict[str, Any]:
+        """Removes the Gaussians flagged in `mask` (bool [N], True = drop; e.g. `importance.prune_mask`) from all six parameters and
+        both Adam moments.  Survivors keep their parameters, moments and the three statistics buffers (`grad_norm_accum`,
+        `collecting_counts`, `max_radii`) bit for bit and in their original order.  With optim.FusedAdam on the GPU it is the device
+        path of `densify_and_prune` with no children and no clones -- a keep-flag row through `gs_scan_rows_i32` + `gs_refine_apply`,
+        then `adopt_flat`; the one host read is the new size --, otherwise the torch path through `_replace_parameters`.  A captured
+        step runner re-captures on its next step, as after `densify_and_prune`.  Single process only."""
+        if is_distributed():
+            raise RuntimeError("GaussianModel.prune: single-process only (replicas would have to agree on the mask; pruning by "
+                               "contribution under view-parallel training is not implemented)")
+        if self.optimizer is None:
+            raise RuntimeError("optimizer has not been registered")
+        dev, n_old = self.means.device, self.nbr_gaussians
+        mask = torch.as_tensor(mask, device=dev)
+        if mask.dtype != torch.bool or mask.shape != (n_old,):
+            raise ValueError(f"GaussianModel.prune: mask must be a bool tensor of shape ({n_old},), got {mask.dtype} {tuple(mask.shape)}")
+        opt = self.optimizer
+        if self.means.is_cuda and hasattr(opt, "adopt_flat") and getattr(self, "device_refine", True):
+            import ctypes as ct
+            from . import _native as nat
+            from .optim import FusedAdam
+            L, K = nat.lib(), 1 + self.sh_rest.shape[1]
+            st = torch.cuda.current_stream(dev).cuda_stream
+            flags = torch.zeros((3, n_old), dtype=torch.int32, device=dev)   # rows: survives | split (none) | cloned (none)
+            flags[0] = (~mask).to(torch.int32)
+            with torch.cuda.device(dev):
+                incl = torch.empty_like(flags)
+                scan_ws = torch.empty((int(L.gs_scan_rows_workspace_ints(3, n_old)),), dtype=torch.int32, device=dev)
+                nat.check(L.gs_scan_rows_i32(st, 3, n_old, flags.data_ptr(), incl.data_ptr(), scan_ws.data_ptr()), "gs_scan_rows_i32")
+                n_new = int(incl[0, -1]) if n_old else 0   # the one host read: it sizes the new buffers
+                widths = [3, 3, 4, 3, 3 * (K - 1), 1]
+                old_offs = list(opt._offs)
+                new_offs, new_ends, total = FusedAdam.flat_layout([n_new * w for w in widths])
+                f32 = dict(dtype=torch.float32, device=dev)
+                new_p, new_m, new_v = torch.empty(total, **f32), torch.empty(total, **f32), torch.empty(total, **f32)
+                for o, w, e in zip(new_offs, widths, new_ends):   # the (<= 3 float) pads between segments
+                    if e > o + n_new * w:
+                        for buf in (new_p, new_m, new_v):
+                            buf[o + n_new * w:e].zero_()
+                src = torch.empty((max(n_new, 1),), dtype=torch.int32, device=dev)
+                tag = torch.empty((max(n_new, 1),), dtype=torch.int8, device=dev)
+                nat.check(L.gs_refine_apply(st, n_old, 1, K, flags.data_ptr(), incl.data_ptr(), n_new, 0, 0, None,
+                                            opt.flat_param.data_ptr(), opt.exp_avg.data_ptr(), opt.exp_avg_sq.data_ptr(),
+                                            (ct.c_int64 * 6)(*old_offs), new_p.data_ptr(), new_m.data_ptr(), new_v.data_ptr(),
+                                            (ct.c_int64 * 6)(*new_offs), src.data_ptr(), tag.data_ptr()), "gs_refine_apply")
+            keep_idx = src[:n_new].to(torch.int64)   # (the survivors' old indices, ascending: what the gather went by)
+            shapes = {"means": (n_new, 3), "log_scales": (n_new, 3), "quats": (n_new, 4), "sh_0": (n_new, 1, 3),
+                      "sh_rest": (n_new, K - 1, 3), "logit_opacities": (n_new,)}
+            new_params = []
+            for name, o, w in zip(self.param_names, new_offs, widths):
+                setattr(self, name, nn.Parameter(new_p[o:o + n_new * w].view(shapes[name])))
+                new_params.append(getattr(self, name))
+            opt.adopt_flat(new_p, new_m, new_v, new_params)
+        else:
+            keep_idx = torch.nonzero(~mask).squeeze(1)   # the one host read
+            n_new = keep_idx.numel()
+            new, new_m, new_v = {}, {}, {}
+            for name in self.param_names:
+                m, v = self._moments(name)
+                new[name], new_m[name], new_v[name] = getattr(self, name).detach()[keep_idx], m[keep_idx], v[keep_idx]
+            self._replace_parameters(new, new_m, new_v)
+        self.grad_norm_accum = self.grad_norm_accum[keep_idx]
+        self.collecting_counts = self.collecting_counts[keep_idx]
+        self.max_radii = self.max_radii[keep_idx]
+        return {"pruned": n_old - n_new, "n_before": n_old, "train/nbr_gaussians": n_new}
+
+    @torch.no_grad()
     def reset_opacities(self):
         """opacity <- min(opacity / 2, 2 * MIN_OPACITY); the group's Adam moments restart at zero
         (/root/reference/model/gaussian.py:130-146)."""

@@ -1746,3 +1746,99 @@ def rasterization(
         meta["means2d"].requires_grad_(True)   # (gsplat's graph tensor: `.retain_grad()` / `.grad` work, see backward)
     holder.means2d_ref = weakref.ref(meta["means2d"])
     return render_colors, render_alphas, meta
+
+
+def blend_weights(
+    means: Tensor,  # [N, 3]
+    quats: Tensor,  # [N, 4]
+    scales: Tensor,  # [N, 3]
+    opacities: Tensor,  # [N]
+    viewmats: Tensor,  # [C, 4, 4]
+    Ks: Tensor,  # [C, 3, 3]
+    width: int,
+    height: int,
+    *,
+    near_plane: float = 0.01,
+    far_plane: float = 1e10,
+    radius_clip: float = 0.0,
+    eps2d: float = 0.3,
+    rasterize_mode: str = "classic",
+    camera_model: str = "pinhole",
+    _activations: str = "none",
+    _tile_culling: str = "gsplat",
+) -> Dict[str, Tensor]:
+    """How much every Gaussian contributed to the images of `viewmats` / `Ks` (INTEGRATION.md "Pruning by contribution").
+
+    The blend TAKES the pair (pixel, Gaussian) when the pixel is live, sigma >= 0, alpha = min(0.999, opacity * exp(-sigma)) >= 1/255
+    and T' = fma(-alpha, T, T) > 1e-4 -- `opacity` being what the blend sees: opacity * rho in the antialiased mode, the activated value
+    under `_activations="exp_sigmoid"` -- and a taken pair has the weight w = alpha * T.  Returns
+    `{"weight_sum": f32 [C,N], "weight_max": f32 [C,N], "hits": i32 [C,N], "radii": i32 [C,N]}`: per camera and Gaussian the sum and
+    the maximum of w over the taken pixels and their number; all three exactly zero for a Gaussian with `radii <= 0` and for one that is
+    listed but never taken.  `hits` and `weight_max` are those of the pixels `rasterization()` blends, bit for bit, in every
+    `_tile_culling` mode; `weight_sum` is an fp32 sum in a fixed order (two calls agree bit for bit).
+
+    No colours are taken and none are evaluated: the projection runs as the depth-only render mode runs it, the blend as a one-channel
+    training-mode forward in one depth round (its walk is what `gs_blend_scores` replays), on the workspace lease of the (device,
+    stream) with the size check and overflow repeat of a training forward.  No autograd: the outputs never require grad.  The keywords
+    mean what they mean in `rasterization()`; an unknown name raises `ValueError`, the antialiased mode with another camera than
+    the pinhole and CPU tensors `NotImplementedError`."""
+    N, C = means.shape[0], viewmats.shape[0]
+    assert means.shape == (N, 3) and quats.shape == (N, 4) and scales.shape == (N, 3) and opacities.shape == (N,), "means / quats / scales / opacities"
+    assert viewmats.shape == (C, 4, 4) and Ks.shape == (C, 3, 3), "viewmats [C,4,4], Ks [C,3,3]"
+    if camera_model not in CAMERA_MODELS:
+        raise ValueError(f"camera_model: one of {sorted(CAMERA_MODELS)} (got {camera_model!r})")
+    if rasterize_mode not in RASTERIZE_MODES:
+        raise ValueError(f"rasterize_mode: one of {sorted(RASTERIZE_MODES)} (got {rasterize_mode!r})")
+    if _activations not in ("none", "exp_sigmoid"):
+        raise ValueError(f"_activations: 'none' or 'exp_sigmoid' (got {_activations!r})")
+    if _tile_culling not in ("gsplat", "tight", "gsplat_eager"):
+        raise ValueError(f"_tile_culling: 'gsplat', 'tight' or 'gsplat_eager' (got {_tile_culling!r})")
+    if rasterize_mode == "antialiased" and camera_model != "pinhole":
+        raise NotImplementedError(f"rasterize_mode='antialiased' with camera_model={camera_model!r}: the antialiased projection kernels "
+                                  "exist for the pinhole model only")
+    if not means.is_cuda:
+        raise NotImplementedError("blend_weights() runs on the GPU only: tensors must live on a HIP device "
+                                  "(there is no CPU fallback in this package)")
+    L = nat.lib()
+    dev = means.device
+
+    def prep(t: Tensor) -> Tensor:
+        if t.dtype != torch.float32:
+            raise TypeError(f"expected float32 tensors, got {t.dtype}")
+        if t.device != dev:
+            raise RuntimeError("all tensors must be on the same device")
+        return t.detach().contiguous()
+
+    means_c, quats_c, scales_c, opac_c, viewmats_c, Ks_c = map(prep, (means, quats, scales, opacities, viewmats, Ks))
+    W, H = int(width), int(height)
+    # the depth-only render mode's call shape (geometry-only projection, the depth as the record's one channel), as a training forward:
+    # "gsplat" and "tight" walk the same lists (the reference list arrays of "gsplat" are meta's business, and there is no meta here)
+    cfg = dict(width=W, height=H, near_plane=float(near_plane), far_plane=float(far_plane), radius_clip=float(radius_clip),
+               eps2d=float(eps2d), sh_degree=None, tile_culling={"gsplat": 1, "tight": 1, "gsplat_eager": 0}[_tile_culling],
+               lazy_ref_lists=False, sh_grads="dense", activations={"none": 0, "exp_sigmoid": 1}[_activations], grad_enabled=True,
+               defer_size_check=False, rounds="off", depth="only", expected_depth=False, camera_grads=False)
+    if camera_model != "pinhole":
+        cfg["camera_model"] = CAMERA_MODELS[camera_model]
+    if rasterize_mode == "antialiased":
+        cfg["antialiased"] = True
+    out = {"weight_sum": torch.zeros((C, N), dtype=torch.float32, device=dev), "weight_max": torch.zeros((C, N), dtype=torch.float32, device=dev),
+           "hits": torch.zeros((C, N), dtype=torch.int32, device=dev)}
+    flush_size_checks()
+    with torch.no_grad(), torch.cuda.device(dev):
+        # (`colors`: never read -- the depth-only mode evaluates none; the means stand in for an [N,3] tensor)
+        img, alphas, meta, s = _forward_stages(means_c, quats_c, scales_c, opac_c, means_c, None, viewmats_c, Ks_c, None, cfg, True)
+        out["radii"] = s["radii"]
+        if N > 0:
+            lease = s["lease"]   # (kept leased by s["lease_ref"] until this function returns)
+            _settle_walk(s, cfg, img, alphas)
+            st, P, lay = _stream(dev), lease.ptr, lease.layout
+            ucls = torch.empty((int(L.gs_unit_classes_ints(lay.cap_units, C, W, H)),), dtype=torch.int32, device=dev) if _BWD_CLASSES else None
+            # the score rows (4 floats) live in the rows region of the lease (12 floats per row of the same cap_rows)
+            _stage("gs_blend_scores", dev, lambda: nat.check(L.gs_blend_scores(
+                st, C, W, H, P(WS.REC), P(WS.QLIST), P(WS.QCNT), P(WS.UNIT_DESC), lay.cap_units, P(WS.CKPT), P(WS.QMASK), P(WS.ROW_BASE),
+                P(WS.WALK_STATE), P(WS.ROWS), lay.cap_rows, _ptr(ucls)), "gs_blend_scores"))
+            _stage("gs_score_reduce", dev, lambda: nat.check(L.gs_score_reduce(
+                st, C, N, _ptr(s["radii"]), P(WS.TILES_PER_GAUSS), P(WS.CUM_TILES), P(WS.ROWS), lay.cap_rows, P(WS.ROW_BASE), P(WS.QMASK),
+                P(WS.WALK_STATE), _ptr(out["weight_sum"]), _ptr(out["weight_max"]), _ptr(out["hits"])), "gs_score_reduce"))
+        del meta, s
+    return out

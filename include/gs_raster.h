@@ -1246,6 +1246,37 @@ int gs_pack_take(void* stream, int64_t n_src, int64_t n_out, int words, const in
                  void* out, int64_t* ids_out);
 int gs_pack_remap(void* stream, int64_t n, int64_t pairs, const int32_t* flatten_ids, const int32_t* incl, int32_t* out);
 
+/* Blend-weight scores (rendering.blend_weights, importance.py): how much each Gaussian contributed to an image.  The
+ * blend TAKES the pair (pixel p, Gaussian n) of camera c when the pixel is live, sigma >= 0, alpha = min(0.999, opacity exp(-sigma))
+ * >= 1/255 and T' = fma(-alpha, T, T) > 1e-4 (opacity: what the blend record holds); a taken pair has the weight w = alpha T.
+ * Per (c, n): weight_sum = the sum of w over the taken pixels, weight_max = their maximum (0: none), hits = their number.
+ * A call sequence: a training-mode gs_blend_fwd / gs_blend_fwd_ch (any channel count; one depth round), gs_blend_scores,
+ * gs_score_reduce [, gs_score_accumulate].  No atomics anywhere: two runs agree bit for bit.
+ * gs_blend_scores: replays the walk the forward left (qlist, qcnt, unit_desc, the T plane of ckpt, qmask, row_base, walk_state)
+ *   through the work-unit pipelines of gs_blend_bwd -- unit_classes as there: may be NULL -- and evaluates sigma, alpha, w and T' with
+ *   the backward's (= the forward's) instruction sequence: the taken set and every w are the forward's bit for bit.  It reads neither
+ *   an image nor a colour.  Writes one 4-float row (weight sum, weight max, taken pixels as int32, 0) per (intersection, quadrant)
+ *   some pixel took into score_rows[cap_rows*4], at the index of the pair's gradient row (row_base[slot] + rank of the quadrant) --
+ *   the rows region gs_blend_bwd writes (cap_rows*12 floats) holds them.  Nothing is written when the step guard is tripped or
+ *   the walk is void (GS_FLAG_UNITS / GS_FLAG_ROWS in walk_state[GS_WALK_FLAGS]).  16-byte aligned: rec, qlist, unit_desc, ckpt,
+ *   qmask, score_rows, unit_classes.
+ * gs_score_reduce: weight_sum / weight_max (f32) and hits (i32), each [C*N] and fully written: the rows of every Gaussian gathered
+ *   as gs_channel_grads gathers them and folded in a fixed order; zeros for culled Gaussians (radii <= 0), Gaussians without rows
+ *   and a void walk.  Honours the step guard.
+ * gs_score_accumulate: one launch; folds a [C*N] triple and radii into per-Gaussian running totals, the cameras in order:
+ *   total_weight_sum f64 [N] += weight_sum; total_weight_max f32 [N] = max; total_hits i64 [N] += hits; views_seen i32 [N] +=
+ *   (radii > 0); views_hit i32 [N] += (hits > 0).  Honours the step guard. */
+int gs_blend_scores(void* stream, int C, int width, int height, const float* rec, const int32_t* qlist,
+                    const int32_t* qcnt, const int32_t* unit_desc, int64_t cap_units, const float* ckpt,
+                    const uint8_t* qmask, const int32_t* row_base, const int32_t* walk_state, float* score_rows,
+                    int64_t cap_rows, int32_t* unit_classes);
+int gs_score_reduce(void* stream, int C, int64_t N, const int32_t* radii, const int32_t* tiles_per_gauss,
+                    const int32_t* cum_tiles, const float* score_rows, int64_t cap_rows, const int32_t* row_base,
+                    const uint8_t* qmask, const int32_t* walk_state, float* weight_sum, float* weight_max, int32_t* hits);
+int gs_score_accumulate(void* stream, int C, int64_t N, const float* weight_sum, const float* weight_max,
+                        const int32_t* hits, const int32_t* radii, double* total_weight_sum, float* total_weight_max,
+                        int64_t* total_hits, int32_t* views_seen, int32_t* views_hit);
+
 #ifdef __cplusplus
 }
 #endif
