@@ -181,3 +181,101 @@ def load_camera_states(path: Path) -> List[CameraState]:
             K = np.array([[cam["fx"], 0, cam["width"] / 2], [0, cam["fy"], cam["height"] / 2], [0, 0, 1]], dtype=np.float32)
             camera_states.append(CameraState(np.linalg.inv(c2w), K, cam["width"], cam["height"]))
     return camera_states
+
+
+# ---- the INRIA point_cloud.ply ----
+
+_PLY_REST_COUNTS = {0: 0, 9: 1, 24: 2, 45: 3, 72: 4}   # f_rest properties -> SH degree: 3 ((deg + 1)^2 - 1)
+
+
+def ply_properties(sh_degree: int) -> List[str]:
+    """The property names of the INRIA layout, in file order: x y z nx ny nz f_dc_0..2 f_rest_0..3(K-1)-1 opacity scale_0..2 rot_0..3
+    (K = (sh_degree + 1)^2), every one a little-endian float."""
+    n_rest = 3 * ((sh_degree + 1) ** 2 - 1)
+    return (["x", "y", "z", "nx", "ny", "nz"] + [f"f_dc_{i}" for i in range(3)] + [f"f_rest_{i}" for i in range(n_rest)] + ["opacity"]
+            + [f"scale_{i}" for i in range(3)] + [f"rot_{i}" for i in range(4)])
+
+
+def save_ply(gaussian_model: torch.nn.Module, path) -> None:
+    """The model as an INRIA `point_cloud.ply`: binary_little_endian, all properties float.  The values are the stored parameters,
+    bit for bit: the normals zeros, `f_rest` channel-major (`sh_rest.transpose(1, 2).reshape(N, -1)`), `opacity` the logit,
+    `scale_*` the logs, `rot_*` wxyz as stored, not normalised."""
+    m = gaussian_model
+    n, degree = int(m.means.shape[0]), int(m.MAX_SH_DEGREE)
+    names = ply_properties(degree)
+    cpu = lambda t: t.detach().float().cpu()   # noqa: E731
+    cols = torch.cat([cpu(m.means).reshape(n, 3), torch.zeros((n, 3)), cpu(m.sh_0).reshape(n, 3),
+                      cpu(m.sh_rest).transpose(1, 2).reshape(n, -1), cpu(m.logit_opacities).reshape(n, 1), cpu(m.log_scales).reshape(n, 3),
+                      cpu(m.quats).reshape(n, 4)], dim=1).numpy()
+    if cols.shape[1] != len(names):
+        raise ValueError(f"sh_rest has {m.sh_rest.shape[1]} coefficients, SH degree {degree} has {(degree + 1) ** 2 - 1}")
+    body = np.empty((n,), dtype=[(name, "<f4") for name in names])
+    for i, name in enumerate(names):
+        body[name] = cols[:, i]
+    header = "\n".join(["ply", "format binary_little_endian 1.0", f"element vertex {n}"] + [f"property float {name}" for name in names]
+                       + ["end_header"]) + "\n"
+    path = Path(path)
+    path.parent.mkdir(parents=True, exist_ok=True)
+    with open(path, "wb") as f:
+        f.write(header.encode("ascii"))
+        f.write(body.tobytes())
+
+
+def load_ply(path, sh_degree: Optional[int] = None, device: Optional[str] = None, **model_kwargs) -> torch.nn.Module:
+    """A `GaussianModel` from an INRIA `point_cloud.ply` (what `save_ply` writes; what the INRIA code and gsplat's exporters write).
+    The SH degree is taken from the number of `f_rest_*` properties (0, 9, 24, 45, 72: degrees 0-4); a `sh_degree` given must agree.
+    All SH bands are active.  `device=None`: the HIP device when there is one.  `model_kwargs` go to the constructor.
+    ValueError: an ASCII or big-endian body, a property that is not a float, a property set that is not the INRIA one."""
+    with open(path, "rb") as f:
+        raw = f.read()
+    end = raw.find(b"end_header\n")
+    if not raw.startswith(b"ply") or end < 0:
+        raise ValueError(f"{path}: not a PLY file (no 'ply' ... 'end_header')")
+    lines = [ln.strip() for ln in raw[:end].decode("ascii", "replace").splitlines()]
+    lines = [ln for ln in lines[1:] if ln and not ln.startswith(("comment", "obj_info"))]
+    if not lines or lines[0].split() != ["format", "binary_little_endian", "1.0"]:
+        raise ValueError(f"{path}: only 'format binary_little_endian 1.0' is read, got {lines[0] if lines else 'no format line'!r}")
+    n, names, in_vertex = None, [], False
+    for ln in lines[1:]:
+        w = ln.split()
+        if w[0] == "element":
+            if len(w) != 3 or (w[1] != "vertex" and int(w[2]) != 0) or (w[1] == "vertex" and n is not None):
+                raise ValueError(f"{path}: one 'element vertex N' is read, got {ln!r}")
+            in_vertex = w[1] == "vertex"
+            if in_vertex:
+                n = int(w[2])
+        elif w[0] == "property" and in_vertex:
+            if len(w) != 3 or w[1] not in ("float", "float32"):
+                raise ValueError(f"{path}: every property must be a float, got {ln!r}")
+            names.append(w[2])
+        elif w[0] != "property":
+            raise ValueError(f"{path}: unexpected header line {ln!r}")
+    if n is None:
+        raise ValueError(f"{path}: no 'element vertex'")
+    n_rest = sum(nm.startswith("f_rest_") for nm in names)
+    if n_rest not in _PLY_REST_COUNTS:
+        raise ValueError(f"{path}: {n_rest} f_rest properties belong to no SH degree (0, 9, 24, 45, 72 give degrees 0-4)")
+    degree = _PLY_REST_COUNTS[n_rest]
+    if sh_degree is not None and sh_degree != degree:
+        raise ValueError(f"{path}: the file holds SH degree {degree}, sh_degree = {sh_degree} was asked for")
+    want = ply_properties(degree)
+    if sorted(names) != sorted(want):
+        odd = sorted(set(names) ^ set(want))
+        raise ValueError(f"{path}: not the INRIA property set of SH degree {degree}: {odd[:6]} missing, unknown or repeated")
+    start = end + len(b"end_header\n")
+    if len(raw) - start < 4 * len(names) * n:
+        raise ValueError(f"{path}: the body holds {len(raw) - start} bytes, {n} vertices of {len(names)} floats need {4 * len(names) * n}")
+    body = np.frombuffer(raw, dtype=[(nm, "<f4") for nm in names], count=n, offset=start)   # (any property ORDER is read by name)
+
+    def take(cols):
+        return torch.from_numpy(np.stack([body[c] for c in cols], axis=1).astype(np.float32)) if n else torch.zeros((0, len(cols)))
+    coeffs = (degree + 1) ** 2 - 1
+    model = _model.GaussianModel(
+        means=take(["x", "y", "z"]), log_scales=take([f"scale_{i}" for i in range(3)]), quats=take([f"rot_{i}" for i in range(4)]),
+        sh_0=take([f"f_dc_{i}" for i in range(3)]).reshape(n, 1, 3),
+        sh_rest=(take([f"f_rest_{i}" for i in range(n_rest)]).reshape(n, 3, coeffs).transpose(1, 2).contiguous() if coeffs
+                 else torch.zeros((n, 0, 3))),
+        logit_opacities=take(["opacity"]).reshape(n), sh_degree=degree, **model_kwargs)
+    if device is None:
+        device = "cuda" if torch.cuda.is_available() else "cpu"
+    return model.to(device)

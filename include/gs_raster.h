@@ -1277,6 +1277,31 @@ int gs_score_accumulate(void* stream, int C, int64_t N, const float* weight_sum,
                         const int32_t* hits, const int32_t* radii, double* total_weight_sum, float* total_weight_max,
                         int64_t* total_hits, int32_t* views_seen, int32_t* views_hit);
 
+/* ---- k-means on the device (kmeans.py, compress.py; DESIGN.md "Exporting a trained model"): Lloyd's assignment and update for
+ * N points x[N][D] and K centroids [K][D], float32.  The definition is csrc/gs_kmeans.h, one k-ascending fmaf chain per sum:
+ *   score(x, c) = fmaf(-2, dot(x, c), dot(c, c)),  label(x) = the smallest index among the centroids of minimal score (a NaN score
+ *   never wins; none wins: label 0),  dist2(x) = chain_k fmaf(d_k, d_k, acc) with d_k = x_k - c_label,k.
+ * The results are that function of the input bit for bit, whatever the tiling (the product runs on the f32-input MFMA
+ * v_mfma_f32_32x32x2_f32, whose result IS the chain).  No atomics: the same input gives the same bits.  No synchronisation.
+ * gs_kmeans_assign: labels int32[N] in [0, K), dist2 float[N]; two launches (centroids k-major with their norms into the workspace,
+ *   then the fused product + argmin: no score is stored).  workspace: gs_kmeans_workspace_bytes(N, K, D) bytes, 256-byte aligned,
+ *   scratch (every word read is written by the same call).
+ * gs_kmeans_update: one launch.  order int32[N] = the point indices sorted by label with a STABLE sort, seg int32[K+1] = the segment
+ *   offsets of the labels in it (both from the caller's sort / bincount + cumsum).  Cluster j's members order[seg[j] .. seg[j+1]) are
+ *   summed in that order in fp64, one accumulator per (cluster, dimension): centroids[j][d] = (float)(sum / count), counts[j] = the
+ *   number of members.  An empty cluster keeps its centroid's bits.  A segment is clamped to [0, N] and an entry of order outside
+ *   [0, N) is skipped and not counted, never dereferenced.
+ * Refused with GS_ERR_ARG before a launch: N outside [1, GS_KMEANS_MAX_N], K outside [1, GS_KMEANS_MAX_K], D outside
+ * [1, GS_KMEANS_MAX_D], null pointers, a misaligned workspace; gs_kmeans_workspace_bytes returns 0 for such sizes. */
+#define GS_KMEANS_MAX_D 128
+#define GS_KMEANS_MAX_K 16777216      /* 2^24: labels and the padded k-major copy are indexed in int32 / int64 */
+#define GS_KMEANS_MAX_N 1073741824    /* 2^30: point indices are int32 */
+size_t gs_kmeans_workspace_bytes(int64_t N, int64_t K, int D);
+int gs_kmeans_assign(void* stream, int64_t N, int64_t K, int D, const float* x, const float* centroids, int32_t* labels,
+                     float* dist2, void* workspace);
+int gs_kmeans_update(void* stream, int64_t N, int64_t K, int D, const float* x, const int32_t* order, const int32_t* seg,
+                     float* centroids, int32_t* counts);
+
 #ifdef __cplusplus
 }
 #endif

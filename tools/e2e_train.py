@@ -177,7 +177,9 @@ def evaluate(model, eval_datas):
     return {"psnr": psnr / n, "ssim": ss / n, "fps": n / cost, "views": len(eval_datas)}
 
 
-def train(data_dir: Path, steps: int = 3000, captured: bool = True, seed: int = 0, device="cuda:0", eval_every: int = 0, knn: str = "host"):
+def train(data_dir: Path, steps: int = 3000, captured: bool = True, seed: int = 0, device="cuda:0", eval_every: int = 0, knn: str = "host",
+          keep=None):
+    """`keep`: a dict that receives the trained "model" and the held-out "eval_datas" (tools/compress_time.py exports and re-renders them)."""
     from easy_gaussian_splatting_amd.loss import LossComputer
     from easy_gaussian_splatting_amd.model import GaussianModel, build_optimizers
     from easy_gaussian_splatting_amd.scene import Scene
@@ -251,6 +253,8 @@ def train(data_dir: Path, steps: int = 3000, captured: bool = True, seed: int = 
     wall = time.perf_counter() - t0
     final = evaluate(model, eval_datas)
     rep = runner.report() if runner is not None else None
+    if keep is not None:
+        keep["model"], keep["eval_datas"] = model, eval_datas
     return {"mode": "captured" if captured else "eager", "steps": steps, "wall_s": round(wall, 3), "train_iters_per_s": round(steps / wall, 1),
             "psnr": round(final["psnr"], 3), "ssim": round(final["ssim"], 4), "eval_fps": round(final["fps"], 1), "held_out_views": final["views"],
             "train_views": n_train_frames, "n_gaussians_initial": n_hist[0], "n_gaussians_final": model.nbr_gaussians, "n_gaussians": n_hist,
