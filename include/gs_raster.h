@@ -1302,6 +1302,40 @@ int gs_kmeans_assign(void* stream, int64_t N, int64_t K, int D, const float* x, 
 int gs_kmeans_update(void* stream, int64_t N, int64_t K, int D, const float* x, const int32_t* order, const int32_t* seg,
                      float* centroids, int32_t* counts);
 
+/* ---- a triangle mesh out of rendered depth (mesh.py): TSDF fusion of pinhole views into a dense volume and
+ * marching tetrahedra over it.  The definition is csrc/gs_tsdf.h; every result is that function of the input bit for bit.  No
+ * atomics: the same input gives the same bits.  Eager-path kernels: the step guard does not apply.
+ * The volume: dims = {nx, ny, nz} voxels (host array), samples at origin + i * h per axis (origin: host array), linear index
+ * ix + nx * (iy + ny * iz); tsdf float[n] (fresh: 1), weight float[n] (fresh: 0), color float[n][3] (fresh: 0) or NULL.
+ * Every dimension >= 2, h > 0 and 7 * nx * ny * nz < 2^31: anything else is GS_ERR_ARG before a launch, as are null pointers and
+ * the argument errors named below.
+ * gs_tsdf_integrate: one launch folds one view in.  viewmat_dev float[16] (world -> camera, row-major) and K_dev float[9] (fx, fy,
+ *   cx, cy; no skew) are DEVICE memory: a render loop needs no host synchronisation.  image float[H][W][image_stride] is read in
+ *   place -- the buffer rasterization(render_mode="RGB+ED") returns --, the depth in channel depth_channel, the colour in the three
+ *   channels from color_channel (or -1 and color == NULL: depth only); alphas float[H][W] or NULL.  A voxel the view does not
+ *   reach (gs_tsdf.h) keeps all its bits.  trunc > 0 finite, max_weight > 0 (may be +inf), depth_max may be +inf, H*W*stride < 2^31, W and H <= 2^24.
+ * gs_mt_flags: edge_flags int32[7n] (zeroed here; 1: the edge (owner voxel, kind) -- index owner * 7 + kind - 1 -- carries a vertex),
+ *   tri_counts int32[n] (the triangles of the cell whose lowest corner the voxel is), their inclusive scans edge_incl / tri_incl
+ *   (gs_scan_rows_i32; scan_workspace: gs_mt_scan_workspace_ints(dims) int32), and {vertices, faces} into totals_host_mapped --
+ *   int64[2] of page-locked, device-addressable host memory -- followed by a system-scope fence, as gs_pack_flags does it: the one
+ *   host read of an extraction.  min_weight > 0.  A volume with more than 2^31 - 1 triangles overflows tri_incl: the caller checks
+ *   0 <= faces <= 12 n.
+ * gs_mt_vertices: vertices float[n_vertices][3] and -- with color -- colors float[n_vertices][3], numbered by (owner, kind)
+ *   ascending.  gs_mt_faces: faces int32[n_faces][3], ordered by (cell, tetrahedron, triangle), (v1 - v0) x (v2 - v0) pointing
+ *   from inside (tsdf < 0) to outside.  One launch each, none when the total is 0; no store leaves the exactly-sized outputs. */
+int gs_tsdf_integrate(void* stream, const int32_t dims[3], const float origin[3], float h, float trunc, float depth_max,
+                      float min_alpha, float max_weight, const float* viewmat_dev, const float* K_dev, int W, int H,
+                      const float* image, int image_stride, int depth_channel, int color_channel, const float* alphas,
+                      float* tsdf, float* weight, float* color);
+size_t gs_mt_scan_workspace_ints(const int32_t dims[3]);
+int gs_mt_flags(void* stream, const int32_t dims[3], float min_weight, const float* tsdf, const float* weight,
+                int32_t* edge_flags, int32_t* edge_incl, int32_t* tri_counts, int32_t* tri_incl, int32_t* scan_workspace,
+                int64_t* totals_host_mapped);
+int gs_mt_vertices(void* stream, const int32_t dims[3], const float origin[3], float h, const float* tsdf, const float* color,
+                   const int32_t* edge_flags, const int32_t* edge_incl, int64_t n_vertices, float* vertices, float* colors);
+int gs_mt_faces(void* stream, const int32_t dims[3], const float* tsdf, const int32_t* tri_counts, const int32_t* tri_incl,
+                const int32_t* edge_incl, int64_t n_vertices, int64_t n_faces, int32_t* faces);
+
 #ifdef __cplusplus
 }
 #endif
