@@ -1336,6 +1336,43 @@ int gs_mt_vertices(void* stream, const int32_t dims[3], const float origin[3], f
 int gs_mt_faces(void* stream, const int32_t dims[3], const float* tsdf, const int32_t* tri_counts, const int32_t* tri_incl,
                 const int32_t* edge_incl, int64_t n_vertices, int64_t n_faces, int32_t* faces);
 
+/* ---- regularising normals for meshing (normals.py): the normal of every Gaussian in camera space, and the
+ * consistency loss between the blended normals and the normals of the rendered depth.  The definition is csrc/gs_normals.h; every
+ * normal and every gradient is that function of the input bit for bit, the value its terms summed in fp64 in a fixed order.  No
+ * atomics: the same input gives the same bits.  Eager-path kernels: the step guard does not apply.
+ * gs_gauss_normals_fwd: means float[N][3], quats float[N][4] (wxyz, not normalised), scales float[N][3] (raw or activated: only
+ *   their order counts), viewmats float[C][16] (world -> camera, row-major, DEVICE memory) -> normals float[C][N][3], the column of
+ *   R(q / |q|) along the smallest scale, in camera space, faced towards the camera.  gs_gauss_normals_bwd: v_normals float[C][N][3]
+ *   -> v_quats float[N][4], written whole, the cameras summed in their order; means and scales receive nothing (the axis and the
+ *   facing are piecewise constant).  0 <= N < 2^31, C >= 1; N == 0 launches nothing.
+ * gs_normal_loss_fwd: render4 float[H][W][4], 16-byte aligned, read in place -- channels 0..2 the blended normal Nb, channel 3 the
+ *   expected z-depth, what rasterization(render_mode="RGB+ED") returns --, alphas float[H][W], mask float[H][W] or NULL (1 excludes
+ *   a pixel), K_dev float[9] in DEVICE memory (fx, fy, cx, cy; no skew).  A pixel is valid when it is interior, it and its four
+ *   neighbours have alpha >= min_alpha and a finite depth > 0, and the cross product of the central differences has a finite
+ *   squared length >= 1e-30.  rec_dev float[GS_NORMAL_REC_FLOATS]: value = sum(w (1 - dot(Nb, n_d))) / sum(w), w = valid * (1 -
+ *   mask), and 1 / sum(w), both exactly 0 when nothing counts; partials double[gs_normal_loss_partials_doubles(H, W)].
+ *   depth_normals float[H][W][3] or NULL: n_d where the pixel is valid (the mask aside), zeros elsewhere.  rec_dev and partials may
+ *   both be NULL when only depth_normals is wanted.  One image pass over GS_NORMAL_TILE_W x GS_NORMAL_TILE_H tiles and a one-block finish.
+ * gs_normal_loss_bwd: v_loss: the upstream gradient of the value, one float on the device; rec_dev: what the forward wrote.
+ *   v_render4 float[H][W][4], 16-byte aligned, EVERY element written: channels 0..2 the gradient of Nb, channel 3 the gradient of the
+ *   depth (exact zeros with detach_depth = 1); zeros where nothing arrives.  Alphas receive no gradient (validity is a threshold).
+ * H * W * 4 >= 2^31, a NaN min_alpha and null or misaligned pointers are GS_ERR_ARG before any launch. */
+#define GS_NORMAL_TILE_W 64
+#define GS_NORMAL_TILE_H 8
+#define GS_NORMAL_REC_FLOATS 4
+#define GS_NORMAL_REC_VALUE 0
+#define GS_NORMAL_REC_INV_W 1
+int gs_gauss_normals_fwd(void* stream, int64_t N, int C, const float* means, const float* quats, const float* scales,
+                         const float* viewmats, float* normals);
+int gs_gauss_normals_bwd(void* stream, int64_t N, int C, const float* means, const float* quats, const float* scales,
+                         const float* viewmats, const float* v_normals, float* v_quats);
+size_t gs_normal_loss_partials_doubles(int height, int width);
+int gs_normal_loss_fwd(void* stream, int height, int width, const float* K_dev, float min_alpha, const float* render4,
+                       const float* alphas, const float* mask, float* rec_dev, double* partials, float* depth_normals);
+int gs_normal_loss_bwd(void* stream, int height, int width, const float* K_dev, float min_alpha, int detach_depth,
+                       const float* render4, const float* alphas, const float* mask, const float* rec_dev, const float* v_loss,
+                       float* v_render4);
+
 #ifdef __cplusplus
 }
 #endif

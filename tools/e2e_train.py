@@ -15,10 +15,12 @@ transforms_{train,test}.json, tools/make_synthetic_dataset.py's writer conventio
     ->  train_graph.TrainStepGraph (captured) or the eager model / loss / FusedAdam loop
     ->  PSNR / SSIM / fps on the held-out views (eval.py's Evaluator: clamp, mean over views).
 
-    python tools/e2e_train.py [--knn host|device] [steps] [captured|eager|both] [out.json]
+    python tools/e2e_train.py [--knn host|device] [--lambda-normal X] [--normal-from STEP] [--geometry] [steps] [captured|eager|both] [out.json]
 
 `--knn device` takes the initial scales from the device's exact 3-NN search (knn.knn_distances) instead of the host's kd-tree;
-the default, `host`, is the run every recorded figure was made with.
+the default, `host`, is the run every recorded figure was made with.  `--lambda-normal X` (default 0: off) adds X times the
+normal-consistency loss of a second, normal render (normals.py) to the eager loop's total from step `--normal-from` on; `--geometry`
+adds that loss on the held-out views and the size of the 256^3 mesh to every run's result.  Without them the run is the one it was.
 """
 from __future__ import annotations
 
@@ -177,13 +179,34 @@ def evaluate(model, eval_datas):
     return {"psnr": psnr / n, "ssim": ss / n, "fps": n / cost, "views": len(eval_datas)}
 
 
+@torch.no_grad()
+def geometry_report(model, eval_datas, resolution: int = 256):
+    """What `--geometry` adds to a run: the normal-consistency loss of the model on the held-out views (mean) and the size of the mesh
+    `extract_mesh` takes from those views at `resolution`^3."""
+    from easy_gaussian_splatting_amd.mesh import extract_mesh
+    from easy_gaussian_splatting_amd.normals import normal_consistency_loss, render_normals
+    losses = []
+    for d in eval_datas:
+        rn = render_normals(model, d)
+        losses.append(float(normal_consistency_loss(rn["render4"], rn["alphas"], d["K"])))
+    v, f, _ = extract_mesh(model, eval_datas, resolution=resolution, color=False)
+    return {"normal_loss": round(sum(losses) / max(1, len(losses)), 5), "mesh_resolution": resolution, "mesh_vertices": int(v.shape[0]),
+            "mesh_faces": int(f.shape[0])}
+
+
 def train(data_dir: Path, steps: int = 3000, captured: bool = True, seed: int = 0, device="cuda:0", eval_every: int = 0, knn: str = "host",
-          keep=None):
-    """`keep`: a dict that receives the trained "model" and the held-out "eval_datas" (tools/compress_time.py exports and re-renders them)."""
+          keep=None, lambda_normal: float = 0.0, normal_from: int = 0, geometry: bool = False):
+    """`keep`: a dict that receives the trained "model" and the held-out "eval_datas" (tools/compress_time.py exports and re-renders them).
+    `lambda_normal` > 0 adds `lambda_normal * normal_consistency_loss` of a second, normal render to the total from step `normal_from`
+    on (eager loop only); `geometry` adds `geometry_report` to the result."""
     from easy_gaussian_splatting_amd.loss import LossComputer
     from easy_gaussian_splatting_amd.model import GaussianModel, build_optimizers
     from easy_gaussian_splatting_amd.scene import Scene
     from easy_gaussian_splatting_amd.train_graph import TrainStepGraph
+    if lambda_normal > 0 and captured:
+        raise SystemExit("--lambda-normal: the normal term runs in the eager loop only (the captured step is out of its scope)")
+    if lambda_normal > 0:
+        from easy_gaussian_splatting_amd.normals import normal_consistency_loss, render_normals
     cfg = schedule(steps)
     dev = torch.device(device)
     np.random.seed(seed)   # (generate_pointcloud draws from numpy's global generator, as the reference's does)
@@ -221,7 +244,12 @@ def train(data_dir: Path, steps: int = 3000, captured: bool = True, seed: int = 
             runner.step(d, d["image"])
         else:
             out = model(d, clamp=False)
-            lc.get_loss_dict(out["render_img"], d["image"], None)["total"].backward(gradient=one)
+            if lambda_normal > 0 and step >= normal_from:
+                rn = render_normals(model, d)
+                total = lc.get_loss_dict(out["render_img"], d["image"], None)["total"]
+                (total + lambda_normal * normal_consistency_loss(rn["render4"], rn["alphas"], d["K"])).backward(gradient=one)
+            else:
+                lc.get_loss_dict(out["render_img"], d["image"], None)["total"].backward(gradient=one)
             model.update_statistics(d, out)
             opt.step(); opt.zero_grad()
         # refinement: the reference collects statistics inside (refine_start, refine_stop] only -- the step here always does,
@@ -255,16 +283,24 @@ def train(data_dir: Path, steps: int = 3000, captured: bool = True, seed: int = 
     rep = runner.report() if runner is not None else None
     if keep is not None:
         keep["model"], keep["eval_datas"] = model, eval_datas
-    return {"mode": "captured" if captured else "eager", "steps": steps, "wall_s": round(wall, 3), "train_iters_per_s": round(steps / wall, 1),
+    extra = {}
+    if lambda_normal > 0:
+        extra.update(lambda_normal=lambda_normal, normal_from=normal_from)
+    if geometry:
+        extra["geometry"] = geometry_report(model, eval_datas)
+    res = {"mode": "captured" if captured else "eager", "steps": steps, "wall_s": round(wall, 3), "train_iters_per_s": round(steps / wall, 1),
             "psnr": round(final["psnr"], 3), "ssim": round(final["ssim"], 4), "eval_fps": round(final["fps"], 1), "held_out_views": final["views"],
             "train_views": n_train_frames, "n_gaussians_initial": n_hist[0], "n_gaussians_final": model.nbr_gaussians, "n_gaussians": n_hist,
             "active_sh_degree": int(model.active_sh_degree), "schedule": {k: cfg[k] for k in ("refine_start", "refine_stop", "refine_every",
                                                                                              "reset_opacities_every", "sh_degree_interval")},
             "evals": evals, "runner": None if rep is None else {k: rep[k] for k in ("captures", "overflows", "replayed_steps", "rebuilds", "projected_rebuilds", "build_ms",
                                                                              "capture_ms", "pool_allocs", "binning", "overflow_log") if k in rep}}
+    res.update(extra)
+    return res
 
 
-def run(steps: int = 3000, modes=("captured", "eager"), size: int = 400, out_dir=None, eval_every: int = 0, knn: str = "host"):
+def run(steps: int = 3000, modes=("captured", "eager"), size: int = 400, out_dir=None, eval_every: int = 0, knn: str = "host",
+        lambda_normal: float = 0.0, normal_from: int = 0, geometry: bool = False):
     with tempfile.TemporaryDirectory() as tmp:
         root = Path(out_dir) if out_dir else Path(tmp) / "synthetic_dome"
         t0 = time.perf_counter()
@@ -272,7 +308,8 @@ def run(steps: int = 3000, modes=("captured", "eager"), size: int = 400, out_dir
         ds["write_s"] = round(time.perf_counter() - t0, 2)
         res = {"dataset": dict(ds, layout="nerf_synthetic (transforms_{train,test}.json + RGBA PNGs), rendered by the HIP forward from ground-truth "
                                            "Gaussians on a sphere, a ground disc and a box; white background"),
-               "runs": {m: train(root, steps, captured=(m == "captured"), eval_every=eval_every, knn=knn) for m in modes}}
+               "runs": {m: train(root, steps, captured=(m == "captured"), eval_every=eval_every, knn=knn, lambda_normal=lambda_normal,
+                                   normal_from=normal_from, geometry=geometry) for m in modes}}
     if knn != "host":
         res["knn"] = knn
     return res
@@ -297,12 +334,38 @@ def split_knn_option(argv):
     return knn, rest
 
 
+def split_normal_options(argv):
+    """(`--lambda-normal X`, `--normal-from STEP` and `--geometry` taken out of argv -- 0.0, 0 and False when absent --, the rest)."""
+    lam, start, geometry, rest, i = 0.0, 0, False, [], 0
+    while i < len(argv):
+        a = argv[i]
+        name, eq, val = a.partition("=")
+        if name in ("--lambda-normal", "--normal-from"):
+            if not eq:
+                if i + 1 >= len(argv):
+                    raise SystemExit(f"{name} needs a value")
+                val, i = argv[i + 1], i + 1
+            if name == "--lambda-normal":
+                lam = float(val)
+            else:
+                start = int(val)
+        elif a == "--geometry":
+            geometry = True
+        else:
+            rest.append(a)
+        i += 1
+    if not lam >= 0.0 or start < 0:
+        raise SystemExit("--lambda-normal must be >= 0 and --normal-from a step >= 0")
+    return lam, start, geometry, rest
+
+
 if __name__ == "__main__":
     knn_mode, argv = split_knn_option(sys.argv[1:])
+    lambda_normal, normal_from, geometry, argv = split_normal_options(argv)
     steps = int(argv[0]) if len(argv) > 0 else 3000
     which = argv[1] if len(argv) > 1 else "both"
     res = run(steps, ("captured", "eager") if which == "both" else (which,), eval_every=int(os.environ.get("GS_E2E_EVAL_EVERY", "0")),
-              knn=knn_mode)
+              knn=knn_mode, lambda_normal=lambda_normal, normal_from=normal_from, geometry=geometry)
     txt = json.dumps(res)
     if len(argv) > 2:
         open(argv[2], "w").write(txt + "\n")
